@@ -2,7 +2,7 @@
 """Headline benchmark: snippets/sec of one full LSTC_VAD training step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ltn_sht|stn_sht|ltn_ucf|ltn_ubnormal|mixed_ubn_sht]
-                    [--scaling strong|weak] [--feed resident|static] [--dtype fp32|bf16|f32x3]
+                    [--scaling strong|weak] [--feed resident|static] [--dtype fp32|bf16|f32x3] [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): LTN temporal transformer, part_len=3,
 n_head=8, d_k=d_v=256, relative position bias (window 4), d_model=2048, n_hidden=4096, 3 layers, MHA + FFN LayerNorm,
@@ -18,11 +18,21 @@ created before this process touches the GPU); it also runs unchanged under ``pyt
 ``--scaling strong`` (default, the split the metric is quoted on): the global batch stays 32 pairs, rank r
 owns pairs [r*32/N, (r+1)*32/N).  ``--scaling weak``: every rank gets its own 32 pairs.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the exact-f32 MFMA GEMM; achieved = the launches'
-algorithmic 2MNK FLOPs / their HIP-event durations, measured live on the launch stream), `cpu_baseline` (the oracle = CPU
-restatement of the reference, timed on the host cores on a bounded sample) and, at N=1, the sub-objects `static_batch`
-(same step on one fixed batch: no batch formation), `stn_headline` (STN, the literal [64,32,16,2048] input), `bf16` and
-`f32x3` (other GEMM compute modes; never `value`).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the rest of the headline pass, with `roofline` where its events ride inside
+the timed steps (fp32: dominant kernel = the exact-f32 MFMA GEMM; achieved = the launches' algorithmic 2MNK FLOPs / their
+HIP-event durations, measured live on the launch stream).
+
+``--full`` adds everything beyond the headline pass: `roofline` of the 16-bit modes (3 further event steps),
+`cpu_baseline` (the oracle = CPU restatement of the reference, timed on the host cores on a bounded sample), `pcie_inclusive`
+and, at N=1, the sub-objects `static_batch` (same step on one fixed batch: no batch formation), `stn_headline` (STN, the
+literal [64,32,16,2048] input), `bf16` and `f32x3` (other GEMM compute modes; never `value`) and `coteach_loop`.
+
+``--dump-outputs DIR`` writes, right after the timed steps, what the last timed step computed as float32 ``DIR/<name>.npy``
+(rank 0): ``scalars`` (the five scalars ``TrainStep.step`` returns: loss, MIL, err, l1, aux) and, per model, a fixed seeded
+sample of every parameter's gradient (``grad.<param>``) and of the updated weights (``weight.<param>``), at most 64 MB in all.
+The inputs (synthetic bank, batch sampler, weights, dropout seeds) depend on the arguments only, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -97,6 +107,42 @@ def cpu_baseline(cfg_name, threads):
             "sample": f"oracle train_step (fwd+loss+bwd+Adagrad), same model, {2 * bs} videos x {pn} parts x "
                       f"{L} snippets = {snippets} snippets/step, median of {len(timed)} timed steps after 1 warm-up "
                       f"(torch.set_num_threads({threads})), {t:.2f} s/step, min {timed[0]:.2f} max {timed[-1]:.2f}"}
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6       # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(out_dir, scalars, models, per_tensor=65536):
+    """--dump-outputs: what the last timed step computed, as float32 ``out_dir/<name>.npy``.  ``scalars``: the step's returned
+    scalar tensor(s); ``models``: [(prefix, TrainStep)].  Per parameter the same seeded index sample (seed = crc32 of the name,
+    sorted, without replacement; whole tensor when smaller) of its last gradient and of its weight after the optimizer step."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"scalars": torch.stack([s.detach().float().reshape(-1) for s in scalars]).squeeze(0).cpu().numpy()}
+    named = []
+    for pre, ts in models:
+        for tag, mod in (("enc.", ts.encoder), ("head.", ts.head)):
+            named += [(pre + tag + n, p) for n, p in mod.named_parameters() if p.is_floating_point()]
+    per_tensor = max(1, min(per_tensor, DUMP_BUDGET_BYTES // (4 * 2 * max(1, len(named)))))
+    with torch.no_grad():
+        for name, p in named:
+            n = p.numel()
+            if n > per_tensor:
+                idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, per_tensor, replace=False))
+                pick = lambda t: t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            else:
+                pick = lambda t: t.detach().reshape(-1)
+            arrays["weight." + name] = pick(p).float().cpu().numpy()
+            if p.grad is not None:
+                arrays["grad." + name] = pick(p.grad).float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET_BYTES}")
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    return {"dir": out_dir, "files": len(arrays), "MB": round(total / 1e6, 2)}
 
 
 # ---------------------------------------------------------------------------------------------- N-rank launcher
@@ -216,9 +262,9 @@ def main():
     ap.add_argument("--lr_scale", type=float, default=1e-3, help="multiplies the reference learning rates (1e-4 / 1e-2): with "
                     "i.i.d. synthetic features the classifier saturates within two Adagrad steps at the reference rates and the "
                     "backward then runs on near-zero operands; timing does not depend on it")
-    ap.add_argument("--h2d", action="store_true", help="(default at N=1) also time the step with the batch arriving from host memory "
-                    "every step through lstc_vad_amd.feed.PinnedFeeder (reported as pcie_inclusive, never as value)")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the pcie_inclusive pass")
+    ap.add_argument("--h2d", action="store_true", help="(default at N=1 under --full) also time the step with the batch arriving from "
+                    "host memory every step through lstc_vad_amd.feed.PinnedFeeder (reported as pcie_inclusive, never as value)")
+    ap.add_argument("--no-h2d", action="store_true", help="skip the pcie_inclusive pass of --full")
     ap.add_argument("--rank_timeout_s", type=float, default=600.0, help="--gpus N launcher watchdog: stop every rank and fail when "
                     "one is still running after this many seconds (0 = no watchdog)")
     ap.add_argument("--naive-last-layer", action="store_true", help="evaluate the last encoder layer for every token like the "
@@ -240,7 +286,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the N=1 sub-objects (static_batch, stn_headline, bf16, f32x3, coteach_loop)")
     ap.add_argument("--no-coteach", action="store_true", help="skip the coteach_loop sub-object (BASELINE config 3: one timed round of the "
                     "co-teaching loop through the Train/ and Test/ entry points, tools/coteach_round.py)")
+    ap.add_argument("--full", action="store_true", help="besides the headline pass, run what the line reports beyond it: cpu_baseline, "
+                    "pcie_inclusive, the 16-bit modes' roofline event steps and, at N=1, static_batch, stn_headline, bf16, f32x3, "
+                    "coteach_loop (the --no-* options above still skip single parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as "
+                    "float32 DIR/<name>.npy (rank 0): the step's five scalars and seeded samples of every gradient and updated weight")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.nccl_algo:
         os.environ["NCCL_ALGO"] = a.nccl_algo            # inherited by the rank processes launch_ranks starts
     if a.nccl_proto:
@@ -348,8 +401,9 @@ def main():
             src, nxt = None, (lambda: (nf, af, al))
         return ts, nxt, src
 
-    def timed_pass(cfg, dtype, feed=None, steps=None, warmup=None, gemm_events=True):
-        """Fresh weights and optimizer state, W untimed steps, K timed steps between barrier + synchronize; MAX over ranks."""
+    def timed_pass(cfg, dtype, feed=None, steps=None, warmup=None, gemm_events=True, dump_dir=None):
+        """Fresh weights and optimizer state, W untimed steps, K timed steps between barrier + synchronize; MAX over ranks.
+        ``dump_dir``: write the last timed step's outputs there (rank 0) before anything else runs on the models."""
         steps = a.steps if steps is None else steps
         warmup = a.warmup if warmup is None else warmup
         Fn.set_compute_dtype(dtype)
@@ -361,7 +415,11 @@ def main():
                 raise SystemExit("mixed_ubn_sht needs an even number of pairs per rank")
             parts = [make("ltn_ubnormal", bs_local // 2, bs_global // 2, 0, feed), make("ltn_sht", bs_local // 2, bs_global // 2, 1, feed)]
             ms_ = MixedStep([p[0] for p in parts])
-            run_step = lambda: ms_.step([p[1]() for p in parts])[-1]
+            mixed_out = [None]                     # every model's scalars of the latest step (--dump-outputs)
+
+            def run_step():
+                mixed_out[0] = ms_.step([p[1]() for p in parts])
+                return mixed_out[0][-1]
             tss = [p[0] for p in parts]
         else:
             ts, nxt, src = make(cfg, bs_local, bs_global, 0, feed)
@@ -399,6 +457,10 @@ def main():
             marks[i + 1].record()
         sync()
         dt = time.perf_counter() - t0
+        dumped = None
+        if dump_dir and rank == 0:
+            dumped = dump_outputs(dump_dir, mixed_out[0] if mixed else [scs[-1]],
+                                  list(zip(("ltn_ubnormal.", "ltn_sht."), tss)) if mixed else [("", tss[0])])
         step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
         comm = None
         if any(t.comm_events for t in tss):
@@ -420,7 +482,7 @@ def main():
                 t.comm_events = None
         Fn.set_gemm_profiling(None)
         pprof, prof_steps = None, steps
-        if want_events and not inline_events:
+        if want_events and not inline_events and a.full:
             prof, pprof, prof_steps = [], [], 3
             Fn.set_gemm_profiling(prof)
             Fn._pack_prof = pprof
@@ -445,7 +507,7 @@ def main():
         res = {"dt": dt, "steps": steps, "step_ms_median": med, "step_ms_min": step_ms[0], "step_ms_max": step_ms[-1], "prof": prof, "pprof": pprof, "prof_steps": prof_steps, "events_inline": inline_events, "loss_first": float(first[0]), "loss_last": float(last[0]),
                "hbm": torch.cuda.max_memory_allocated(dev), "comm": comm,
                "allreduce_MB": round(sum(t.reducer.payload_bytes() for t in tss if t.reducer is not None) / 1e6, 1),
-               "bank_GB": None if mixed or src is None else round(src.bank_GB, 2)}
+               "bank_GB": None if mixed or src is None else round(src.bank_GB, 2), "dumped": dumped}
         del tss, run_step
         if mixed:
             del parts, ms_
@@ -537,7 +599,7 @@ def main():
     # ---- the CPU baseline leg first (rank 0, N = 1): the GPU passes then run back to back.  The GPU idles during this leg -
     # a utilisation average taken over the whole bench.py run (the driver's gpu_busy) includes these seconds; the line says so.
     cpu_base = None
-    if world == 1 and not a.no_cpu_baseline and a.config != "mixed_ubn_sht":
+    if a.full and world == 1 and not a.no_cpu_baseline and a.config != "mixed_ubn_sht":
         # torch-CPU sgemm on the GPU box's host peaks at 16-32 threads (tools/cpu_threads_scan.py: 1.3 TFLOP/s
         # at 16-32, 0.5 at 128 of 256 hardware threads), so the baseline uses min(32, available) threads
         t_cpu = time.perf_counter()
@@ -547,11 +609,12 @@ def main():
                             "includes these wall_s seconds of host-only work")
 
     # ---- the headline pass -------------------------------------------------------------------------------------------
-    head_res = timed_pass(a.config, a.dtype)
+    head_res = timed_pass(a.config, a.dtype, dump_dir=a.dump_outputs)
     value = snippets_per_step(a.config) * a.steps / head_res["dt"]
 
+    # ---- --full: everything else the line can report ----------------------------------------------------------------
     extras = {}
-    solo = world == 1 and not force_dist and not a.no_extras and a.config != "mixed_ubn_sht"
+    solo = a.full and world == 1 and not force_dist and not a.no_extras and a.config != "mixed_ubn_sht"
     if solo:
         if a.feed == "resident":
             extras["static_batch"] = dict(sub_object(timed_pass(a.config, a.dtype, feed="static", gemm_events=False), a.config, a.dtype),
@@ -585,7 +648,7 @@ def main():
             shutil.rmtree(tmp, ignore_errors=True)
             Fn.set_compute_dtype("fp32")
     pcie = None
-    if (a.h2d or not a.no_h2d) and world == 1 and not force_dist and a.config != "mixed_ubn_sht":
+    if (a.h2d or (a.full and not a.no_h2d)) and world == 1 and not force_dist and a.config != "mixed_ubn_sht":
         from lstc_vad_amd.feed import PinnedFeeder
         Fn.set_compute_dtype(a.dtype)
         ts, nxt, _ = make(a.config, bs_local, bs_global, 0, "static")
@@ -670,6 +733,8 @@ def main():
                           "nccl_env": {k: v for k, v in sorted(os.environ.items()) if k.startswith(("NCCL_", "RCCL_"))}},
                "loss_first_timed_step": head_res["loss_first"], "loss_last_timed_step": head_res["loss_last"],
                "hbm_peak_GB": round(head_res["hbm"] / 1e9, 2), "roofline": roof}
+        if head_res["dumped"]:
+            out["dumped_outputs"] = head_res["dumped"]
         out.update(extras)
         if pcie:
             out["pcie_inclusive"] = pcie

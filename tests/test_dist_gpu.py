@@ -255,6 +255,29 @@ def test_bench_line_contract_and_the_forced_rccl_bucket_path():
     assert abs(f["loss_first_timed_step"] - o["loss_first_timed_step"]) < 1e-6 and abs(f["loss_last_timed_step"] - o["loss_last_timed_step"]) < 1e-6
 
 
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: float32 .npy files of what the last timed step computed - its five scalars (the loss the line
+    reports as loss_last_timed_step), seeded samples of every gradient and updated weight - under 64 MB, and the same arrays from a
+    second run with the same arguments (inputs, weights and dropout seeds are fixed by the arguments; split-K and bias-table
+    gradients are summed by atomics, so the bar is the one of the other run-to-run comparisons, not bit equality)."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    o = _bench_line(["--dump-outputs", str(dirs[0])])
+    assert o["dumped_outputs"]["files"] > 50
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert "scalars.npy" in files and any(f.startswith("grad.enc.") for f in files) and any(f.startswith("weight.head.") for f in files)
+    assert sum(p.stat().st_size for p in dirs[0].iterdir()) < 64e6
+    sc = np.load(dirs[0] / "scalars.npy")
+    assert sc.dtype == np.float32 and sc.shape == (5,) and float(sc[0]) == o["loss_last_timed_step"]
+    f = _bench_line(["--dump-outputs", str(dirs[1])])
+    assert sorted(p.name for p in dirs[1].iterdir()) == files
+    assert abs(f["loss_last_timed_step"] - o["loss_last_timed_step"]) < 1e-6
+    for name in files:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), name
+        off = np.abs(a - b) > 1e-4 * float(np.abs(a).max()) + 1e-7
+        assert float(off.mean()) <= 1e-3, (name, float(np.abs(a - b).max()))
+
+
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_bench_two_ranks_start_themselves_and_report_one_line(dtype):

@@ -6,7 +6,7 @@ TAG=${1:-r05}
 R="$PWD"; OUT=$R/gpurun_out/rank_$TAG; mkdir -p $OUT
 for dt in fp32 bf16; do
   for cfg in ltn_sht ltn_ucf mixed_ubn_sht; do
-    timeout 600 python bench.py --config $cfg --batch_size 4 --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 30 --warmup 5 \
+    timeout 600 python bench.py --full --config $cfg --batch_size 4 --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 30 --warmup 5 \
       > $OUT/${TAG}_rank_${cfg}_bs4_$dt.json 2> $OUT/rank_${cfg}_$dt.err
   done
 done

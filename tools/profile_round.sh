@@ -7,12 +7,12 @@ R="$PWD"; OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd "$R"
 for dt in fp32 bf16; do
   D=gpurun_out/rp_$dt; rm -rf $D
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o p -- python3 bench.py --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 7 --warmup 3 \
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o p -- python3 bench.py --full --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 7 --warmup 3 \
       > $OUT/${TAG}_bench_under_rocprof_$dt.json 2> $OUT/rocprof_$dt.err
   S=$(find $D -name "*kernel_stats.csv" | head -1)
   if [ -n "$S" ]; then
     cp $S $OUT/${TAG}_bench_ltn_sht_kernel_stats_$dt.csv
-    python3 tools/summarize_rocprof.py stats $D $OUT/${TAG}_bench_ltn_sht_kernel_stats_$dt.md "LTN-SHT step, $dt mode, rocprofv3 --kernel-trace --stats -- python3 bench.py --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 7 --warmup 3 (10 steps incl. warm-up; round ${TAG#r})"
+    python3 tools/summarize_rocprof.py stats $D $OUT/${TAG}_bench_ltn_sht_kernel_stats_$dt.md "LTN-SHT step, $dt mode, rocprofv3 --kernel-trace --stats -- python3 bench.py --full --dtype $dt --no-extras --no-cpu-baseline --no-h2d --steps 7 --warmup 3 (10 steps incl. warm-up; round ${TAG#r})"
   fi
   rm -rf $D
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 5: every measurement the profiles/ directory quotes, in one box run.   tools/r05_measure_all.sh
 R="$PWD"; OUT=$R/gpurun_out/r05_final; mkdir -p $OUT
-timeout 900 python bench.py > $OUT/r05_bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/r05_bench_default.json 2> $OUT/bench_default.err
 bash tools/profile_round.sh r05 > $OUT/profile_round.log 2>&1
 cp gpurun_out/prof_r05/* $OUT/ 2>/dev/null
 bash tools/bench_fp32_others.sh r05 > $OUT/others_fp32.txt 2>&1

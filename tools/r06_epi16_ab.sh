@@ -7,7 +7,7 @@ for rep in 1 2 3; do
   for v in r05 epi16a tree; do
     lib=$PWD/build/$v/liblstc_hip.so; [ $v = tree ] && lib=$PWD/lstc_vad_amd/liblstc_hip.so
     for cfg in ltn_sht; do
-      LSTC_LIBRARY=$lib timeout 300 python bench.py --config $cfg --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 \
+      LSTC_LIBRARY=$lib timeout 300 python bench.py --full --config $cfg --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 \
         > $OUT/ab_${cfg}_${v}_$rep.json 2> /dev/null
       python3 -c "import json; o=json.load(open('$OUT/ab_${cfg}_${v}_$rep.json')); print('$cfg $v rep $rep: ms/step', o['ms_per_step'], 'median', o['ms_per_step_median'], 'GEMM TFLOP/s', o['roofline']['achieved'], 'gemm ms', o['roofline']['gemm_ms_per_step'], 'loss', o['loss_last_timed_step'])"
     done
@@ -16,7 +16,7 @@ done
 for v in r05 tree; do
   lib=$PWD/build/$v/liblstc_hip.so; [ $v = tree ] && lib=$PWD/lstc_vad_amd/liblstc_hip.so
   for cfg in stn_sht ltn_ubnormal ltn_ucf; do
-    LSTC_LIBRARY=$lib timeout 300 python bench.py --config $cfg --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 > $OUT/ab_${cfg}_${v}.json 2> /dev/null
+    LSTC_LIBRARY=$lib timeout 300 python bench.py --full --config $cfg --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 > $OUT/ab_${cfg}_${v}.json 2> /dev/null
     python3 -c "import json; o=json.load(open('$OUT/ab_${cfg}_${v}.json')); print('$cfg $v: ms/step', o['ms_per_step'], 'GEMM TFLOP/s', o['roofline']['achieved'])"
   done
 done

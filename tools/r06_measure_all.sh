@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6: every measurement the profiles/ directory quotes for the final code, in one box run.   tools/r06_measure_all.sh
 R="$PWD"; OUT=$R/gpurun_out/r06_final; mkdir -p $OUT
-timeout 900 python bench.py > $OUT/r06_bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/r06_bench_default.json 2> $OUT/bench_default.err
 bash tools/profile_round.sh r06 > $OUT/profile_round.log 2>&1
 cp gpurun_out/prof_r06/* $OUT/ 2>/dev/null
 bash tools/bench_fp32_others.sh r06 > $OUT/others_fp32.txt 2>&1

@@ -26,7 +26,7 @@ for rep in 1 2 3; do
   for v in ref 0 1 2; do
     if [ $v = ref ]; then export LSTC_LIBRARY=$PWD/build/qtail/liblstc_hip.so; unset LSTC_P1_XWALK; else unset LSTC_LIBRARY; export LSTC_P1_XWALK=$v; fi
     for bs in 32 8; do
-      timeout 300 python bench.py --config ltn_sht --batch_size $bs --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 > $OUT/ab_bs${bs}_${v}_$rep.json 2> /dev/null
+      timeout 300 python bench.py --full --config ltn_sht --batch_size $bs --dtype bf16 --no-extras --no-cpu-baseline --no-h2d --steps 20 --warmup 5 > $OUT/ab_bs${bs}_${v}_$rep.json 2> /dev/null
       python3 -c "import json; o=json.load(open('$OUT/ab_bs${bs}_${v}_$rep.json')); print('ltn_sht bs $bs walk $v rep $rep: ms/step', o['ms_per_step'], 'median', o['ms_per_step_median'], 'gemm ms', o['roofline']['gemm_ms_per_step'], 'loss', o['loss_last_timed_step'])"
     done
   done
