@@ -174,7 +174,13 @@ int lstc_colsum_pack1(const void* packed, int64_t rows, int32_t K, float* partia
  * block, exactly the reference's `relative_position_index[:len_q-1, :len_q-1]` slice (:108).
  */
 typedef struct LstcAttnDesc {
-    int32_t N, S, H, dk, dv;        /* dk, dv multiples of 32; S <= 128 */
+    int32_t N, S, H, dk, dv;        /* S <= 128: the short kernels below.  128 < S <= 512: the key-tiled kernels
+                                       (csrc/attention_long.hip) - row (not packed) inputs and outputs only (packed forms ->
+                                       LSTC_E_UNSUPPORTED), probs_ld 0 or S (as for every row-input call: LSTC_E_UNSUPPORTED
+                                       otherwise), in the backward a table gradient only as dtable_chunks > 0 partial tables
+                                       (else LSTC_E_UNSUPPORTED); `variant` is ignored there.  dk or dv not a multiple of 16,
+                                       per-wave bias tables past the LDS budget, and S > 512: LSTC_E_RANGE.  LSTC_BF16 there
+                                       is currently SLOWER than LSTC_F32 */
     int32_t ldq, ldk, ldv, ldo;     /* token strides in elements (normally H*dk / H*dv) */
     int32_t dtype;                  /* LSTC_F32: every product on the exact-f32 MFMA.  LSTC_BF16 (bf16 training mode): the operands of
                                        Q K^T, Pd V and of the four backward products are rounded to bf16 (RNE) in registers and
@@ -247,7 +253,8 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream);
  * (Train/temporal_transformer_shanghaitech.py:123; Train/spatio_transformer_shanghaitech.py:97), so its queries are
  * needed for token 0 only while keys/values still span all S tokens (row 0 carries no relative bias:
  * models/MultiHeadAttention.py:111 adds it to attn[:, :, 1:, 1:]).  Same descriptor; Q/dQ/O/dO hold ONE row per
- * sequence ([N, ldq] / [N, ldo]) and probs is [N, H, S]. */
+ * sequence ([N, ldq] / [N, ldo]) and probs is [N, H, S].  S <= 512 (LSTC_E_RANGE above); S <= 128 runs the original
+ * instantiation unchanged.  (lstc_cls_dot / _wsum / _outer and their packed forms below keep S <= 128.) */
 int lstc_attn_cls_fwd(const LstcAttnDesc* d, void* stream);
 int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream);
 

@@ -793,7 +793,7 @@ int fill_params(const LstcAttnDesc* d, AttnParams& p, bool bwd) {
     const bool gpk = bwd && d->dQ_pack && d->dK_pack && d->dV_pack;
     if (bwd && (!d->dO || (!gpk && (!d->dQ || !d->dK || !d->dV)))) return LSTC_E_NULL;
     if (d->N <= 0 || d->S < 1 || d->H <= 0 || d->dk <= 0 || d->dv <= 0) return LSTC_E_SHAPE;
-    if (d->S > 128) return LSTC_E_RANGE;
+    if (d->S > 512) return LSTC_E_RANGE;                  // 128 < S <= 512: csrc/attention_long.hip (its own preconditions)
     if (d->in_pack_cols < 0 || d->dO_pack_cols < 0) return LSTC_E_SHAPE;
     if (d->in_pack_cols == 0 && (d->ldq < d->H * d->dk || d->ldk < d->H * d->dk || d->ldv < d->H * d->dv)) return LSTC_E_SHAPE;
     if (!(d->O_pack && !bwd) && !(bwd && d->dO_pack_cols > 0) && d->ldo < d->H * d->dv) return LSTC_E_SHAPE;
@@ -861,6 +861,7 @@ int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
     AttnParams p;
     int rc = fill_params(d, p, false);
     if (rc) return rc;
+    if (p.S > 128) return attn_long_fwd_launch(d, p, (hipStream_t)stream);      // key-tiled long-sequence kernels
     if (d->O_pack) {        // packed bf16 output: token rows and head columns fill the pack's even tile grid exactly
         const int64_t M = (int64_t)p.N * p.S;
         if (M % 256 || (p.H * p.dv) % 64 || p.dv % 32 || M * (int64_t)(p.H * p.dv) * 2 > 0x7fffffffLL) return LSTC_E_UNSUPPORTED;
@@ -938,6 +939,7 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) {
     AttnParams p;
     int rc = fill_params(d, p, true);
     if (rc) return rc;
+    if (p.S > 128) return attn_long_bwd_launch(d, p, (hipStream_t)stream);      // key-tiled long-sequence kernels
     hipStream_t st = (hipStream_t)stream;
     const bool bf = d->dtype == LSTC_BF16;
     const int T = (p.S + 31) / 32;
@@ -1054,11 +1056,15 @@ struct ClsParams {
     int has_drop;
 };
 
-constexpr int CLS_MAXS = 128;
+// MAXS = 128 for S <= 128 (the original instantiation: same body, same summation order), CLS_MAXS for 128 < S <= 512 (the
+// key-tiled long-sequence path's range): the scores of a wave's (sequence, head) in LDS and MAXS / 64 of them per lane.
+constexpr int CLS_MAXS = 512;
 
+template <int MAXS>
 __global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p) {
+    constexpr int NJ = MAXS / 64;
     const DropKey dkn = drop_key_now(p.dkey);
-    __shared__ float sc[NT / 64][CLS_MAXS];
+    __shared__ float sc[NT / 64][MAXS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = blockIdx.x * (NT / 64) + wave;
     if (pair >= p.N * p.H) return;
@@ -1074,9 +1080,9 @@ __global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p) {
         if (lane == 0) s[j] = a;
     }
     __builtin_amdgcn_wave_barrier();
-    float v[2], m = -INFINITY;
+    float v[NJ], m = -INFINITY;
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
+    for (int jj = 0; jj < NJ; ++jj) {
         const int j = lane + 64 * jj;
         v[jj] = j < S ? s[j] : -INFINITY;
         m = fmaxf(m, v[jj]);
@@ -1084,14 +1090,14 @@ __global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p) {
     m = wave_max(m);
     float sum = 0.f;
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
+    for (int jj = 0; jj < NJ; ++jj) {
         v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
         sum += v[jj];
     }
     sum = wave_sum(sum);
     const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);       // row 0 of the full tensor
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
+    for (int jj = 0; jj < NJ; ++jj) {
         const int j = lane + 64 * jj;
         if (j < S) {
             float pv = v[jj] / sum;
@@ -1109,10 +1115,12 @@ __global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p) {
     }
 }
 
+template <int MAXS>
 __global__ void __launch_bounds__(NT) attn_cls_bwd_kernel(const ClsParams p) {
+    constexpr int NJ = MAXS / 64;
     const DropKey dkn = drop_key_now(p.dkey);
-    __shared__ float sp[NT / 64][CLS_MAXS];      // dropped probabilities
-    __shared__ float sd[NT / 64][CLS_MAXS];      // d(logit)
+    __shared__ float sp[NT / 64][MAXS];      // dropped probabilities
+    __shared__ float sd[NT / 64][MAXS];      // d(logit)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = blockIdx.x * (NT / 64) + wave;
     if (pair >= p.N * p.H) return;
@@ -1134,9 +1142,9 @@ __global__ void __launch_bounds__(NT) attn_cls_bwd_kernel(const ClsParams p) {
     }
     __builtin_amdgcn_wave_barrier();
     const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
-    float pv[2], dp[2], keep[2], rs = 0.f;
+    float pv[NJ], dp[NJ], keep[NJ], rs = 0.f;
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
+    for (int jj = 0; jj < NJ; ++jj) {
         const int j = lane + 64 * jj;
         pv[jj] = dp[jj] = keep[jj] = 0.f;
         if (j < S) {
@@ -1148,7 +1156,7 @@ __global__ void __launch_bounds__(NT) attn_cls_bwd_kernel(const ClsParams p) {
     }
     rs = wave_sum(rs);
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
+    for (int jj = 0; jj < NJ; ++jj) {
         const int j = lane + 64 * jj;
         if (j < S) {
             ds[j] = pv[jj] * (dp[jj] - rs);
@@ -1203,7 +1211,9 @@ int lstc_attn_cls_fwd(const LstcAttnDesc* d, void* stream) {
     int rc = fill_cls(d, p, false);
     if (rc) return rc;
     const int pairs = p.N * p.H;
-    hipLaunchKernelGGL(attn_cls_fwd_kernel, (pairs + NT / 64 - 1) / (NT / 64), NT, 0, (hipStream_t)stream, p);
+    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
+    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_fwd_kernel<128>, grid, NT, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(attn_cls_fwd_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p);
     return lstc_launch_status();
 }
 
@@ -1212,7 +1222,9 @@ int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream) {
     int rc = fill_cls(d, p, true);
     if (rc) return rc;
     const int pairs = p.N * p.H;
-    hipLaunchKernelGGL(attn_cls_bwd_kernel, (pairs + NT / 64 - 1) / (NT / 64), NT, 0, (hipStream_t)stream, p);
+    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
+    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_bwd_kernel<128>, grid, NT, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(attn_cls_bwd_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p);
     return lstc_launch_status();
 }
 

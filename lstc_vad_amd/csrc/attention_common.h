@@ -1,5 +1,6 @@
 // Shared by the attention translation units (csrc/attention.hip: first / second generation kernels, CLS kernels, the C-ABI entry
-// points; csrc/attention_pk.hip: the packed-operand kernels of the bf16 mode).
+// points; csrc/attention_pk.hip: the packed-operand kernels of the bf16 mode; csrc/attention_long.hip: the key-tiled kernels for
+// 128 < S <= 512).
 #pragma once
 #include "lstc_common.h"
 
@@ -47,5 +48,9 @@ __attribute__((visibility("hidden"))) int attn3_fwd_launch(const AttnParams& p, 
 __attribute__((visibility("hidden"))) int attn3_bwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st);
 // exact-f32 forward on the same structure (f32 operands, dense probs): csrc/attention_pk.hip
 __attribute__((visibility("hidden"))) int attn3f_fwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st);
+// csrc/attention_long.hip: the key-tiled kernels for 128 < S <= 512 (row inputs and outputs only), called by lstc_attn_fwd /
+// lstc_attn_bwd after fill_params; check their own preconditions, then launch
+__attribute__((visibility("hidden"))) int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
+__attribute__((visibility("hidden"))) int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
 
 }  // namespace lstc_attn

@@ -983,7 +983,7 @@ def _attn_dtype():
 def attn_fwd_pack(N, S, H, dv) -> bool:
     """bf16 mode: the attention forward can write O as a packed bf16 operand (include/lstc_hip.h, O_pack)."""
     M = N * S
-    return (_FUSE_PACKS and _packed_kind() == _lib.BF16P and dv % 32 == 0 and M % 256 == 0 and (H * dv) % 64 == 0 and
+    return (_FUSE_PACKS and _packed_kind() == _lib.BF16P and S <= 128 and dv % 32 == 0 and M % 256 == 0 and (H * dv) % 64 == 0 and
             M * H * dv * 2 < 2 ** 31 and M >= max(_x3_min[0], 1) and H * dv >= max(_x3_min[1], 256) and
             M * H * dv * max(_x3_min[0], 256) >= _x3_min[2])
 
