@@ -186,9 +186,11 @@ typedef struct LstcAttnDesc {
                                        Q K^T, Pd V and of the four backward products are rounded to bf16 (RNE) in registers and
                                        contracted by v_mfma_f32_32x32x16_bf16 with f32 accumulation; Q, K, V, O, probs and the
                                        gradients stay f32 in memory, softmax / bias / dropout stay f32.  Taken by the staged
-                                       kernels (S <= 96, dk and dv multiples of 32, 16-B aligned operands, variant 0); every other
-                                       case computes the exact-f32 products (the first-generation loops are latency-bound and got
-                                       slower with bf16 products).  lstc_attn_cls_* : LSTC_F32 only */
+                                       kernels (S <= 96, dk and dv multiples of 32, 16-B aligned operands, variant 0) and by the
+                                       key-tiled kernels (128 < S <= 512: K and Q*scale rounded in the forward, every operand
+                                       of the backward products likewise); every other case (S <= 128 outside the staged
+                                       kernels) computes the exact-f32 products (the first-generation loops are latency-bound
+                                       and got slower with bf16 products).  lstc_attn_cls_* : LSTC_F32 only */
     int32_t index_ld;               /* 0 = no relative bias */
     int32_t table_rows;             /* rows of `table` / `dtable` (backward: size of the per-workgroup LDS accumulator) */
     float   scale;                  /* 1/sqrt(d_k): multiplies Q (reference divides by temperature :49,:103) */
@@ -198,7 +200,12 @@ typedef struct LstcAttnDesc {
     void*  O;
     float* probs;                   /* [N,H,S,S] f32 */
     const float*   table;           /* [rows, H] or NULL */
-    const int64_t* index;           /* or NULL */
+    const int64_t* index;           /* or NULL.  Precondition of the backward (not checked): within each row i of the (S-1) x
+                                       (S-1) block read, distinct columns j map to distinct table rows - both backwards add
+                                       the table gradient by a plain LDS read-modify-write covering many keys of one query
+                                       per instruction.  Every index the models build satisfies it (relative offsets of
+                                       distinct positions differ; tests/test_longseq_host.py checks each); a non-injective
+                                       row loses updates */
     /* backward only */
     const void* dO;                 /* [N,S,H*dv] */
     void* dQ; void* dK; void* dV;   /* [N,S,H*dk|dv], written (not accumulated) */

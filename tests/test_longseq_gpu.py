@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from util import attn_reference, attn_rounded_probs
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -24,24 +26,6 @@ def _rel_index(S, ld):
     i = torch.arange(ld).view(-1, 1)
     j = torch.arange(ld).view(1, -1)
     return (j - i + ld - 1).long(), 2 * ld - 1
-
-
-def _reference(q, k, v, do, N, S, H, dk, dv, table, index, keep, p_drop):
-    """float64 restatement: A = (Q scale) K^T + bias; P = softmax(A); O = (P * keep / (1-p)) V; gradients by autograd."""
-    qd, kd, vd = (t.double().view(N, S, H, -1).transpose(1, 2).requires_grad_(True) for t in (q, k, v))
-    td = table.double().requires_grad_(True) if table is not None else None
-    a = torch.matmul(qd * (1.0 / math.sqrt(dk)), kd.transpose(-1, -2))
-    if td is not None:
-        ix = index[: S - 1, : S - 1].reshape(-1)
-        bias = td[ix].view(S - 1, S - 1, H).permute(2, 0, 1)
-        a = torch.cat([a[:, :, :1, :], torch.cat([a[:, :, 1:, :1], a[:, :, 1:, 1:] + bias], -1)], 2)
-    p = torch.softmax(a, -1)
-    pd = p * keep.double() / (1.0 - p_drop) if p_drop > 0 else p
-    o = torch.matmul(pd, vd)
-    o.backward(do.double().view(N, S, H, dv).transpose(1, 2))
-    g = lambda t: t.grad.transpose(1, 2).reshape(N * S, -1)
-    return (p.detach(), o.detach().transpose(1, 2).reshape(N * S, H * dv), g(qd), g(kd), g(vd),
-            td.grad if td is not None else None)
 
 
 def _run(N, S, H, dk, bias, sliced, p_drop, seed=11, bf16=False):
@@ -65,9 +49,9 @@ def _run(N, S, H, dk, bias, sliced, p_drop, seed=11, bf16=False):
         dq, dk_, dv_, dtab = Fn.attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, out=out)
     finally:
         Fn.set_compute_dtype(prev)
-    keep = Fn.dropout_mask((N, H, S, S), p_drop, seed, DEV) if p_drop > 0 else torch.ones((N, H, S, S), device=DEV)
-    ref = _reference(q, k, v, do, N, S, H, dk, dv, table, index, keep, p_drop)
-    return (probs, o, dq, dk_, dv_, dtab), ref
+    keep = Fn.dropout_mask((N, H, S, S), p_drop, seed, DEV) if p_drop > 0 else None
+    ref = attn_reference(q, k, v, do, N, S, H, dk, dv, table, index, keep, p_drop)
+    return (probs, o, dq, dk_, dv_, dtab), ref, (q, k, table, index)
 
 
 SHAPES = [(4, 129, 2, 16), (8, 145, 2, 32), (2, 257, 8, 256), (1, 512, 1, 64)]
@@ -76,7 +60,8 @@ SHAPES = [(4, 129, 2, 16), (8, 145, 2, 32), (2, 257, 8, 256), (1, 512, 1, 64)]
 @pytest.mark.parametrize("bias,sliced,p_drop", [(False, False, 0.0), (True, False, 0.2), (True, True, 0.0), (True, True, 0.2)])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_long_attention_matches_float64(shape, bias, sliced, p_drop):
-    got, ref = _run(*shape, bias, sliced, p_drop)
+    """Exact-f32 products at the short path's bars: P within 1e-6, the rest within 2e-5 of the tensor's maximum + 1e-6."""
+    got, ref, _ = _run(*shape, bias, sliced, p_drop)
     names = ("probs", "O", "dQ", "dK", "dV", "dtable")
     for name, a, b in zip(names, got, ref):
         if b is None:
@@ -85,17 +70,23 @@ def test_long_attention_matches_float64(shape, bias, sliced, p_drop):
         a, b = a.double(), b.to(a.device)
         assert torch.isfinite(a).all(), name
         err = float((a - b).abs().max())
-        bar = 1e-6 if name == "probs" else 2e-4 * float(b.abs().max()) + 1e-7
+        bar = 1e-6 if name == "probs" else 2e-5 * float(b.abs().max()) + 1e-6
         assert err <= bar, (name, err, bar)
 
 
 @pytest.mark.parametrize("shape", [(4, 129, 2, 16), (2, 257, 8, 256)])
 def test_long_attention_bf16_products_track_float64(shape):
-    got, ref = _run(*shape, True, True, 0.2, bf16=True)
-    for name, a, b in zip(("probs", "O", "dQ", "dK", "dV", "dtable"), got, ref):
-        a, b = a.double().flatten(), b.to(a.device).flatten()
-        cos = float(torch.dot(a, b) / (a.norm() * b.norm()))
-        assert cos > 0.999, (name, cos)
+    """bf16 products: P within 4e-6 of the f64 softmax of the logits of the RNE-rounded operands (K and Q * scale); O and every
+    gradient with a relative Frobenius error above 10x the exact-f32 run's (the bf16 path ran) and below 8e-3."""
+    got, ref, (q, k, table, index) = _run(*shape, True, True, 0.2, bf16=True)
+    exact, _, _ = _run(*shape, True, True, 0.2)
+    N, S, H, dk = shape
+    err_p = float((got[0].double() - attn_rounded_probs(q, k, N, S, H, dk, table, index)).abs().max())
+    assert err_p < 4e-6, err_p
+    for name, a, e, b in zip(("O", "dQ", "dK", "dV", "dtable"), got[1:], exact[1:], ref[1:]):
+        err = float((a.double() - b).norm() / b.norm())
+        err_exact = float((e.double() - b).norm() / b.norm())
+        assert err_exact < 1e-5 and 10 * err_exact < err < 8e-3, (name, err, err_exact)
 
 
 def test_long_backward_is_bit_reproducible():
@@ -146,9 +137,36 @@ def test_return_attn_probabilities_are_normalised_rows():
 
 @pytest.mark.parametrize("cls_only", [False, True])
 def test_training_step_gradients_match_oracle_at_s145(cls_only):
-    """One LTN step at part_len 9 x 16 patches (S = 145) through TrainStep against the oracle (non-zero bias tables): scores,
-    loss and EVERY parameter gradient at the bars of the golden step test (2e-4 of the tensor's maximum).  cls_only=True runs the
-    last layer on the S <= 512 instantiation of the CLS-query kernels."""
+    """One LTN step at part_len 9 x 16 patches (S = 145) through TrainStep against the oracle evaluated in float64 (non-zero
+    bias tables): scores, loss and EVERY parameter gradient at the bars of the golden step test (2e-4 of the tensor's
+    maximum).  cls_only=True runs the last layer on the S <= 512 instantiation of the CLS-query kernels."""
+    _training_step_matches_oracle(9, 16, cls_only)
+
+
+@pytest.mark.parametrize("cls_only", [False, True])
+@pytest.mark.parametrize("part_len,n_patch", [(8, 16), (31, 16), (31, 9)])
+def test_training_step_gradients_match_oracle_long(part_len, n_patch, cls_only):
+    """As the S = 145 step at S = 129 (the first long length), 497 (part_len 31: the largest bias table the models build, 61 x 49
+    rows, 47 KB of per-wave LDS tables in the backward) and 280 (9 patches, window 3: the 61 x 25-row table)."""
+    _training_step_matches_oracle(part_len, n_patch, cls_only)
+
+
+def _oracle_ltn_f64(orc, enc_P, head_P, ecfg, st, nf, af, al):
+    """The LTN branch of oracle.forward_loss with parameters, features and activations in float64 (forward_loss casts the
+    features to f32): the same oracle functions, without the reference's own f32 rounding.  At S = 497 that rounding alone
+    moved the f32 oracle's gradients by up to 11x the bar on some CPUs (ReLU-edge units), while the product stays within
+    half of it."""
+    bs, pn, L, Pn, d = st.batch_size, st.part_num, st.part_len, st.n_patch, ecfg.d_model
+    x = torch.cat([nf.double().reshape(bs * pn, L * Pn, d), af.double().reshape(bs * pn, L * Pn, d)], 0)
+    enc = orc.encoder_forward(enc_P, x, ecfg, True, None)
+    cls = enc[:, 0, :].reshape(bs * 2, pn, d)
+    outputs = orc.head_forward(head_P, cls, "classifier", st.head_dropout, True, None).reshape(bs * 2 * pn, -1)
+    ce = orc.ce_loss(outputs, orc.soft_targets(al, bs, pn, L).double().reshape(bs * 2 * pn, -1))
+    mil, _, _ = orc.mil_loss(outputs[:, 1], bs, pn, 1, st.lambda_1)
+    return outputs, st.lambda_MIL * mil + st.lambda_CE * ce
+
+
+def _training_step_matches_oracle(part_len, n_patch, cls_only):
     from argparse import Namespace
     from lstc_vad_amd import synthetic as syn
     from lstc_vad_amd.engine import TrainStep
@@ -156,8 +174,8 @@ def test_training_step_gradients_match_oracle_at_s145(cls_only):
     from oracle import lstc_oracle as orc
     torch.manual_seed(0)
     ekw = dict(n_head=2, d_k=16, d_v=16, d_model=32, d_inner=64, MHA_layerNorm=True, FFN_layerNorm=True, relative_pe=True,
-               window_size=4, window_depth=9)
-    bs, pn, L, P, d = 2, 3, 9, 16, 32
+               window_size=int(round(n_patch ** 0.5)), window_depth=part_len)
+    bs, pn, L, P, d = 2, 3, part_len, n_patch, 32
     args = Namespace(batch_size=bs, part_num=pn, part_len=L, n_patch=P, lambda_1=0.01, lambda_MIL=1.0, lambda_CE=0.8,
                      temporal_only=False, clip_grad=False)
     enc = Encoder(n_layers=3, MHA_attn_dropout=0.0, MHA_fc_dropout=0.0, FFN_dropout=0.0, weight_init=True, **ekw)
@@ -166,8 +184,8 @@ def test_training_step_gradients_match_oracle_at_s145(cls_only):
         for name, prm in enc.named_parameters():
             if "relative_position_bias_table" in name:
                 prm.normal_(0.0, 0.5)
-    enc_P = {k: (v.detach().clone().requires_grad_(True) if v.is_floating_point() else v.clone()) for k, v in enc.state_dict().items()}
-    head_P = {k: v.detach().clone().requires_grad_(True) for k, v in head.state_dict().items()}
+    enc_P = {k: (v.detach().double().requires_grad_(True) if v.is_floating_point() else v.clone()) for k, v in enc.state_dict().items()}
+    head_P = {k: v.detach().double().requires_grad_(True) for k, v in head.state_dict().items()}
     nf, _, af, al = (torch.from_numpy(x) for x in syn.training_batch(bs, pn, L, P, d, seed=3, threshold=0.6))
     enc, head = enc.to(DEV).train(), head.to(DEV).train()
     ts = TrainStep(args, "LTN", enc, head, 1e-4, 1e-2, 1e-3, cls_only=cls_only)
@@ -177,10 +195,10 @@ def test_training_step_gradients_match_oracle_at_s145(cls_only):
     torch.cuda.synchronize()
     ecfg = orc.EncoderCfg(n_layers=3, MHA_attn_dropout=0.0, MHA_fc_dropout=0.0, FFN_dropout=0.0, **ekw)
     st = orc.StepCfg(mode="LTN", batch_size=bs, part_num=pn, part_len=L, n_patch=P, head_dropout=0.0)
-    ref = orc.forward_loss(enc_P, head_P, ecfg, st, nf, af, al, training=True)
-    ref["loss"].backward()
-    assert float((outputs.detach().cpu() - ref["outputs"].detach().reshape(outputs.shape)).abs().max()) < 1e-4
-    assert abs(float(scalars[0]) - float(ref["loss"].detach())) < 2e-5
+    ref_outputs, ref_loss = _oracle_ltn_f64(orc, enc_P, head_P, ecfg, st, nf, af, al)
+    ref_loss.backward()
+    assert float((outputs.detach().cpu().double() - ref_outputs.detach().reshape(outputs.shape)).abs().max()) < 1e-4
+    assert abs(float(scalars[0]) - float(ref_loss.detach())) < 2e-5
     n = 0
     for mod, refp in ((enc, enc_P), (head, head_P)):
         for k, p in mod.named_parameters():
@@ -189,7 +207,8 @@ def test_training_step_gradients_match_oracle_at_s145(cls_only):
                 assert p.grad is None, k
                 continue
             tol = 2e-4 * float(g.abs().max()) + 1e-7
-            assert float((p.grad.cpu() - g).abs().max()) < tol, (k, float((p.grad.cpu() - g).abs().max()), tol)
+            err = float((p.grad.cpu().double() - g).abs().max())
+            assert err < tol, (k, err, tol)
             n += 1
     assert n > 20
 

@@ -85,3 +85,32 @@ def test_long_sequence_backward_needs_partial_tables(lib):
     a.table_rows = 100000                                             # per-wave LDS tables past 160 KB
     a.dtable_chunks = 1
     assert lib.lstc_attn_bwd(C.byref(a), None) == -5
+
+
+def _row_injective(idx):
+    s = idx.sort(dim=1).values
+    return bool((s[:, 1:] != s[:, :-1]).all())
+
+
+def test_model_indices_are_row_injective_on_every_read_corner():
+    """Both attention backwards add the bias-table gradient by a plain LDS read-modify-write, one query per instruction
+    (csrc/attention.hip attn_bwd_kernel, csrc/attention_long.hip pass Q): correct only if, within one row of the top-left
+    (S-1) x (S-1) corner the kernels read, distinct keys map to distinct table rows (include/lstc_hip.h, `index`).  Every
+    index the models build for S <= 512: the 3-D index for windows 3 and 4 and depths up to 32, the 2-D index for
+    ws^2 + 1 <= 512.  A corner's rows are prefixes of the rows of the largest corner, so checking that one covers every S."""
+    import torch
+    from lstc_vad_amd.models.MultiHeadAttention import relative_position_index_2d, relative_position_index_3d
+    n_checked = 0
+    for ws in (3, 4):
+        for L in range(1, 33):
+            idx = relative_position_index_3d(L, ws)
+            m = min(idx.shape[0], 511)
+            assert _row_injective(idx[:m, :m]), (ws, L)
+            n_checked += 1
+    for ws in range(1, 23):
+        idx = relative_position_index_2d(ws)
+        assert ws * ws + 1 <= 512 and _row_injective(idx), ws
+        n_checked += 1
+    assert n_checked == 86
+    bad = torch.tensor([[0, 1, 0], [2, 1, 0], [0, 1, 2]])        # the check itself sees a repeated table row
+    assert not _row_injective(bad) and _row_injective(bad[1:, :2])

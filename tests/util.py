@@ -1,4 +1,4 @@
-"""Shared helpers for the parity tests: load a golden case, build oracle configs."""
+"""Shared helpers for the parity tests: load a golden case, build oracle configs, the float64 attention reference."""
 import os
 
 import numpy as np
@@ -59,6 +59,50 @@ def host_dropout_keep(i, p, seed):
     h = (h * u(0xC2B2AE3D)) & lo
     h ^= h >> u(16)
     return h >= u(thr)
+
+
+def attn_reference(q, k, v, do, N, S, H, dk, dv, table, index, keep, p_drop, cut_key=None):
+    """float64 restatement of the attention contract (include/lstc_hip.h, "attention"), computed by torch autograd on the
+    device of its inputs: A = (Q / sqrt(d_k)) K^T; A[:, :, 1:, 1:] += table[index[i-1, j-1], h] over the top-left
+    (S-1) x (S-1) corner of a possibly wider index; P = softmax(A); O = (P * keep / (1 - p)) V, head-merged.  Returns
+    (P [N, H, S, S], O [N*S, H*dv], dQ, dK, dV, dtable): the gradients for the output gradient ``do`` (all None when ``do`` is
+    None; dtable None without a table).  ``keep``: the [N, H, S, S] dropout mask (``Fn.dropout_mask``), None without dropout.
+    ``cut_key``: a key left out of the softmax (its logit -inf) - the bar-sensitivity check of the tests."""
+    grad = do is not None
+    qd, kd, vd = (t.detach().double().reshape(N, S, H, -1).transpose(1, 2).requires_grad_(grad) for t in (q, k, v))
+    td = table.detach().double().requires_grad_(grad) if table is not None else None
+    a = torch.matmul(qd * (1.0 / dk ** 0.5), kd.transpose(-1, -2))
+    if td is not None and S > 1:
+        ix = index[: S - 1, : S - 1].reshape(-1).to(td.device)
+        bias = td[ix].view(S - 1, S - 1, H).permute(2, 0, 1)
+        a = a + torch.nn.functional.pad(bias, (1, 0, 1, 0))
+    if cut_key is not None:
+        cut = torch.zeros(S, dtype=torch.bool, device=a.device)
+        cut[cut_key] = True
+        a = a.masked_fill(cut, float("-inf"))
+    p = torch.softmax(a, -1)
+    pd = p * keep.double() / (1.0 - p_drop) if p_drop > 0 else p
+    o = torch.matmul(pd, vd)
+    out = o.detach().transpose(1, 2).reshape(N * S, H * dv)
+    if not grad:
+        return p.detach(), out, None, None, None, None
+    o.backward(do.detach().double().reshape(N, S, H, dv).transpose(1, 2))
+    g = lambda t: t.grad.transpose(1, 2).reshape(N * S, -1)
+    return p.detach(), out, g(qd), g(kd), g(vd), (td.grad if td is not None else None)
+
+
+def attn_rounded_probs(q, k, N, S, H, dk, table, index):
+    """f64 softmax of the logits the bf16 long forward contracts (csrc/attention_long.hip tile_xt): K and Q * scale (an f32
+    product, scale the float LstcAttnDesc.scale) rounded to bf16 (RNE), products and sums in f64, the f32 bias added."""
+    scale = torch.tensor(1.0 / dk ** 0.5, dtype=torch.float32, device=q.device)
+    qs = (q * scale).to(torch.bfloat16).double().reshape(N, S, H, dk).transpose(1, 2)
+    kr = k.to(torch.bfloat16).double().reshape(N, S, H, dk).transpose(1, 2)
+    a = torch.matmul(qs, kr.transpose(-1, -2))
+    if table is not None and S > 1:
+        ix = index[: S - 1, : S - 1].reshape(-1).to(q.device)
+        bias = table.double()[ix].view(S - 1, S - 1, H).permute(2, 0, 1)
+        a = a + torch.nn.functional.pad(bias, (1, 0, 1, 0))
+    return torch.softmax(a, -1)
 
 
 _BATCH_CACHE = {}
