@@ -265,6 +265,31 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream);
 int lstc_attn_cls_fwd(const LstcAttnDesc* d, void* stream);
 int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream);
 
+/* Attention masks (reference models/MultiHeadAttention.py:105-106: attn.masked_fill(mask == 0, -1e9) before the relative bias
+ * and the softmax).  One byte per (n, h, query i, key j), read as mask[n*sn + h*sh + i*sq + j*sk]; a stride of 0 broadcasts
+ * that axis, so a key-padding mask [N, 1, 1, S] is (S, 0, 0, 1) and costs S bytes per sequence.  The caller owns the extent:
+ * every offset up to (N-1)*sn + (H-1)*sh + (S-1)*sq + (S-1)*sk must lie inside the buffer.
+ *   forward : where the byte is 0 the logit is -1e9f IN PLACE OF the scaled q.k; the bias is added afterwards in f32 (for
+ *             |bias| < 32 the sum rounds back to -1e9f).  In a row that keeps a key every masked key has probability exactly
+ *             0.0; a fully masked row is uniform, 1/S in every column - no -inf, no NaN.  probs hold the masked P before dropout;
+ *             the dropout index of (n, h, i, j) is unchanged.
+ *   backward: dV and rowsum(dP' * P) are as unmasked (the saved P carries the mask); the dA that feeds dQ and dK is zero at
+ *             masked positions, the dA that feeds dtable is not (it differs from zero only in fully masked rows).
+ * Same descriptor as the unmasked calls, row operands only: O_pack, dQ_pack / dK_pack / dV_pack, in_pack_cols > 0 and
+ * dO_pack_cols > 0 return LSTC_E_UNSUPPORTED.  S <= 128 runs the masked instantiation of the first-generation kernels (any d_k,
+ * d_v, alignment; exact-f32 products for LSTC_BF16 too; `variant` is not consulted), 128 < S <= 512 that of the key-tiled kernels
+ * (d_k, d_v multiples of 16, else LSTC_E_RANGE; LSTC_BF16 = bf16 products), the CLS forms row 0 of the mask (sq is not read).
+ * m or m->mask NULL: LSTC_E_NULL; a negative stride: LSTC_E_SHAPE - all checked before any launch.  Results are
+ * bit-reproducible run to run (fixed summation order, one writer per element, no float atomics with dtable_chunks > 0). */
+typedef struct LstcAttnMask {
+    const uint8_t* mask;            /* 0 = masked, non-zero = kept */
+    int64_t sn, sh, sq, sk;         /* element strides over (n, h, query i, key j); 0 = broadcast */
+} LstcAttnMask;
+int lstc_attn_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);
+int lstc_attn_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);
+int lstc_attn_cls_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);   /* query row 0: sq is ignored */
+int lstc_attn_cls_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);
+
 /* Re-associated CLS attention of the last layer: with one query per (sequence, head) the key / value projections are
  * never materialised — score[n,h,j] = u[n,h].x[n,j] with u = (q_h*scale) Wk_h, and o[n,h] = Wv_h (sum_j p[n,h,j] x[n,j]) —
  * which removes the layer's two [N*S,d]x[d,H*dk] projection GEMMs and their four backward GEMMs (same reference lines

@@ -20,7 +20,8 @@ EPI_BIAS, EPI_RELU, EPI_DROPOUT, EPI_RESIDUAL, EPI_RELU_MASK, EPI_ACCUM, EPI_OUT
 EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 
 EXPORTS = (
-    "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd", "lstc_cls_dot", "lstc_cls_wsum",
+    "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
+    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_cls_dot", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
@@ -57,6 +58,11 @@ class AttnDesc(C.Structure):
                 ("O_pack", C.c_void_p),
                 ("in_pack_cols", C.c_int32), ("Q_col0", C.c_int32), ("K_col0", C.c_int32), ("V_col0", C.c_int32),
                 ("dO_pack_cols", C.c_int32), ("dO_col0", C.c_int32), ("probs_ld", C.c_int32)]
+
+
+class AttnMask(C.Structure):
+    """LstcAttnMask (include/lstc_hip.h): a byte mask and its element strides over (n, h, query, key); 0 = broadcast."""
+    _fields_ = [("mask", C.c_void_p), ("sn", C.c_int64), ("sh", C.c_int64), ("sq", C.c_int64), ("sk", C.c_int64)]
 
 
 class PackItem(C.Structure):
@@ -104,6 +110,10 @@ def load():
         "lstc_attn_bwd": [C.POINTER(AttnDesc), vp],
         "lstc_attn_cls_fwd": [C.POINTER(AttnDesc), vp],
         "lstc_attn_cls_bwd": [C.POINTER(AttnDesc), vp],
+        "lstc_attn_fwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
+        "lstc_attn_bwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
+        "lstc_attn_cls_fwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
+        "lstc_attn_cls_bwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
         "lstc_cls_dot": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
         "lstc_cls_wsum": [vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_outer": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],

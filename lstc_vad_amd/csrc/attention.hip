@@ -188,164 +188,27 @@ __device__ __forceinline__ void lds_times_rows(const float* __restrict__ Alds, c
     }
 }
 
-template <int T>
-__global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const AttnParams p) {
-    const DropKey dkn = drop_key_now(p.dkey);
-    constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
-    constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int n = ATTN_CHUNK, h = ATTN_HEAD, S = p.S;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    float* Ob = p.O + (size_t)n * S * p.ldo + (size_t)h * p.dv;
-
-#pragma unroll 1
-    for (int t = wave; t < T * T; t += NT / 64) {
-        const int ti = t / T, tj = t % T;
-        if (32 * ti >= S || 32 * tj >= S) continue;   // fully padded tile: rows/cols are rewritten below
-        const floatx16 acc = tile_abt<BF>(Qb, p.ldq, 32 * ti, Kb, p.ldk, 32 * tj, S, p.dk, p.scale, p.vec_qk);
-        store_tile_lds<LD>(sm, ti, tj, acc);
-    }
-    __syncthreads();
-
-    float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
-    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
-#pragma unroll 1
-    for (int i = wave; i < SP; i += NT / 64) {
-        float* row = sm + i * LD;
-        if (i >= S) {
-            for (int j = lane; j < SP; j += 64) row[j] = 0.f;
-            continue;
-        }
-        float v[NJ];
-        float m = -INFINITY;
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int j = lane + 64 * jj;
-            float x = -INFINITY;
-            if (j < S) {
-                x = row[j];
-                if (p.index_ld > 0 && i >= 1 && j >= 1)
-                    x += p.table[(size_t)p.index[(size_t)(i - 1) * p.index_ld + (j - 1)] * p.H + h];
-            }
-            v[jj] = x;
-            m = fmaxf(m, x);
-        }
-        m = wave_max(m);
-        float s = 0.f;
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
-            s += v[jj];
-        }
-        s = wave_sum(s);
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int j = lane + 64 * jj;
-            if (j < SP) {
-                float pv = 0.f;
-                if (j < S) {
-                    pv = v[jj] / s;
-                    pr_base[(size_t)i * S + j] = pv;
-                    if (p.has_drop) pv = drop_keep(flat0 + (uint32_t)(i * S + j), dkn) ? pv * dkn.scale : 0.f;
-                }
-                row[j] = pv;
-            }
-        }
-    }
-    __syncthreads();
-    lds_times_rows<T, false, BF>(sm, Vb, p.ldv, S, p.dv, 1.f, Ob, p.ldo, reinterpret_cast<__bf16*>(p.Op), (uint32_t)n * (uint32_t)S,
-                             (uint32_t)((h * p.dv) >> 5), (uint32_t)p.kbo);
-}
-
-template <int T>
-__global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const AttnParams p) {
-    const DropKey dkn = drop_key_now(p.dkey);
-    constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
-    constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Dm = sm;                 // dP~ then dA
-    float* Pm = sm + SP * LD;       // dropped probabilities
-    float* tacc = sm + 2 * SP * LD; // [NT/64][table_rows] bias-table gradient of this head, one copy per wave
-    const int h = ATTN_HEAD, S = p.S;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool has_bias = p.index_ld > 0 && p.dtable != nullptr;
-    if (has_bias)
-        for (int i = threadIdx.x; i < (NT / 64) * p.table_rows; i += NT) tacc[i] = 0.f;
-    // a wave owns its copy: within one row i the S - 1 columns map to distinct table rows (relative offsets of distinct
-    // positions differ), and a wave walks its rows in order, so plain read-modify-write is race-free and the sum order fixed
-    float* const tw = tacc + wave * p.table_rows;
-    const int n_begin = ATTN_CHUNK * p.n_per_wg;
-    const int n_end = min(p.N, n_begin + p.n_per_wg);
-#pragma unroll 1
-    for (int n = n_begin; n < n_end; ++n) {
-        const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-        const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-        const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-        const float* dOb = p.dO + (size_t)n * S * p.ldo + (size_t)h * p.dv;
-        __syncthreads();   // previous sequence's LDS readers are done
-#pragma unroll 1
-        for (int t = wave; t < T * T; t += NT / 64) {
-            const int ti = t / T, tj = t % T;
-            if (32 * ti >= S || 32 * tj >= S) continue;
-            const floatx16 acc = tile_abt<BF>(dOb, p.ldo, 32 * ti, Vb, p.ldv, 32 * tj, S, p.dv, 1.f, p.vec_v);
-            store_tile_lds<LD>(Dm, ti, tj, acc);
-        }
-        __syncthreads();
-        const float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
-        const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
-#pragma unroll 1
-        for (int i = wave; i < SP; i += NT / 64) {
-            float* drow = Dm + i * LD;
-            float* prow = Pm + i * LD;
-            if (i >= S) {
-                for (int j = lane; j < SP; j += 64) drow[j] = prow[j] = 0.f;
-                continue;
-            }
-            float pv[NJ], dp[NJ], keep[NJ];
-            float s = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < NJ; ++jj) {
-                const int j = lane + 64 * jj;
-                pv[jj] = dp[jj] = keep[jj] = 0.f;
-                if (j < S) {
-                    pv[jj] = pr_base[(size_t)i * S + j];
-                    keep[jj] = p.has_drop ? (drop_keep(flat0 + (uint32_t)(i * S + j), dkn) ? dkn.scale : 0.f) : 1.f;
-                    dp[jj] = drow[j] * keep[jj];
-                    s += dp[jj] * pv[jj];
-                }
-            }
-            s = wave_sum(s);
-#pragma unroll
-            for (int jj = 0; jj < NJ; ++jj) {
-                const int j = lane + 64 * jj;
-                if (j < SP) {
-                    const float da = pv[jj] * (dp[jj] - s);      // zero for j >= S
-                    drow[j] = da;
-                    prow[j] = pv[jj] * keep[jj];
-                    if (has_bias && i >= 1 && j >= 1 && j < S)
-                        tw[p.index[(size_t)(i - 1) * p.index_ld + (j - 1)]] += da;
-                }
-            }
-        }
-        __syncthreads();
-        lds_times_rows<T, true, BF>(Pm, dOb, p.ldo, S, p.dv, 1.f, p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv, p.ldv);
-        lds_times_rows<T, false, BF>(Dm, Kb, p.ldk, S, p.dk, p.scale, p.dQ + (size_t)n * S * p.ldq + (size_t)h * p.dk, p.ldq);
-        lds_times_rows<T, true, BF>(Dm, Qb, p.ldq, S, p.dk, p.scale, p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk, p.ldk);
-    }
-    if (has_bias) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < p.table_rows; i += NT) {
-            float v = tacc[i];
-#pragma unroll
-            for (int w = 1; w < NT / 64; ++w) v += tacc[w * p.table_rows + i];
-            if (p.table_partials) p.dtable[((size_t)ATTN_CHUNK * p.table_rows + i) * p.H + h] = v;
-            else atomicAdd(&p.dtable[(size_t)i * p.H + h], v);
-        }
-    }
-}
+// First-generation kernels attn_fwd_kernel<T> / attn_bwd_kernel<T>: the kernel text is in attention_gen1.inc, included once under the kernels' own names
+// (unmasked: exactly the text they always had) and once as the *_masked_kernel instantiations, which take the attention mask
+// (attention_common.h MaskParams) as a second argument.
+#define ATTN_MASKED 0
+#define ATTN_MASK_PARAM
+#define ATTN1_FWD attn_fwd_kernel
+#define ATTN1_BWD attn_bwd_kernel
+#include "attention_gen1.inc"
+#undef ATTN_MASKED
+#undef ATTN_MASK_PARAM
+#undef ATTN1_FWD
+#undef ATTN1_BWD
+#define ATTN_MASKED 1
+#define ATTN_MASK_PARAM , const MaskParams mk
+#define ATTN1_FWD attn_fwd_masked_kernel
+#define ATTN1_BWD attn_bwd_masked_kernel
+#include "attention_gen1.inc"
+#undef ATTN_MASKED
+#undef ATTN_MASK_PARAM
+#undef ATTN1_FWD
+#undef ATTN1_BWD
 
 // =====================================================================================================
 // Second-generation backward (T <= 3, NW = 4 waves for T <= 2 and 8 for T = 3; d_k and d_v multiples of 32, 16-B aligned operands): same math, same LDS score tiles,
@@ -848,6 +711,17 @@ int fill_packed_inputs(const LstcAttnDesc* d, AttnParams& p, bool bwd) {
     return 0;
 }
 
+// The mask of the *_masked entry points, checked before anything is launched.  Masked calls take row operands only: every packed
+// form of the descriptor is refused, and the range rules are those of the unmasked calls.
+int fill_mask(const LstcAttnDesc* d, const LstcAttnMask* m, MaskParams& mk) {
+    if (!d || !m || !m->mask) return LSTC_E_NULL;
+    if (m->sn < 0 || m->sh < 0 || m->sq < 0 || m->sk < 0) return LSTC_E_SHAPE;
+    if (d->O_pack || d->dQ_pack || d->dK_pack || d->dV_pack || d->in_pack_cols > 0 || d->dO_pack_cols > 0) return LSTC_E_UNSUPPORTED;
+    if (d->S > 512 || (d->S > 128 && (d->dk % 16 || d->dv % 16))) return LSTC_E_RANGE;
+    mk.m = m->mask; mk.sn = m->sn; mk.sh = m->sh; mk.sq = m->sq; mk.sk = m->sk;
+    return 0;
+}
+
 template <typename Kern>
 void set_lds(Kern k, size_t lds) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1031,6 +905,81 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) {
     return lstc_launch_status();
 }
 
+// Masked forms (include/lstc_hip.h, "attention masks"): the first-generation kernels for S <= 128 (any d_k, d_v, alignment; exact-f32
+// products in both dtypes), the key-tiled kernels above.  `variant` is not consulted.
+int lstc_attn_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
+    MaskParams mk;
+    int rc = fill_mask(d, m, mk);
+    if (rc) return rc;
+    AttnParams p;
+    rc = fill_params(d, p, false);
+    if (rc) return rc;
+    if (!d->O) return LSTC_E_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.S > 128) return attn_long_fwd_masked_launch(d, p, mk, st);
+    const int T = (p.S + 31) / 32;
+    const size_t lds = (size_t)(32 * T) * (32 * T + 1) * sizeof(float);
+    dim3 grid = ATTN_GRID(p.N, p.H);
+#define LSTC_FWDM(TT)                                                             \
+    do {                                                                          \
+        static LstcDevOnce once;                                                  \
+        const int dev_ = once.begin();                                            \
+        if (dev_ >= 0) { set_lds(attn_fwd_masked_kernel<TT>, 160 * 1024); once.end(dev_); } \
+        hipLaunchKernelGGL(attn_fwd_masked_kernel<TT>, grid, NT, lds, st, p, mk);  \
+    } while (0)
+    switch (T) {
+        case 1: LSTC_FWDM(1); break;
+        case 2: LSTC_FWDM(2); break;
+        case 3: LSTC_FWDM(3); break;
+        default: LSTC_FWDM(4); break;
+    }
+#undef LSTC_FWDM
+    return lstc_launch_status();
+}
+
+int lstc_attn_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
+    MaskParams mk;
+    int rc = fill_mask(d, m, mk);
+    if (rc) return rc;
+    AttnParams p;
+    rc = fill_params(d, p, true);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.S > 128) return attn_long_bwd_masked_launch(d, p, mk, st);
+    const int T = (p.S + 31) / 32;
+    p.table_rows = (d->index_ld > 0 && d->dtable) ? d->table_rows : 0;
+    if (d->index_ld > 0 && d->dtable && d->table_rows <= 0) return LSTC_E_SHAPE;
+    const size_t lds = ((size_t)2 * (32 * T) * (32 * T + 1) + (size_t)(NT / 64) * p.table_rows) * sizeof(float);
+    if (lds > 160 * 1024) return LSTC_E_RANGE;
+    int npw = (int)(((int64_t)p.N * p.H + 4095) / 4096);      // as lstc_attn_bwd
+    if (npw < 1) npw = 1;
+    if (npw > 8) npw = 8;
+    p.table_partials = 0;
+    if (p.table_rows > 0 && d->dtable_chunks > 0) {
+        npw = (p.N + d->dtable_chunks - 1) / d->dtable_chunks;
+        p.table_partials = 1;
+    }
+    p.n_per_wg = npw;
+    const int chunks_ = (p.N + npw - 1) / npw;
+    dim3 grid = ATTN_GRID(chunks_, p.H);
+    if (p.table_partials && chunks_ != d->dtable_chunks) return LSTC_E_SHAPE;
+#define LSTC_BWDM(TT)                                                             \
+    do {                                                                          \
+        static LstcDevOnce once;                                                  \
+        const int dev_ = once.begin();                                            \
+        if (dev_ >= 0) { set_lds(attn_bwd_masked_kernel<TT>, 160 * 1024); once.end(dev_); } \
+        hipLaunchKernelGGL(attn_bwd_masked_kernel<TT>, grid, NT, lds, st, p, mk);  \
+    } while (0)
+    switch (T) {
+        case 1: LSTC_BWDM(1); break;
+        case 2: LSTC_BWDM(2); break;
+        case 3: LSTC_BWDM(3); break;
+        default: LSTC_BWDM(4); break;
+    }
+#undef LSTC_BWDM
+    return lstc_launch_status();
+}
+
 }  // extern "C"
 
 // =====================================================================================================
@@ -1060,126 +1009,27 @@ struct ClsParams {
 // key-tiled long-sequence path's range): the scores of a wave's (sequence, head) in LDS and MAXS / 64 of them per lane.
 constexpr int CLS_MAXS = 512;
 
-template <int MAXS>
-__global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p) {
-    constexpr int NJ = MAXS / 64;
-    const DropKey dkn = drop_key_now(p.dkey);
-    __shared__ float sc[NT / 64][MAXS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pair = blockIdx.x * (NT / 64) + wave;
-    if (pair >= p.N * p.H) return;
-    const int n = pair / p.H, h = pair % p.H, S = p.S;
-    const float* q = p.Q + (size_t)n * p.ldq + (size_t)h * p.dk;
-    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    float* s = sc[wave];
-    for (int j = 0; j < S; ++j) {
-        float a = 0.f;
-        for (int c = lane; c < p.dk; c += 64) a += (q[c] * p.scale) * Kb[(size_t)j * p.ldk + c];
-        a = wave_sum(a);
-        if (lane == 0) s[j] = a;
-    }
-    __builtin_amdgcn_wave_barrier();
-    float v[NJ], m = -INFINITY;
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-        const int j = lane + 64 * jj;
-        v[jj] = j < S ? s[j] : -INFINITY;
-        m = fmaxf(m, v[jj]);
-    }
-    m = wave_max(m);
-    float sum = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-        v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
-        sum += v[jj];
-    }
-    sum = wave_sum(sum);
-    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);       // row 0 of the full tensor
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-        const int j = lane + 64 * jj;
-        if (j < S) {
-            float pv = v[jj] / sum;
-            p.probs[((size_t)n * p.H + h) * S + j] = pv;
-            if (p.has_drop) pv = drop_keep(flat0 + (uint32_t)j, dkn) ? pv * dkn.scale : 0.f;
-            s[j] = pv;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    float* o = p.O + (size_t)n * p.ldo + (size_t)h * p.dv;
-    for (int c = lane; c < p.dv; c += 64) {
-        float a = 0.f;
-        for (int j = 0; j < S; ++j) a += s[j] * Vb[(size_t)j * p.ldv + c];
-        o[c] = a;
-    }
-}
-
-template <int MAXS>
-__global__ void __launch_bounds__(NT) attn_cls_bwd_kernel(const ClsParams p) {
-    constexpr int NJ = MAXS / 64;
-    const DropKey dkn = drop_key_now(p.dkey);
-    __shared__ float sp[NT / 64][MAXS];      // dropped probabilities
-    __shared__ float sd[NT / 64][MAXS];      // d(logit)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pair = blockIdx.x * (NT / 64) + wave;
-    if (pair >= p.N * p.H) return;
-    const int n = pair / p.H, h = pair % p.H, S = p.S;
-    const float* q = p.Q + (size_t)n * p.ldq + (size_t)h * p.dk;
-    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    const float* dO = p.dO + (size_t)n * p.ldo + (size_t)h * p.dv;
-    float* dKb = p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    float* dVb = p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    float* pd = sp[wave];
-    float* ds = sd[wave];
-    // dP~_j = dO . V_j
-    for (int j = 0; j < S; ++j) {
-        float a = 0.f;
-        for (int c = lane; c < p.dv; c += 64) a += dO[c] * Vb[(size_t)j * p.ldv + c];
-        a = wave_sum(a);
-        if (lane == 0) ds[j] = a;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
-    float pv[NJ], dp[NJ], keep[NJ], rs = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-        const int j = lane + 64 * jj;
-        pv[jj] = dp[jj] = keep[jj] = 0.f;
-        if (j < S) {
-            pv[jj] = p.probs[((size_t)n * p.H + h) * S + j];
-            keep[jj] = p.has_drop ? (drop_keep(flat0 + (uint32_t)j, dkn) ? dkn.scale : 0.f) : 1.f;
-            dp[jj] = ds[j] * keep[jj];
-            rs += dp[jj] * pv[jj];
-        }
-    }
-    rs = wave_sum(rs);
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-        const int j = lane + 64 * jj;
-        if (j < S) {
-            ds[j] = pv[jj] * (dp[jj] - rs);
-            pd[j] = pv[jj] * keep[jj];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // dV_j = Pd_j dO ; dK_j = scale dA_j q ; dq = scale sum_j dA_j K_j
-    for (int c = lane; c < p.dv; c += 64) {
-        const float g = dO[c];
-        for (int j = 0; j < S; ++j) dVb[(size_t)j * p.ldv + c] = pd[j] * g;
-    }
-    float* dq = p.dQ + (size_t)n * p.ldq + (size_t)h * p.dk;
-    for (int c = lane; c < p.dk; c += 64) {
-        const float qs = q[c] * p.scale;
-        float a = 0.f;
-        for (int j = 0; j < S; ++j) {
-            a += ds[j] * Kb[(size_t)j * p.ldk + c];
-            dKb[(size_t)j * p.ldk + c] = ds[j] * qs;
-        }
-        dq[c] = a * p.scale;
-    }
-}
+// attn_cls_fwd_kernel<MAXS> / attn_cls_bwd_kernel<MAXS>: the kernel text is in attention_cls.inc, included once under the kernels' own names
+// (unmasked: exactly the text they always had) and once as the *_masked_kernel instantiations, which take the attention mask
+// (attention_common.h MaskParams) as a second argument.
+#define ATTN_MASKED 0
+#define ATTN_MASK_PARAM
+#define ATTN_CLS_FWD attn_cls_fwd_kernel
+#define ATTN_CLS_BWD attn_cls_bwd_kernel
+#include "attention_cls.inc"
+#undef ATTN_MASKED
+#undef ATTN_MASK_PARAM
+#undef ATTN_CLS_FWD
+#undef ATTN_CLS_BWD
+#define ATTN_MASKED 1
+#define ATTN_MASK_PARAM , const MaskParams mk
+#define ATTN_CLS_FWD attn_cls_fwd_masked_kernel
+#define ATTN_CLS_BWD attn_cls_bwd_masked_kernel
+#include "attention_cls.inc"
+#undef ATTN_MASKED
+#undef ATTN_MASK_PARAM
+#undef ATTN_CLS_FWD
+#undef ATTN_CLS_BWD
 
 int fill_cls(const LstcAttnDesc* d, ClsParams& p, bool bwd) {
     if (!d) return LSTC_E_NULL;
@@ -1225,6 +1075,36 @@ int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream) {
     const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
     if (p.S <= 128) hipLaunchKernelGGL(attn_cls_bwd_kernel<128>, grid, NT, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_cls_bwd_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p);
+    return lstc_launch_status();
+}
+
+// Masked forms: row 0 of the mask (LstcAttnMask.sq is not read).
+int lstc_attn_cls_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
+    MaskParams mk;
+    int rc = fill_mask(d, m, mk);
+    if (rc) return rc;
+    ClsParams p;
+    rc = fill_cls(d, p, false);
+    if (rc) return rc;
+    if (!d->O) return LSTC_E_NULL;
+    const int pairs = p.N * p.H;
+    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
+    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_fwd_masked_kernel<128>, grid, NT, 0, (hipStream_t)stream, p, mk);
+    else hipLaunchKernelGGL(attn_cls_fwd_masked_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p, mk);
+    return lstc_launch_status();
+}
+
+int lstc_attn_cls_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
+    MaskParams mk;
+    int rc = fill_mask(d, m, mk);
+    if (rc) return rc;
+    ClsParams p;
+    rc = fill_cls(d, p, true);
+    if (rc) return rc;
+    const int pairs = p.N * p.H;
+    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
+    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_bwd_masked_kernel<128>, grid, NT, 0, (hipStream_t)stream, p, mk);
+    else hipLaunchKernelGGL(attn_cls_bwd_masked_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p, mk);
     return lstc_launch_status();
 }
 

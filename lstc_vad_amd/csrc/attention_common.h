@@ -37,6 +37,17 @@ struct AttnParams {
     int pld;                // row pitch of `probs` in floats (packed-input kernels: a multiple of 4, >= S; else S)
 };
 
+// Attention mask of the *_masked entry points (LstcAttnMask): one byte per (n, h, query i, key j) through four element strides
+// (0 = broadcast); byte 0 = masked.  A second kernel argument of the masked instantiations only: AttnParams and the unmasked
+// kernels are as they were.
+struct MaskParams {
+    const uint8_t* m;
+    int64_t sn, sh, sq, sk;
+};
+// the logit of a masked position, in place of the scaled q.k and before the relative bias (the reference's masked_fill value);
+// -1e9f + bias rounds back to -1e9f for |bias| < 32, so a fully masked row comes out uniform and nothing is ever -inf or NaN
+constexpr float ATTN_MASK_FILL = -1e9f;
+
 typedef __bf16 attn_h8 __attribute__((ext_vector_type(8)));
 typedef float attn_f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 attn_h2 __attribute__((ext_vector_type(2)));
@@ -52,5 +63,8 @@ __attribute__((visibility("hidden"))) int attn3f_fwd_launch(const AttnParams& p,
 // lstc_attn_bwd after fill_params; check their own preconditions, then launch
 __attribute__((visibility("hidden"))) int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
 __attribute__((visibility("hidden"))) int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
+// the same with an attention mask (lstc_attn_fwd_masked / lstc_attn_bwd_masked): the masked instantiations of the same kernels
+__attribute__((visibility("hidden"))) int attn_long_fwd_masked_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams& mk, hipStream_t st);
+__attribute__((visibility("hidden"))) int attn_long_bwd_masked_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams& mk, hipStream_t st);
 
 }  // namespace lstc_attn

@@ -1002,11 +1002,42 @@ def attn_packed_inputs(N, S, H, dk, dv) -> bool:
             dk % 64 == 0 and dv % 64 == 0 and N * S * H * (2 * dk + dv) * 2 < 2 ** 31)
 
 
-def attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_drop, seed, packed=False):
+def attn_mask_arg(mask, N, H, S, device=None):
+    """Normalise an attention mask for the ``*_masked`` entry points (include/lstc_hip.h, LstcAttnMask): anything torch broadcasts
+    against [N, H, S, S] - [S, S], [1, 1, S, S], [N, 1, 1, S] (key padding), [N, 1, S, S], [N, H, S, S] - of any dtype, zero =
+    masked (the reference's ``masked_fill(mask == 0, -1e9)``).  Returns ``(m, strides)``: ``m`` a uint8 view of shape
+    [N, H, S, S] with values in {0, 1} over a buffer of the mask's OWN size (``expand``: a broadcast axis has stride 0, nothing
+    is copied out to [N, H, S, S]), ``strides`` its four element strides.  Pure torch; runs on CPU tensors.  ``device``: where the
+    bytes should live (moved before the expand)."""
+    if not torch.is_tensor(mask):
+        raise TypeError(f"attention mask: expected a tensor, got {type(mask).__name__}")
+    full = (int(N), int(H), int(S), int(S))
+    if mask.dim() > 4:
+        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against [N, H, S, S] = {list(full)}")
+    shape = (1,) * (4 - mask.dim()) + tuple(mask.shape)
+    if any(a != b and a != 1 for a, b in zip(shape, full)):
+        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against [N, H, S, S] = {list(full)}")
+    m8 = (mask != 0).to(torch.uint8).reshape(shape)
+    if device is not None:
+        m8 = m8.to(device)
+    m = m8.expand(full)
+    return m, tuple(0 if full[i] == 1 else int(m.stride(i)) for i in range(4))
+
+
+def _mask_desc(mask):
+    """ctypes LstcAttnMask of a normalised mask (``attn_mask_arg``'s result)."""
+    m, st = mask
+    return _lib.AttnMask(dev_ptr(m), *st)
+
+
+def attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_drop, seed, packed=False, mask=None):
     """``packed``: O comes back ONLY as a ``Packed`` bf16 operand (returns (Packed, probs)) - see ``attn_fwd_pack``.
-    ``q`` may be the ``Packed`` fused Q | K | V projection (``k``, ``v`` None): the packed-input kernels, ``packed`` implied."""
+    ``q`` may be the ``Packed`` fused Q | K | V projection (``k``, ``v`` None): the packed-input kernels, ``packed`` implied.
+    ``mask``: a normalised attention mask (``attn_mask_arg``) - lstc_attn_fwd_masked; row operands only."""
     M = N * S
     in_pack = isinstance(q, Packed)
+    if mask is not None and (in_pack or packed):
+        raise RuntimeError("attn_fwd: a masked call takes row operands only (no packed inputs or outputs)")
     dev = q.buf.device if in_pack else q.device
     packed = packed or in_pack
     if packed:
@@ -1041,6 +1072,9 @@ def attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_drop, seed, packed=False)
         d.O_pack = dev_ptr(obuf)
     else:
         d.O = dev_ptr(o)
+    if mask is not None:
+        check(_lib.load().lstc_attn_fwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_fwd_masked")
+        return o, probs
     check(_lib.load().lstc_attn_fwd(C.byref(d), stream_ptr()), "lstc_attn_fwd")
     if packed:
         return Packed(obuf, M, H * dv, _lib.BF16P), probs
@@ -1055,12 +1089,15 @@ def attn_bwd_packs(N, S, H, dk, dv) -> bool:
             M >= max(_x3_min[0], 1) and H * min(dk, dv) >= max(_x3_min[1], 256) and M * H * min(dk, dv) * max(_x3_min[0], 256) >= _x3_min[2])
 
 
-def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, out=None, packed=False):
+def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, out=None, packed=False, mask=None):
     """``packed``: return dQ, dK, dV as ``Packed`` bf16 operands (no f32 copies) - see ``attn_bwd_packs``; ``packed="fused"``:
     ONE Packed [N*S, H*(2 dk + dv)] with the column blocks dQ | dK | dV (gradient of the fused Q|K|V projection).
     ``q`` and ``do`` may be ``Packed`` (the fused Q | K | V projection, the packed input gradient of fc; ``k``, ``v`` None): the
-    packed-input kernel, ``packed="fused"`` implied."""
+    packed-input kernel, ``packed="fused"`` implied.
+    ``mask``: the normalised mask the forward ran with (``attn_mask_arg``) - lstc_attn_bwd_masked; row operands only."""
     in_pack = isinstance(q, Packed)
+    if mask is not None and (in_pack or packed):
+        raise RuntimeError("attn_bwd: a masked call takes row operands only (no packed inputs or outputs)")
     if in_pack:
         if not (isinstance(do, Packed) and do.K == H * dv and do.kind == _lib.BF16P):
             raise RuntimeError("attn_bwd: a packed Q | K | V operand needs dO as a packed bf16 operand [N*S, H*d_v] too")
@@ -1114,7 +1151,10 @@ def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, ou
     else:
         d.dQ, d.dK, d.dV = dev_ptr(dq), dev_ptr(dk_), dev_ptr(dv_)
     d.variant = _ATTN_VARIANT
-    check(_lib.load().lstc_attn_bwd(C.byref(d), stream_ptr()), "lstc_attn_bwd")
+    if mask is not None:
+        check(_lib.load().lstc_attn_bwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_bwd_masked")
+    else:
+        check(_lib.load().lstc_attn_bwd(C.byref(d), stream_ptr()), "lstc_attn_bwd")
     if parts is not None:
         dtable = colsum(parts).view(table.shape[0], H)
     if packed == "fused":
@@ -1275,7 +1315,8 @@ class MHAFunction(torch.autograd.Function):
         xa = xp if xp is not None else x2
         wqkv = _fused_qkv_weight(wq, wk, wv)
         qkv_p = None
-        if (xp is not None and wqkv is not None and wqkv.shape[0] == H * (2 * dk + dv) and attn_packed_inputs(N, S, H, dk, dv) and
+        mask = cfg.get("mask")          # normalised attention mask (attn_mask_arg), not differentiable: row operands, masked kernels
+        if (mask is None and xp is not None and wqkv is not None and wqkv.shape[0] == H * (2 * dk + dv) and attn_packed_inputs(N, S, H, dk, dv) and
                 packed_out_shape(N * S, wqkv.shape[0]) and packed_out_shape(N * S, H * dv) and wfc.shape[0] >= max(_x3_min[0], 1)):
             # bf16 mode: Q | K | V exist only as ONE packed bf16 operand - the projection writes it (LSTC_EPI_OUT_PACK), the attention
             # core reads it (forward and backward) and writes O / dQ | dK | dV as packs: no f32 activation between the two GEMMs
@@ -1297,12 +1338,12 @@ class MHAFunction(torch.autograd.Function):
         if qkv_p is not None:
             op, probs = attn_fwd(qkv_p, None, None, N, S, H, dk, dv, table, index, p_attn, seed_a)
             o = None
-        elif xp is not None and attn_fwd_pack(N, S, H, dv) and wfc.shape[0] >= max(_x3_min[0], 1):
+        elif mask is None and xp is not None and attn_fwd_pack(N, S, H, dv) and wfc.shape[0] >= max(_x3_min[0], 1):
             # bf16 mode: the attention output exists only as the packed bf16 operand of fc (and of fc's weight gradient)
             op, probs = attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_attn, seed_a, packed=True)
             o = None
         else:
-            o, probs = attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_attn, seed_a)
+            o, probs = attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_attn, seed_a, mask=mask)
             op = maybe_pack(o)
         y = gemm(op if op is not None else o, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=x2)
         if cfg["layer_norm"]:
@@ -1336,20 +1377,22 @@ class MHAFunction(torch.autograd.Function):
             rq, rk = wq.shape[0], wk.shape[0]
             if qkv_p is not None:
                 dqkv, _, _, dtable = attn_bwd(do, qkv_p, None, None, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"])
-            elif xp is not None and attn_bwd_packs(N, S, H, dk, dv) and N * S * wqkv.shape[0] * 2 < 2 ** 31:
+            elif c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv) and N * S * wqkv.shape[0] * 2 < 2 ** 31:
                 # bf16 mode: the attention backward writes dQ | dK | dV straight into ONE packed bf16 operand
                 dqkv, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], packed="fused")
             else:
                 dqkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
                 outs = (dqkv[:, :rq], dqkv[:, rq: rq + rk], dqkv[:, rq + rk:])
-                _, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], out=outs)
+                _, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], out=outs,
+                                           mask=c.get("mask"))
             dwqkv = wgrad(dqkv, x2, xp, out=fused_grad_sink(wq, wk, wv))      # one TN GEMM for the three weight gradients
             dwq, dwk, dwv = deliver(wq, dwqkv[:rq]), deliver(wk, dwqkv[rq: rq + rk]), deliver(wv, dwqkv[rq + rk:])
             if ctx.needs_input_grad[0]:
                 dx = gemm(dqkv, wqkv, residual=dy).view(N, S, -1)   # dQ Wq + dK Wk + dV Wv + residual in one GEMM (K = 3*H*dk)
         else:
             dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
-                                            packed=xp is not None and attn_bwd_packs(N, S, H, dk, dv))
+                                            packed=c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv),
+                                            mask=c.get("mask"))
             dwq = deliver(wq, wgrad(dq, x2, xp, out=grad_sink(wq)))
             dwk = deliver(wk, wgrad(dk_, x2, xp, out=grad_sink(wk)))
             dwv = deliver(wv, wgrad(dv_, x2, xp, out=grad_sink(wv)))
@@ -1553,7 +1596,8 @@ class MHAClsAssocFunction(torch.autograd.Function):
         return dx, deliver(wq, dwq), deliver(wk, dwk), deliver(wv, dwv), dwfc, dln_w, dln_b, dtable, None
 
 
-def attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_drop, seed):
+def attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_drop, seed, mask=None):
+    """``mask``: a normalised attention mask (``attn_mask_arg``); the CLS kernels read its query row 0."""
     oc = torch.empty((N, H * dv), device=qc.device, dtype=torch.float32)
     probs = torch.empty((N, H, S), device=qc.device, dtype=torch.float32)
     d = AttnDesc()
@@ -1562,11 +1606,14 @@ def attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_drop, seed):
     d.dtype, d.scale = F32, 1.0 / (dk ** 0.5)
     d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
     d.Q, d.K, d.V, d.O, d.probs = dev_ptr(qc), dev_ptr(k), dev_ptr(v), dev_ptr(oc), dev_ptr(probs)
-    check(_lib.load().lstc_attn_cls_fwd(C.byref(d), stream_ptr()), "lstc_attn_cls_fwd")
+    if mask is not None:
+        check(_lib.load().lstc_attn_cls_fwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_cls_fwd_masked")
+    else:
+        check(_lib.load().lstc_attn_cls_fwd(C.byref(d), stream_ptr()), "lstc_attn_cls_fwd")
     return oc, probs
 
 
-def attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, p_drop, seed):
+def attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, p_drop, seed, mask=None):
     dqc, dk_, dv_ = torch.empty_like(qc), torch.empty_like(k), torch.empty_like(v)
     d = AttnDesc()
     d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
@@ -1575,7 +1622,10 @@ def attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, p_drop, seed):
     d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
     d.Q, d.K, d.V, d.probs = dev_ptr(qc), dev_ptr(k), dev_ptr(v), dev_ptr(probs)
     d.dO, d.dQ, d.dK, d.dV = dev_ptr(doc), dev_ptr(dqc), dev_ptr(dk_), dev_ptr(dv_)
-    check(_lib.load().lstc_attn_cls_bwd(C.byref(d), stream_ptr()), "lstc_attn_cls_bwd")
+    if mask is not None:
+        check(_lib.load().lstc_attn_cls_bwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_cls_bwd_masked")
+    else:
+        check(_lib.load().lstc_attn_cls_bwd(C.byref(d), stream_ptr()), "lstc_attn_cls_bwd")
     return dqc, dk_, dv_
 
 
@@ -1609,7 +1659,7 @@ class MHAClsFunction(torch.autograd.Function):
             _note(cfg["site"] + "attn_dropout#cls", p_attn, seed_a, (N, H, S, S))     # row 0 of the full mask
         if p_fc > 0:
             _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
-        oc, probs = attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_attn, seed_a)
+        oc, probs = attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_attn, seed_a, mask=cfg.get("mask"))
         y = gemm(oc, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xc)
         if cfg["layer_norm"]:
             z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6)
@@ -1636,7 +1686,7 @@ class MHAClsFunction(torch.autograd.Function):
         df = dropout_apply(dy, c["p_fc"], c["seed_f"]) if c["p_fc"] > 0 else dy
         dwfc = deliver(wfc, wgrad(df, oc, out=grad_sink(wfc)))
         doc = gemm(df, wfc)
-        dqc, dk_, dv_ = attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, c["p_attn"], c["seed_a"])
+        dqc, dk_, dv_ = attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, c["p_attn"], c["seed_a"], mask=c.get("mask"))
         dwq = deliver(wq, wgrad(dqc, xc, out=grad_sink(wq)))
         dwk, dwv = deliver(wk, wgrad(dk_, x2, out=grad_sink(wk))), deliver(wv, wgrad(dv_, x2, out=grad_sink(wv)))
         dx = None

@@ -111,14 +111,15 @@ class Encoder(nn.Module):
             enc_output = DropoutFunction.apply(enc_output, self.position_dropout.p, "position_dropout")
         return enc_output
 
-    def forward_cls(self, enc_output, enc_output_hi=None):
-        """``forward(x)[:, 0, :]`` without computing the rows nobody reads: the train / eval loops consume only the
+    def forward_cls(self, enc_output, enc_output_hi=None, src_mask=None):
+        """``forward(x, src_mask)[:, 0, :]`` without computing the rows nobody reads: the train / eval loops consume only the
         CLS token of the last layer (Train/temporal_transformer_shanghaitech.py:123,
         Train/spatio_transformer_shanghaitech.py:97), so the last layer evaluates its query, output projection and
         FFN for that token alone (K/V still use every token).  Saves ~25 % of the step's FLOPs at 3 layers."""
         # enc_output_hi: optional second half of the batch (the abnormal sequences) so the caller need not cat
+        # src_mask: the full layers get the mask, the CLS-only last layer its query row 0; the bf16 activation stream stays off
         n = len(self.layer_stack)
-        act = self._act_chain(enc_output, enc_output_hi, list(self.layer_stack[:-1]))
+        act = src_mask is None and self._act_chain(enc_output, enc_output_hi, list(self.layer_stack[:-1]))
         enc_output = self._embed(enc_output, enc_output_hi, pack_only=act)
         # the CLS-only layer reads the stream's pack too when its re-associated form applies (lstc_cls_dot_pack ...), else f32 rows
         cls_pack = act and isinstance(enc_output, PackedAct) and \
@@ -127,8 +128,8 @@ class Encoder(nn.Module):
             layer.pos_ffn._emit_pack = i + 1 < n - 1          # f32 activations: the CLS-only last layer reads no packed operand
             # bf16 activation stream: every block hands a pack on
             layer.slf_attn._act16_out, layer.pos_ffn._act16_out = act, act and (i + 1 < n - 1 or cls_pack)
-            enc_output = layer(enc_output)[0]
-        out = self.layer_stack[-1].forward_cls(enc_output)
+            enc_output = layer(enc_output, slf_attn_mask=src_mask)[0]
+        out = self.layer_stack[-1].forward_cls(enc_output, slf_attn_mask=src_mask)
         drop_producer_packs()
         return out
 

@@ -7,7 +7,7 @@ arithmetic runs in ``MHAFunction`` (GEMM -> fused attention core -> GEMM epilogu
 import torch
 from torch import nn
 
-from ..functional import MHAClsAssocFunction, MHAClsFunction, MHAFunction, PackedAct
+from ..functional import MHAClsAssocFunction, MHAClsFunction, MHAFunction, PackedAct, attn_mask_arg
 
 
 def relative_position_index_3d(window_depth: int, window_size: int) -> torch.Tensor:
@@ -84,12 +84,19 @@ class MultiHeadAttention(nn.Module):
         from ..functional import cls_pack_ok
         return self._cls_assoc_ok(S) and cls_pack_ok(N, S, self.n_head, self.d_model)
 
-    def forward_cls(self, x):
-        """CLS-query attention for the last encoder layer: x [N, S, d] -> [N, d] (== ``forward(x, x, x)[0][:, 0]``)."""
+    def forward_cls(self, x, mask=None):
+        """CLS-query attention for the last encoder layer: x [N, S, d] -> [N, d] (== ``forward(x, x, x, mask)[0][:, 0]``).
+        ``mask`` as in ``forward``; only its query row 0 is read."""
         cfg = dict(n_head=self.n_head, d_k=self.d_k, d_v=self.d_v, layer_norm=self.layerNorm_flag,
                    attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
                    site=self._site)
-        if isinstance(x, PackedAct):       # bf16 activation stream: Encoder checked cls_takes_pack(); the pack's bf16 view goes through autograd
+        if mask is not None:
+            # the re-associated form does its softmax inside lstc_cls_dot and stays unmasked: the K/V-projecting form takes the mask
+            if isinstance(x, PackedAct):
+                raise NotImplementedError("an attention mask needs the f32 activations (Encoder keeps the bf16 stream off when one is given)")
+            cfg.update(mask=attn_mask_arg(mask, x.shape[0], self.n_head, x.shape[1], device=x.device))
+            fn = MHAClsFunction
+        elif isinstance(x, PackedAct):       # bf16 activation stream: Encoder checked cls_takes_pack(); the pack's bf16 view goes through autograd
             cfg.update(act_shape=x.shape)
             fn, x = MHAClsAssocFunction, x.t
         else:
@@ -102,10 +109,11 @@ class MultiHeadAttention(nn.Module):
                                     cfg)
 
     def forward(self, q, k, v, mask=None, return_attn=False, return_attn_v=False):
-        if mask is not None:
-            raise NotImplementedError("attention masks are never passed on the LSTC_VAD path (SURVEY 8a A3)")
+        """``mask``: anything torch broadcasts against [N, H, S, S], any dtype, zero = masked (reference :105-106: the logit of a
+        masked position is -1e9 before the relative bias and the softmax; a fully masked row comes out uniform)."""
         if not (q is k and k is v):
-            raise NotImplementedError("only self-attention (q is k is v) is on the LSTC_VAD path")
+            raise NotImplementedError("only self-attention (q is k is v): the attention kernels have one sequence length, and the "
+                                      "reference's relative-bias slice needs len_q == len_k anyway")
         has_bias = self.relative_pe or self.relative_pe_2D
         if self.relative_pe_2D and q.shape[1] - 1 != self.window_size ** 2:
             raise RuntimeError("relative_pe_2D needs window_size**2 patch tokens (models/MultiHeadAttention.py:114)")
@@ -113,6 +121,10 @@ class MultiHeadAttention(nn.Module):
                    attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
                    site=self._site)
         act = isinstance(q, PackedAct)
+        if mask is not None:
+            if act:
+                raise NotImplementedError("an attention mask needs the f32 activations (Encoder keeps the bf16 stream off when one is given)")
+            cfg.update(mask=attn_mask_arg(mask, q.shape[0], self.n_head, q.shape[1], device=q.device))
         if act:        # bf16 activation stream (functional.PackedAct): the pack's bf16 view goes through autograd, the shape rides in cfg
             if return_attn_v:
                 raise NotImplementedError("return_attn_v needs the f32 activations (Encoder keeps them when it is asked for)")
