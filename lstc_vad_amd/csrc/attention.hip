@@ -188,27 +188,194 @@ __device__ __forceinline__ void lds_times_rows(const float* __restrict__ Alds, c
     }
 }
 
-// First-generation kernels attn_fwd_kernel<T> / attn_bwd_kernel<T>: the kernel text is in attention_gen1.inc, included once under the kernels' own names
-// (unmasked: exactly the text they always had) and once as the *_masked_kernel instantiations, which take the attention mask
-// (attention_common.h MaskParams) as a second argument.
-#define ATTN_MASKED 0
-#define ATTN_MASK_PARAM
-#define ATTN1_FWD attn_fwd_kernel
-#define ATTN1_BWD attn_bwd_kernel
-#include "attention_gen1.inc"
-#undef ATTN_MASKED
-#undef ATTN_MASK_PARAM
-#undef ATTN1_FWD
-#undef ATTN1_BWD
-#define ATTN_MASKED 1
-#define ATTN_MASK_PARAM , const MaskParams mk
-#define ATTN1_FWD attn_fwd_masked_kernel
-#define ATTN1_BWD attn_bwd_masked_kernel
-#include "attention_gen1.inc"
-#undef ATTN_MASKED
-#undef ATTN_MASK_PARAM
-#undef ATTN1_FWD
-#undef ATTN1_BWD
+// First-generation kernels (S <= 128), forward and backward.
+// MASKED: where the mask byte of (n, h, i, j) is 0 the scaled logit is replaced by ATTN_MASK_FILL before the bias is added; in the
+// backward the saved P carries the mask already, so dV and the row sums do not change.  The unmasked instantiation compiles to
+// what the kernel was before masks existed (tools/attn_isa_diff.py).
+template <int T, bool MASKED>
+__global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+    const DropKey dkn = drop_key_now(p.dkey);
+    constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
+    constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = ATTN_CHUNK, h = ATTN_HEAD, S = p.S;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
+    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
+    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
+    float* Ob = p.O + (size_t)n * S * p.ldo + (size_t)h * p.dv;
+
+#pragma unroll 1
+    for (int t = wave; t < T * T; t += NT / 64) {
+        const int ti = t / T, tj = t % T;
+        if (32 * ti >= S || 32 * tj >= S) continue;   // fully padded tile: rows/cols are rewritten below
+        const floatx16 acc = tile_abt<BF>(Qb, p.ldq, 32 * ti, Kb, p.ldk, 32 * tj, S, p.dk, p.scale, p.vec_qk);
+        store_tile_lds<LD>(sm, ti, tj, acc);
+    }
+    __syncthreads();
+
+    float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
+    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    const uint8_t* mk_nh = nullptr;
+    if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
+    // sq == 0 (a key-padding mask): every query row reads the same S bytes - once per (sequence, head), ahead of the row loop,
+    // instead of one more exposed load per row of these latency-bound loops
+    bool mk_rows_alike = false;
+    uint8_t mk0[NJ];
+    if constexpr (MASKED) {
+        mk_rows_alike = mk.sq == 0;
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) mk0[jj] = (mk_rows_alike && lane + 64 * jj < S) ? mk_nh[(int64_t)(lane + 64 * jj) * mk.sk] : (uint8_t)1;
+    }
+#pragma unroll 1
+    for (int i = wave; i < SP; i += NT / 64) {
+        float* row = sm + i * LD;
+        if (i >= S) {
+            for (int j = lane; j < SP; j += 64) row[j] = 0.f;
+            continue;
+        }
+        float v[NJ];
+        float m = -INFINITY;
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            const int j = lane + 64 * jj;
+            float x = -INFINITY;
+            if (j < S) {
+                x = row[j];
+                // a predicated select before the bias; the wave owns row i and its lanes walk j: one 64-byte run of mask bytes
+                if constexpr (MASKED) x = (mk_rows_alike ? mk0[jj] : mk_nh[(int64_t)i * mk.sq + (int64_t)j * mk.sk]) ? x : ATTN_MASK_FILL;
+                if (p.index_ld > 0 && i >= 1 && j >= 1)
+                    x += p.table[(size_t)p.index[(size_t)(i - 1) * p.index_ld + (j - 1)] * p.H + h];
+            }
+            v[jj] = x;
+            m = fmaxf(m, x);
+        }
+        m = wave_max(m);
+        float s = 0.f;
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
+            s += v[jj];
+        }
+        s = wave_sum(s);
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            const int j = lane + 64 * jj;
+            if (j < SP) {
+                float pv = 0.f;
+                if (j < S) {
+                    pv = v[jj] / s;
+                    pr_base[(size_t)i * S + j] = pv;
+                    if (p.has_drop) pv = drop_keep(flat0 + (uint32_t)(i * S + j), dkn) ? pv * dkn.scale : 0.f;
+                }
+                row[j] = pv;
+            }
+        }
+    }
+    __syncthreads();
+    lds_times_rows<T, false, BF>(sm, Vb, p.ldv, S, p.dv, 1.f, Ob, p.ldo, reinterpret_cast<__bf16*>(p.Op), (uint32_t)n * (uint32_t)S,
+                             (uint32_t)((h * p.dv) >> 5), (uint32_t)p.kbo);
+}
+
+template <int T, bool MASKED>
+__global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+    const DropKey dkn = drop_key_now(p.dkey);
+    constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
+    constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* Dm = sm;                 // dP~ then dA
+    float* Pm = sm + SP * LD;       // dropped probabilities
+    float* tacc = sm + 2 * SP * LD; // [NT/64][table_rows] bias-table gradient of this head, one copy per wave
+    const int h = ATTN_HEAD, S = p.S;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool has_bias = p.index_ld > 0 && p.dtable != nullptr;
+    if (has_bias)
+        for (int i = threadIdx.x; i < (NT / 64) * p.table_rows; i += NT) tacc[i] = 0.f;
+    // a wave owns its copy: within one row i the S - 1 columns map to distinct table rows (relative offsets of distinct
+    // positions differ), and a wave walks its rows in order, so plain read-modify-write is race-free and the sum order fixed
+    float* const tw = tacc + wave * p.table_rows;
+    const int n_begin = ATTN_CHUNK * p.n_per_wg;
+    const int n_end = min(p.N, n_begin + p.n_per_wg);
+#pragma unroll 1
+    for (int n = n_begin; n < n_end; ++n) {
+        const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
+        const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
+        const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
+        const float* dOb = p.dO + (size_t)n * S * p.ldo + (size_t)h * p.dv;
+        __syncthreads();   // previous sequence's LDS readers are done
+#pragma unroll 1
+        for (int t = wave; t < T * T; t += NT / 64) {
+            const int ti = t / T, tj = t % T;
+            if (32 * ti >= S || 32 * tj >= S) continue;
+            const floatx16 acc = tile_abt<BF>(dOb, p.ldo, 32 * ti, Vb, p.ldv, 32 * tj, S, p.dv, 1.f, p.vec_v);
+            store_tile_lds<LD>(Dm, ti, tj, acc);
+        }
+        __syncthreads();
+        const float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
+        const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+        const uint8_t* mk_nh = nullptr;
+        if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
+        bool mk_rows_alike = false;                     // as in the forward: a key-padding mask is read once per (sequence, head)
+        uint8_t mk0[NJ];
+        if constexpr (MASKED) {
+            mk_rows_alike = mk.sq == 0;
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) mk0[jj] = (mk_rows_alike && lane + 64 * jj < S) ? mk_nh[(int64_t)(lane + 64 * jj) * mk.sk] : (uint8_t)1;
+        }
+#pragma unroll 1
+        for (int i = wave; i < SP; i += NT / 64) {
+            float* drow = Dm + i * LD;
+            float* prow = Pm + i * LD;
+            if (i >= S) {
+                for (int j = lane; j < SP; j += 64) drow[j] = prow[j] = 0.f;
+                continue;
+            }
+            float pv[NJ], dp[NJ], keep[NJ];
+            bool kept[NJ];                              // masked only: the mask keeps (i, j)
+            float s = 0.f;
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) {
+                const int j = lane + 64 * jj;
+                pv[jj] = dp[jj] = keep[jj] = 0.f;
+                if constexpr (MASKED) kept[jj] = j < S ? (mk_rows_alike ? mk0[jj] : mk_nh[(int64_t)i * mk.sq + (int64_t)j * mk.sk]) != 0 : true;
+                if (j < S) {
+                    pv[jj] = pr_base[(size_t)i * S + j];
+                    keep[jj] = p.has_drop ? (drop_keep(flat0 + (uint32_t)(i * S + j), dkn) ? dkn.scale : 0.f) : 1.f;
+                    dp[jj] = drow[j] * keep[jj];
+                    s += dp[jj] * pv[jj];
+                }
+            }
+            s = wave_sum(s);
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) {
+                const int j = lane + 64 * jj;
+                if (j < SP) {
+                    const float da = pv[jj] * (dp[jj] - s);      // zero for j >= S
+                    // dQ = dA K and dK = dA^T Q read Dm: no gradient reaches q.k at a masked position; the bias table below still gets dA
+                    if constexpr (MASKED) drow[j] = kept[jj] ? da : 0.f;
+                    else drow[j] = da;
+                    prow[j] = pv[jj] * keep[jj];
+                    if (has_bias && i >= 1 && j >= 1 && j < S)
+                        tw[p.index[(size_t)(i - 1) * p.index_ld + (j - 1)]] += da;
+                }
+            }
+        }
+        __syncthreads();
+        lds_times_rows<T, true, BF>(Pm, dOb, p.ldo, S, p.dv, 1.f, p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv, p.ldv);
+        lds_times_rows<T, false, BF>(Dm, Kb, p.ldk, S, p.dk, p.scale, p.dQ + (size_t)n * S * p.ldq + (size_t)h * p.dk, p.ldq);
+        lds_times_rows<T, true, BF>(Dm, Qb, p.ldq, S, p.dk, p.scale, p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk, p.ldk);
+    }
+    if (has_bias) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < p.table_rows; i += NT) {
+            float v = tacc[i];
+#pragma unroll
+            for (int w = 1; w < NT / 64; ++w) v += tacc[w * p.table_rows + i];
+            if (p.table_partials) p.dtable[((size_t)ATTN_CHUNK * p.table_rows + i) * p.H + h] = v;
+            else atomicAdd(&p.dtable[(size_t)i * p.H + h], v);
+        }
+    }
+}
 
 // =====================================================================================================
 // Second-generation backward (T <= 3, NW = 4 waves for T <= 2 and 8 for T = 3; d_k and d_v multiples of 32, 16-B aligned operands): same math, same LDS score tiles,
@@ -722,20 +889,15 @@ int fill_mask(const LstcAttnDesc* d, const LstcAttnMask* m, MaskParams& mk) {
     return 0;
 }
 
-template <typename Kern>
-void set_lds(Kern k, size_t lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-}  // namespace
-
-extern "C" {
-
-int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
+// Forward and backward behind lstc_attn_fwd / lstc_attn_bwd and their *_masked forms; mk: the checked mask (fill_mask), null for none.
+// A masked call runs the first-generation kernels for every S <= 128 (any d_k, d_v, alignment; exact-f32 products in both dtypes)
+// and the key-tiled kernels above; `variant` is not consulted, and fill_mask has refused every packed form of the descriptor.
+int attn_fwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
     AttnParams p;
     int rc = fill_params(d, p, false);
     if (rc) return rc;
-    if (p.S > 128) return attn_long_fwd_launch(d, p, (hipStream_t)stream);      // key-tiled long-sequence kernels
+    if (mk && !d->O) return LSTC_E_NULL;
+    if (p.S > 128) return attn_long_fwd_launch(d, p, mk, st);      // key-tiled long-sequence kernels
     if (d->O_pack) {        // packed bf16 output: token rows and head columns fill the pack's even tile grid exactly
         const int64_t M = (int64_t)p.N * p.S;
         if (M % 256 || (p.H * p.dv) % 64 || p.dv % 32 || M * (int64_t)(p.H * p.dv) * 2 > 0x7fffffffLL) return LSTC_E_UNSUPPORTED;
@@ -743,7 +905,6 @@ int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
         p.Op = d->O_pack;
         p.kbo = (p.H * p.dv) / 32;
     }
-    hipStream_t st = (hipStream_t)stream;
     const bool bf = d->dtype == LSTC_BF16;
     const int T = (p.S + 31) / 32;
     if (d->in_pack_cols > 0) {      // third generation: packed bf16 inputs and output
@@ -760,7 +921,7 @@ int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
         dim3 grid3((p.N + npw - 1) / npw, p.H);
         return attn3_fwd_launch(p, T, (int)grid3.x, st);
     }
-    if (!bf && (d->variant == 3 || (d->variant == 0 && T != 2)) && d->O && T <= 3 && p.vec_qk && p.vec_v && p.dk % 32 == 0 && p.dv % 64 == 0) {
+    if (!mk && !bf && (d->variant == 3 || (d->variant == 0 && T != 2)) && d->O && T <= 3 && p.vec_qk && p.vec_v && p.dk % 32 == 0 && p.dv % 64 == 0) {
         // third-generation structure on the exact-f32 MFMA (csrc/attention_pk.hip, attn_fwd3f_kernel).  Same box, N = 2048, H = 8,
         // d_k = 256 (tools/attn3f_check.py): S = 81 2.85 -> 1.89 ms, S = 96 3.1 -> 2.1, S = 17 0.30 -> 0.27; S = 49 1.13 vs 1.17 and
         // S = 33 0.97 vs 1.1 (the padded 64-key tiles cost MFMA time the first generation skips): 32 < S <= 64 stays where it was
@@ -771,7 +932,7 @@ int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
     }
     const size_t lds = (size_t)(32 * T) * (32 * T + 1) * sizeof(float);
     dim3 grid = ATTN_GRID(p.N, p.H);
-    if ((T == 1 || T == 3 || (bf && T == 2)) && p.vec_qk && p.vec_v && (p.dk % 32) == 0 && (p.dv % 32) == 0 && (d->variant == 0 || d->variant == 2)) {
+    if (!mk && (T == 1 || T == 3 || (bf && T == 2)) && p.vec_qk && p.vec_v && (p.dk % 32) == 0 && (p.dv % 32) == 0 && (d->variant == 0 || d->variant == 2)) {
         // second-generation kernel (LDS-DMA staged Q K^T, register-resident V rows).  Interleaved A/B on one MI355X
         // (tools/attn_time.py): S = 17 0.283 vs 0.350 ms; S = 49 with exact-f32 products 1.10 vs 1.02 ms (the first generation's 4
         // waves per SIMD hide more latency than this kernel's 2) - stays on the first generation; with bf16 products (LSTC_BF16)
@@ -779,42 +940,33 @@ int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) {
         // instantiation runs 8 waves.
         const int SP = 32 * T;
         const size_t lds2 = ((size_t)((SP * (SP + 1) + 3) & ~3) + (size_t)4 * SP * 32) * sizeof(float);
-#define LSTC_FWD2(TT, BB, WW)                                                              \
-    do {                                                                                   \
-        static LstcDevOnce once2;                                                          \
-        const int dev2_ = once2.begin();                                                   \
-        if (dev2_ >= 0) { set_lds(attn_fwd2_kernel<TT, BB, WW>, 160 * 1024); once2.end(dev2_); } \
-        hipLaunchKernelGGL((attn_fwd2_kernel<TT, BB, WW>), grid, 64 * WW, lds2, st, p);    \
-    } while (0)
-        if (!bf) { if (T == 1) LSTC_FWD2(1, false, 4); else LSTC_FWD2(3, false, 8); }
-        else if (T == 1) LSTC_FWD2(1, true, 4); else if (T == 2) LSTC_FWD2(2, true, 4); else LSTC_FWD2(3, true, 8);
-#undef LSTC_FWD2
+        if (!bf) {
+            if (T == 1) launch_big_lds<attn_fwd2_kernel<1, false, 4>>(grid, 64 * 4, lds2, st, p);
+            else launch_big_lds<attn_fwd2_kernel<3, false, 8>>(grid, 64 * 8, lds2, st, p);
+        } else if (T == 1) launch_big_lds<attn_fwd2_kernel<1, true, 4>>(grid, 64 * 4, lds2, st, p);
+        else if (T == 2) launch_big_lds<attn_fwd2_kernel<2, true, 4>>(grid, 64 * 4, lds2, st, p);
+        else launch_big_lds<attn_fwd2_kernel<3, true, 8>>(grid, 64 * 8, lds2, st, p);
         return lstc_launch_status();
     }
-#define LSTC_FWD(TT)                                                      \
-    do {                                                                  \
-        static LstcDevOnce once;                                          \
-        const int dev_ = once.begin();                                    \
-        if (dev_ >= 0) { set_lds(attn_fwd_kernel<TT>, 160 * 1024); once.end(dev_); } \
-        hipLaunchKernelGGL(attn_fwd_kernel<TT>, grid, NT, lds, st, p);    \
-    } while (0)
-    switch (T) {
-        case 1: LSTC_FWD(1); break;
-        case 2: LSTC_FWD(2); break;
-        case 3: LSTC_FWD(3); break;
-        default: LSTC_FWD(4); break;
-    }
-#undef LSTC_FWD
+    auto gen1 = [&](auto masked, const auto& mask_arg) {
+        constexpr bool M = decltype(masked)::value;
+        switch (T) {
+            case 1: launch_big_lds<attn_fwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 2: launch_big_lds<attn_fwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 3: launch_big_lds<attn_fwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg); break;
+            default: launch_big_lds<attn_fwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg); break;
+        }
+    };
+    if (mk) gen1(std::true_type{}, *mk); else gen1(std::false_type{}, NoMask{});
     return lstc_launch_status();
 }
 
 // d->dtable rows: the caller passes the table row count through `index_ld`'s companion below.
-int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) {
+int attn_bwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
     AttnParams p;
     int rc = fill_params(d, p, true);
     if (rc) return rc;
-    if (p.S > 128) return attn_long_bwd_launch(d, p, (hipStream_t)stream);      // key-tiled long-sequence kernels
-    hipStream_t st = (hipStream_t)stream;
+    if (p.S > 128) return attn_long_bwd_launch(d, p, mk, st);      // key-tiled long-sequence kernels
     const bool bf = d->dtype == LSTC_BF16;
     const int T = (p.S + 31) / 32;
     p.table_rows = (d->index_ld > 0 && d->dtable) ? d->table_rows : 0;
@@ -847,7 +999,7 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) {
     // S = 49: 1.63 vs 2.75 ms, S = 17: 0.53 vs 1.19 ms per LTN / STN layer (interleaved A/B); S = 81 (T = 3): 138 KB of LDS =
     // one workgroup per CU; with 4 waves that was no faster than the first generation (193 spilled registers, 7.3 vs 7.1 ms),
     // the 8-wave instantiation (two waves per SIMD, 12 rows / 3 DMA pieces / <= 2 jobs per wave) runs 4.3 ms
-    const bool v2 = T <= 3 && p.vec_qk && p.vec_v && (p.dk % 32) == 0 && (p.dv % 32) == 0 && d->variant != 1;
+    const bool v2 = !mk && T <= 3 && p.vec_qk && p.vec_v && (p.dk % 32) == 0 && (p.dv % 32) == 0 && d->variant != 1;
     if (d->dQ_pack || d->dK_pack || d->dV_pack) {
         // packed bf16 gradients: the staged kernel only, token rows and head columns filling the packs' even tile grid exactly
         const int64_t M = (int64_t)p.N * p.S;
@@ -873,111 +1025,51 @@ int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) {
         const int SP = 32 * T, NW = T == 3 ? 8 : 4;      // 64 < S <= 96: 138 KB of LDS = one workgroup per CU, so that one runs 8 waves
         const size_t lds2 = ((size_t)((2 * SP * (SP + 1) + 3) & ~3) + (size_t)4 * SP * 32 + (size_t)NW * p.table_rows) * sizeof(float);
         if (lds2 <= 160 * 1024) {
-#define LSTC_BWD2(TT, BB, WW)                                                              \
-    do {                                                                                   \
-        static LstcDevOnce once2;                                                          \
-        const int dev2_ = once2.begin();                                                   \
-        if (dev2_ >= 0) { set_lds(attn_bwd2_kernel<TT, BB, WW>, 160 * 1024); once2.end(dev2_); } \
-        hipLaunchKernelGGL((attn_bwd2_kernel<TT, BB, WW>), grid, 64 * WW, lds2, st, p);    \
-    } while (0)
-            if (T == 1) { if (bf) LSTC_BWD2(1, true, 4); else LSTC_BWD2(1, false, 4); }
-            else if (T == 2) { if (bf) LSTC_BWD2(2, true, 4); else LSTC_BWD2(2, false, 4); }
-            else { if (bf) LSTC_BWD2(3, true, 8); else LSTC_BWD2(3, false, 8); }
-#undef LSTC_BWD2
+            if (T == 1) {
+                if (bf) launch_big_lds<attn_bwd2_kernel<1, true, 4>>(grid, 64 * 4, lds2, st, p);
+                else launch_big_lds<attn_bwd2_kernel<1, false, 4>>(grid, 64 * 4, lds2, st, p);
+            } else if (T == 2) {
+                if (bf) launch_big_lds<attn_bwd2_kernel<2, true, 4>>(grid, 64 * 4, lds2, st, p);
+                else launch_big_lds<attn_bwd2_kernel<2, false, 4>>(grid, 64 * 4, lds2, st, p);
+            } else {
+                if (bf) launch_big_lds<attn_bwd2_kernel<3, true, 8>>(grid, 64 * 8, lds2, st, p);
+                else launch_big_lds<attn_bwd2_kernel<3, false, 8>>(grid, 64 * 8, lds2, st, p);
+            }
             return lstc_launch_status();
         }
     }
     if (p.dQp) return LSTC_E_UNSUPPORTED;
-#define LSTC_BWD(TT)                                                         \
-    do {                                                                     \
-        static LstcDevOnce once;                                             \
-        const int dev_ = once.begin();                                       \
-        if (dev_ >= 0) { set_lds(attn_bwd_kernel<TT>, 160 * 1024); once.end(dev_); } \
-        hipLaunchKernelGGL(attn_bwd_kernel<TT>, grid, NT, lds, st, p);       \
-    } while (0)
-    switch (T) {
-        case 1: LSTC_BWD(1); break;
-        case 2: LSTC_BWD(2); break;
-        case 3: LSTC_BWD(3); break;
-        default: LSTC_BWD(4); break;
-    }
-#undef LSTC_BWD
+    auto gen1 = [&](auto masked, const auto& mask_arg) {
+        constexpr bool M = decltype(masked)::value;
+        switch (T) {
+            case 1: launch_big_lds<attn_bwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 2: launch_big_lds<attn_bwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 3: launch_big_lds<attn_bwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg); break;
+            default: launch_big_lds<attn_bwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg); break;
+        }
+    };
+    if (mk) gen1(std::true_type{}, *mk); else gen1(std::false_type{}, NoMask{});
     return lstc_launch_status();
 }
 
-// Masked forms (include/lstc_hip.h, "attention masks"): the first-generation kernels for S <= 128 (any d_k, d_v, alignment; exact-f32
-// products in both dtypes), the key-tiled kernels above.  `variant` is not consulted.
+}  // namespace
+
+extern "C" {
+
+int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) { return attn_fwd(d, nullptr, (hipStream_t)stream); }
+int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) { return attn_bwd(d, nullptr, (hipStream_t)stream); }
+
+// Masked forms (include/lstc_hip.h, "attention masks"): the mask is checked first, then everything as in the unmasked call
 int lstc_attn_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
-    int rc = fill_mask(d, m, mk);
-    if (rc) return rc;
-    AttnParams p;
-    rc = fill_params(d, p, false);
-    if (rc) return rc;
-    if (!d->O) return LSTC_E_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (p.S > 128) return attn_long_fwd_masked_launch(d, p, mk, st);
-    const int T = (p.S + 31) / 32;
-    const size_t lds = (size_t)(32 * T) * (32 * T + 1) * sizeof(float);
-    dim3 grid = ATTN_GRID(p.N, p.H);
-#define LSTC_FWDM(TT)                                                             \
-    do {                                                                          \
-        static LstcDevOnce once;                                                  \
-        const int dev_ = once.begin();                                            \
-        if (dev_ >= 0) { set_lds(attn_fwd_masked_kernel<TT>, 160 * 1024); once.end(dev_); } \
-        hipLaunchKernelGGL(attn_fwd_masked_kernel<TT>, grid, NT, lds, st, p, mk);  \
-    } while (0)
-    switch (T) {
-        case 1: LSTC_FWDM(1); break;
-        case 2: LSTC_FWDM(2); break;
-        case 3: LSTC_FWDM(3); break;
-        default: LSTC_FWDM(4); break;
-    }
-#undef LSTC_FWDM
-    return lstc_launch_status();
+    const int rc = fill_mask(d, m, mk);
+    return rc ? rc : attn_fwd(d, &mk, (hipStream_t)stream);
 }
 
 int lstc_attn_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
-    int rc = fill_mask(d, m, mk);
-    if (rc) return rc;
-    AttnParams p;
-    rc = fill_params(d, p, true);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (p.S > 128) return attn_long_bwd_masked_launch(d, p, mk, st);
-    const int T = (p.S + 31) / 32;
-    p.table_rows = (d->index_ld > 0 && d->dtable) ? d->table_rows : 0;
-    if (d->index_ld > 0 && d->dtable && d->table_rows <= 0) return LSTC_E_SHAPE;
-    const size_t lds = ((size_t)2 * (32 * T) * (32 * T + 1) + (size_t)(NT / 64) * p.table_rows) * sizeof(float);
-    if (lds > 160 * 1024) return LSTC_E_RANGE;
-    int npw = (int)(((int64_t)p.N * p.H + 4095) / 4096);      // as lstc_attn_bwd
-    if (npw < 1) npw = 1;
-    if (npw > 8) npw = 8;
-    p.table_partials = 0;
-    if (p.table_rows > 0 && d->dtable_chunks > 0) {
-        npw = (p.N + d->dtable_chunks - 1) / d->dtable_chunks;
-        p.table_partials = 1;
-    }
-    p.n_per_wg = npw;
-    const int chunks_ = (p.N + npw - 1) / npw;
-    dim3 grid = ATTN_GRID(chunks_, p.H);
-    if (p.table_partials && chunks_ != d->dtable_chunks) return LSTC_E_SHAPE;
-#define LSTC_BWDM(TT)                                                             \
-    do {                                                                          \
-        static LstcDevOnce once;                                                  \
-        const int dev_ = once.begin();                                            \
-        if (dev_ >= 0) { set_lds(attn_bwd_masked_kernel<TT>, 160 * 1024); once.end(dev_); } \
-        hipLaunchKernelGGL(attn_bwd_masked_kernel<TT>, grid, NT, lds, st, p, mk);  \
-    } while (0)
-    switch (T) {
-        case 1: LSTC_BWDM(1); break;
-        case 2: LSTC_BWDM(2); break;
-        case 3: LSTC_BWDM(3); break;
-        default: LSTC_BWDM(4); break;
-    }
-#undef LSTC_BWDM
-    return lstc_launch_status();
+    const int rc = fill_mask(d, m, mk);
+    return rc ? rc : attn_bwd(d, &mk, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1009,27 +1101,131 @@ struct ClsParams {
 // key-tiled long-sequence path's range): the scores of a wave's (sequence, head) in LDS and MAXS / 64 of them per lane.
 constexpr int CLS_MAXS = 512;
 
-// attn_cls_fwd_kernel<MAXS> / attn_cls_bwd_kernel<MAXS>: the kernel text is in attention_cls.inc, included once under the kernels' own names
-// (unmasked: exactly the text they always had) and once as the *_masked_kernel instantiations, which take the attention mask
-// (attention_common.h MaskParams) as a second argument.
-#define ATTN_MASKED 0
-#define ATTN_MASK_PARAM
-#define ATTN_CLS_FWD attn_cls_fwd_kernel
-#define ATTN_CLS_BWD attn_cls_bwd_kernel
-#include "attention_cls.inc"
-#undef ATTN_MASKED
-#undef ATTN_MASK_PARAM
-#undef ATTN_CLS_FWD
-#undef ATTN_CLS_BWD
-#define ATTN_MASKED 1
-#define ATTN_MASK_PARAM , const MaskParams mk
-#define ATTN_CLS_FWD attn_cls_fwd_masked_kernel
-#define ATTN_CLS_BWD attn_cls_bwd_masked_kernel
-#include "attention_cls.inc"
-#undef ATTN_MASKED
-#undef ATTN_MASK_PARAM
-#undef ATTN_CLS_FWD
-#undef ATTN_CLS_BWD
+// MASKED: row 0 of the mask (LstcAttnMask.sq is not read).
+template <int MAXS, bool MASKED>
+__global__ void __launch_bounds__(NT) attn_cls_fwd_kernel(const ClsParams p, const MaskArg<MASKED> mk) {
+    constexpr int NJ = MAXS / 64;
+    const DropKey dkn = drop_key_now(p.dkey);
+    __shared__ float sc[NT / 64][MAXS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pair = blockIdx.x * (NT / 64) + wave;
+    if (pair >= p.N * p.H) return;
+    const int n = pair / p.H, h = pair % p.H, S = p.S;
+    const float* q = p.Q + (size_t)n * p.ldq + (size_t)h * p.dk;
+    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
+    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
+    float* s = sc[wave];
+    for (int j = 0; j < S; ++j) {
+        float a = 0.f;
+        for (int c = lane; c < p.dk; c += 64) a += (q[c] * p.scale) * Kb[(size_t)j * p.ldk + c];
+        a = wave_sum(a);
+        if (lane == 0) s[j] = a;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float v[NJ], m = -INFINITY;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int j = lane + 64 * jj;
+        v[jj] = j < S ? s[j] : -INFINITY;
+        if constexpr (MASKED)       // row 0 of the mask; row 0 carries no bias
+            if (j < S) v[jj] = mk.m[(int64_t)n * mk.sn + (int64_t)h * mk.sh + (int64_t)j * mk.sk] ? v[jj] : ATTN_MASK_FILL;
+        m = fmaxf(m, v[jj]);
+    }
+    m = wave_max(m);
+    float sum = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
+        sum += v[jj];
+    }
+    sum = wave_sum(sum);
+    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);       // row 0 of the full tensor
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int j = lane + 64 * jj;
+        if (j < S) {
+            float pv = v[jj] / sum;
+            p.probs[((size_t)n * p.H + h) * S + j] = pv;
+            if (p.has_drop) pv = drop_keep(flat0 + (uint32_t)j, dkn) ? pv * dkn.scale : 0.f;
+            s[j] = pv;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    float* o = p.O + (size_t)n * p.ldo + (size_t)h * p.dv;
+    for (int c = lane; c < p.dv; c += 64) {
+        float a = 0.f;
+        for (int j = 0; j < S; ++j) a += s[j] * Vb[(size_t)j * p.ldv + c];
+        o[c] = a;
+    }
+}
+
+template <int MAXS, bool MASKED>
+__global__ void __launch_bounds__(NT) attn_cls_bwd_kernel(const ClsParams p, const MaskArg<MASKED> mk) {
+    constexpr int NJ = MAXS / 64;
+    const DropKey dkn = drop_key_now(p.dkey);
+    __shared__ float sp[NT / 64][MAXS];      // dropped probabilities
+    __shared__ float sd[NT / 64][MAXS];      // d(logit)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pair = blockIdx.x * (NT / 64) + wave;
+    if (pair >= p.N * p.H) return;
+    const int n = pair / p.H, h = pair % p.H, S = p.S;
+    const float* q = p.Q + (size_t)n * p.ldq + (size_t)h * p.dk;
+    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
+    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
+    const float* dO = p.dO + (size_t)n * p.ldo + (size_t)h * p.dv;
+    float* dKb = p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk;
+    float* dVb = p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv;
+    float* pd = sp[wave];
+    float* ds = sd[wave];
+    // dP~_j = dO . V_j
+    for (int j = 0; j < S; ++j) {
+        float a = 0.f;
+        for (int c = lane; c < p.dv; c += 64) a += dO[c] * Vb[(size_t)j * p.ldv + c];
+        a = wave_sum(a);
+        if (lane == 0) ds[j] = a;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    float pv[NJ], dp[NJ], keep[NJ], rs = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int j = lane + 64 * jj;
+        pv[jj] = dp[jj] = keep[jj] = 0.f;
+        if (j < S) {
+            pv[jj] = p.probs[((size_t)n * p.H + h) * S + j];
+            keep[jj] = p.has_drop ? (drop_keep(flat0 + (uint32_t)j, dkn) ? dkn.scale : 0.f) : 1.f;
+            dp[jj] = ds[j] * keep[jj];
+            rs += dp[jj] * pv[jj];
+        }
+    }
+    rs = wave_sum(rs);
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int j = lane + 64 * jj;
+        if (j < S) {
+            // masked: d(logit) of a masked key is zero (no bias in row 0, so nothing else consumes it)
+            if constexpr (MASKED) ds[j] = mk.m[(int64_t)n * mk.sn + (int64_t)h * mk.sh + (int64_t)j * mk.sk] ? pv[jj] * (dp[jj] - rs) : 0.f;
+            else ds[j] = pv[jj] * (dp[jj] - rs);
+            pd[j] = pv[jj] * keep[jj];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // dV_j = Pd_j dO ; dK_j = scale dA_j q ; dq = scale sum_j dA_j K_j
+    for (int c = lane; c < p.dv; c += 64) {
+        const float g = dO[c];
+        for (int j = 0; j < S; ++j) dVb[(size_t)j * p.ldv + c] = pd[j] * g;
+    }
+    float* dq = p.dQ + (size_t)n * p.ldq + (size_t)h * p.dk;
+    for (int c = lane; c < p.dk; c += 64) {
+        const float qs = q[c] * p.scale;
+        float a = 0.f;
+        for (int j = 0; j < S; ++j) {
+            a += ds[j] * Kb[(size_t)j * p.ldk + c];
+            dKb[(size_t)j * p.ldk + c] = ds[j] * qs;
+        }
+        dq[c] = a * p.scale;
+    }
+}
 
 int fill_cls(const LstcAttnDesc* d, ClsParams& p, bool bwd) {
     if (!d) return LSTC_E_NULL;
@@ -1052,60 +1248,45 @@ int fill_cls(const LstcAttnDesc* d, ClsParams& p, bool bwd) {
     return 0;
 }
 
+// behind lstc_attn_cls_fwd / _bwd and their *_masked forms; mk: the checked mask, null for none.  Static LDS only.
+int attn_cls(const LstcAttnDesc* d, const MaskParams* mk, bool bwd, hipStream_t st) {
+    ClsParams p;
+    int rc = fill_cls(d, p, bwd);
+    if (rc) return rc;
+    if (mk && !bwd && !d->O) return LSTC_E_NULL;
+    const int pairs = p.N * p.H;
+    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
+    auto go = [&](auto masked, const auto& mask_arg) {
+        constexpr bool M = decltype(masked)::value;
+        if (!bwd) {
+            if (p.S <= 128) hipLaunchKernelGGL((attn_cls_fwd_kernel<128, M>), grid, NT, 0, st, p, mask_arg);
+            else hipLaunchKernelGGL((attn_cls_fwd_kernel<CLS_MAXS, M>), grid, NT, 0, st, p, mask_arg);
+        } else {
+            if (p.S <= 128) hipLaunchKernelGGL((attn_cls_bwd_kernel<128, M>), grid, NT, 0, st, p, mask_arg);
+            else hipLaunchKernelGGL((attn_cls_bwd_kernel<CLS_MAXS, M>), grid, NT, 0, st, p, mask_arg);
+        }
+    };
+    if (mk) go(std::true_type{}, *mk); else go(std::false_type{}, NoMask{});
+    return lstc_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
 
-int lstc_attn_cls_fwd(const LstcAttnDesc* d, void* stream) {
-    ClsParams p;
-    int rc = fill_cls(d, p, false);
-    if (rc) return rc;
-    const int pairs = p.N * p.H;
-    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
-    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_fwd_kernel<128>, grid, NT, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(attn_cls_fwd_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p);
-    return lstc_launch_status();
-}
+int lstc_attn_cls_fwd(const LstcAttnDesc* d, void* stream) { return attn_cls(d, nullptr, false, (hipStream_t)stream); }
+int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream) { return attn_cls(d, nullptr, true, (hipStream_t)stream); }
 
-int lstc_attn_cls_bwd(const LstcAttnDesc* d, void* stream) {
-    ClsParams p;
-    int rc = fill_cls(d, p, true);
-    if (rc) return rc;
-    const int pairs = p.N * p.H;
-    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
-    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_bwd_kernel<128>, grid, NT, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(attn_cls_bwd_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p);
-    return lstc_launch_status();
-}
-
-// Masked forms: row 0 of the mask (LstcAttnMask.sq is not read).
 int lstc_attn_cls_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
-    int rc = fill_mask(d, m, mk);
-    if (rc) return rc;
-    ClsParams p;
-    rc = fill_cls(d, p, false);
-    if (rc) return rc;
-    if (!d->O) return LSTC_E_NULL;
-    const int pairs = p.N * p.H;
-    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
-    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_fwd_masked_kernel<128>, grid, NT, 0, (hipStream_t)stream, p, mk);
-    else hipLaunchKernelGGL(attn_cls_fwd_masked_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p, mk);
-    return lstc_launch_status();
+    const int rc = fill_mask(d, m, mk);
+    return rc ? rc : attn_cls(d, &mk, false, (hipStream_t)stream);
 }
 
 int lstc_attn_cls_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
-    int rc = fill_mask(d, m, mk);
-    if (rc) return rc;
-    ClsParams p;
-    rc = fill_cls(d, p, true);
-    if (rc) return rc;
-    const int pairs = p.N * p.H;
-    const dim3 grid((pairs + NT / 64 - 1) / (NT / 64));
-    if (p.S <= 128) hipLaunchKernelGGL(attn_cls_bwd_masked_kernel<128>, grid, NT, 0, (hipStream_t)stream, p, mk);
-    else hipLaunchKernelGGL(attn_cls_bwd_masked_kernel<CLS_MAXS>, grid, NT, 0, (hipStream_t)stream, p, mk);
-    return lstc_launch_status();
+    const int rc = fill_mask(d, m, mk);
+    return rc ? rc : attn_cls(d, &mk, true, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1601,18 +1782,14 @@ int lstc_cls_dot(const float* U, const float* X, float* out, float* probs, int64
     if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
     const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
     if (lds > 96 * 1024) return LSTC_E_RANGE;
-    static LstcDevOnce once;
-    const int dev_ = once.begin();
-    if (dev_ >= 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cls_dot_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cls_dot_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cls_dot_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cls_dot_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        once.end(dev_);
-    }
     const DropKey dk = make_drop_key(dropout_p, seed);
     const int has_drop = dropout_p > 0.f;
-    LSTC_H_DISPATCH(cls_dot_kernel, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, U, X, out, probs, S, H, d, mode, dk, has_drop);
+    const dim3 grid((unsigned)N);
+    hipStream_t st = (hipStream_t)stream;
+    if (H <= 2) launch_big_lds<cls_dot_kernel<2>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
+    else if (H <= 4) launch_big_lds<cls_dot_kernel<4>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
+    else if (H <= 8) launch_big_lds<cls_dot_kernel<8>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
+    else launch_big_lds<cls_dot_kernel<16>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
     return lstc_launch_status();
 }
 

@@ -3,6 +3,7 @@
 // 128 < S <= 512).
 #pragma once
 #include "lstc_common.h"
+#include <type_traits>
 
 namespace lstc_attn {
 
@@ -38,12 +39,15 @@ struct AttnParams {
 };
 
 // Attention mask of the *_masked entry points (LstcAttnMask): one byte per (n, h, query i, key j) through four element strides
-// (0 = broadcast); byte 0 = masked.  A second kernel argument of the masked instantiations only: AttnParams and the unmasked
-// kernels are as they were.
+// (0 = broadcast); byte 0 = masked.  The second argument of every maskable kernel is a MaskArg<MASKED>: the mask for the masked
+// instantiation, an empty NoMask for the unmasked one, whose body then holds no trace of it (`if constexpr (MASKED)`).
 struct MaskParams {
     const uint8_t* m;
     int64_t sn, sh, sq, sk;
 };
+struct NoMask {};
+template <bool MASKED>
+using MaskArg = std::conditional_t<MASKED, MaskParams, NoMask>;
 // the logit of a masked position, in place of the scaled q.k and before the relative bias (the reference's masked_fill value);
 // -1e9f + bias rounds back to -1e9f for |bias| < 32, so a fully masked row comes out uniform and nothing is ever -inf or NaN
 constexpr float ATTN_MASK_FILL = -1e9f;
@@ -59,12 +63,23 @@ __attribute__((visibility("hidden"))) int attn3_fwd_launch(const AttnParams& p, 
 __attribute__((visibility("hidden"))) int attn3_bwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st);
 // exact-f32 forward on the same structure (f32 operands, dense probs): csrc/attention_pk.hip
 __attribute__((visibility("hidden"))) int attn3f_fwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st);
-// csrc/attention_long.hip: the key-tiled kernels for 128 < S <= 512 (row inputs and outputs only), called by lstc_attn_fwd /
-// lstc_attn_bwd after fill_params; check their own preconditions, then launch
-__attribute__((visibility("hidden"))) int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
-__attribute__((visibility("hidden"))) int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, hipStream_t st);
-// the same with an attention mask (lstc_attn_fwd_masked / lstc_attn_bwd_masked): the masked instantiations of the same kernels
-__attribute__((visibility("hidden"))) int attn_long_fwd_masked_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams& mk, hipStream_t st);
-__attribute__((visibility("hidden"))) int attn_long_bwd_masked_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams& mk, hipStream_t st);
+// csrc/attention_long.hip: the key-tiled kernels for 128 < S <= 512 (row inputs and outputs only), called by the forward /
+// backward entry points after fill_params; check their own preconditions, then launch.  mk: the attention mask of the *_masked
+// entry points (the masked instantiations of the same kernels), null for none
+__attribute__((visibility("hidden"))) int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams* mk, hipStream_t st);
+__attribute__((visibility("hidden"))) int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams* mk, hipStream_t st);
+
+// Host side: launch a kernel that asks for more than 64 KB of dynamic LDS.  The opt-in (MAX_LDS bytes; 160 KB = the whole LDS of a
+// CU) is a per-device attribute of the kernel: set once per device and kernel instantiation, ahead of its first launch there.
+template <auto Kern, int MAX_LDS = 160 * 1024, typename... Args>
+void launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    static LstcDevOnce once;
+    const int dev = once.begin();
+    if (dev >= 0) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+        once.end(dev);
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+}
 
 }  // namespace lstc_attn

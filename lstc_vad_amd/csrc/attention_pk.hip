@@ -786,9 +786,21 @@ __global__ void __launch_bounds__(64 * (T + 1), T == 1 ? 4 : (T == 2 ? 3 : 2)) a
     }
 }
 
-template <typename Kern>
-void set_lds(Kern k, size_t lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// one launch per kernel family: workgroups of T + 1 waves (T consumers and the producer), ring of NB slots in dynamic LDS
+template <int T, int NB>
+void fwd3_go(const AttnParams& p, int chunks, hipStream_t st) {
+    launch_big_lds<attn_fwd3_kernel<T, NB>>(dim3((unsigned)chunks * (unsigned)p.H), 64 * (T + 1), (size_t)NB * 2 * (32 * T) * 64, st, p);
+}
+template <int T, int NB>
+void fwd3f_go(const AttnParams& p, int chunks, hipStream_t st) {
+    launch_big_lds<attn_fwd3f_kernel<T, NB>>(dim3((unsigned)chunks * (unsigned)p.H), 64 * (T + 1), (size_t)NB * 2 * (32 * T) * 128, st, p);
+}
+template <int T, int NB>
+int bwd3_go(const AttnParams& p, int chunks, hipStream_t st) {
+    const size_t lds3 = (size_t)NB * 2 * (32 * T) * 64 + (size_t)(32 * T) * 72 + (size_t)T * p.table_rows * sizeof(float);
+    if (lds3 > 160 * 1024) return LSTC_E_RANGE;
+    launch_big_lds<attn_bwd3_kernel<T, NB>>(dim3((unsigned)chunks * (unsigned)p.H), 64 * (T + 1), lds3, st, p);
+    return lstc_launch_status();
 }
 
 }  // namespace
@@ -797,46 +809,17 @@ namespace lstc_attn {
 
 // ring depth per instantiation: (NB - 1) x slot x resident workgroups ~ 100-130 KB of DMA in flight per CU (block comment above)
 int attn3_fwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st) {
-#define LSTC_FWD3(TT, NBB)                                                                 \
-    do {                                                                                   \
-        static LstcDevOnce once3;                                                          \
-        const int dev3_ = once3.begin();                                                   \
-        if (dev3_ >= 0) { set_lds(attn_fwd3_kernel<TT, NBB>, 160 * 1024); once3.end(dev3_); } \
-        hipLaunchKernelGGL((attn_fwd3_kernel<TT, NBB>), dim3((unsigned)chunks * (unsigned)p.H), 64 * (TT + 1), \
-                           (size_t)NBB * 2 * (32 * TT) * 64, st, p);                       \
-    } while (0)
-    if (T == 1) LSTC_FWD3(1, 6); else if (T == 2) LSTC_FWD3(2, 9); else if (T == 3) LSTC_FWD3(3, 6); else return LSTC_E_RANGE;
-#undef LSTC_FWD3
+    if (T == 1) fwd3_go<1, 6>(p, chunks, st); else if (T == 2) fwd3_go<2, 9>(p, chunks, st); else if (T == 3) fwd3_go<3, 6>(p, chunks, st); else return LSTC_E_RANGE;
     return lstc_launch_status();
 }
 
 int attn3f_fwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st) {
-#define LSTC_FWD3F(TT, NBB)                                                                \
-    do {                                                                                   \
-        static LstcDevOnce once3;                                                          \
-        const int dev3_ = once3.begin();                                                   \
-        if (dev3_ >= 0) { set_lds(attn_fwd3f_kernel<TT, NBB>, 160 * 1024); once3.end(dev3_); } \
-        hipLaunchKernelGGL((attn_fwd3f_kernel<TT, NBB>), dim3((unsigned)chunks * (unsigned)p.H), 64 * (TT + 1), \
-                           (size_t)NBB * 2 * (32 * TT) * 128, st, p);                      \
-    } while (0)
-    if (T == 1) LSTC_FWD3F(1, 3); else if (T == 2) LSTC_FWD3F(2, 3); else if (T == 3) LSTC_FWD3F(3, 3); else return LSTC_E_RANGE;
-#undef LSTC_FWD3F
+    if (T == 1) fwd3f_go<1, 3>(p, chunks, st); else if (T == 2) fwd3f_go<2, 3>(p, chunks, st); else if (T == 3) fwd3f_go<3, 3>(p, chunks, st); else return LSTC_E_RANGE;
     return lstc_launch_status();
 }
 
 int attn3_bwd_launch(const AttnParams& p, int T, int chunks, hipStream_t st) {
-#define LSTC_BWD3(TT, NBB)                                                                 \
-    do {                                                                                   \
-        const size_t lds3 = (size_t)NBB * 2 * (32 * TT) * 64 + (size_t)(32 * TT) * 72 + (size_t)TT * p.table_rows * sizeof(float); \
-        if (lds3 > 160 * 1024) return LSTC_E_RANGE;                                        \
-        static LstcDevOnce once3;                                                          \
-        const int dev3_ = once3.begin();                                                   \
-        if (dev3_ >= 0) { set_lds(attn_bwd3_kernel<TT, NBB>, 160 * 1024); once3.end(dev3_); } \
-        hipLaunchKernelGGL((attn_bwd3_kernel<TT, NBB>), dim3((unsigned)chunks * (unsigned)p.H), 64 * (TT + 1), lds3, st, p); \
-    } while (0)
-    if (T == 1) LSTC_BWD3(1, 9); else if (T == 2) LSTC_BWD3(2, 8); else if (T == 3) LSTC_BWD3(3, 5); else return LSTC_E_RANGE;
-#undef LSTC_BWD3
-    return lstc_launch_status();
+    return T == 1 ? bwd3_go<1, 9>(p, chunks, st) : T == 2 ? bwd3_go<2, 8>(p, chunks, st) : T == 3 ? bwd3_go<3, 5>(p, chunks, st) : LSTC_E_RANGE;
 }
 
 }  // namespace lstc_attn

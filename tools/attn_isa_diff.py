@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Compare the gfx950 machine code of the attention kernels of two builds, symbol by symbol.
 
-    python tools/attn_isa_diff.py OLD_TREE NEW_TREE [> profiles/attn_mask_isa_diff.txt]
+    python tools/attn_isa_diff.py OLD_TREE NEW_TREE [> profiles/attn_template_isa_diff.txt]
 
 Each tree must have been built with `make` (the per-file objects lstc_vad_amd/csrc/attention*.o are read: one offload bundle
-each).  Every kernel symbol of OLD is looked up in NEW and its disassembly compared as text after the addresses are stripped
-(instruction words and operands stay).  Kernels only NEW has are listed, not compared.  Exit status 1 if an OLD kernel is missing
-or differs."""
+each).  Every kernel of OLD is looked up in NEW by its demangled name (key(): the two spellings of a masked instantiation count
+as one) and its disassembly compared as text after the addresses are stripped (instruction words and operands stay).  Exit
+status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
 import os
 import re
 import subprocess
@@ -18,7 +18,7 @@ FILES = ("attention", "attention_long", "attention_pk")
 
 
 def kernels(tree, name, tmp):
-    d = os.path.join(tmp, f"{abs(hash(tree))}_{name}")
+    d = os.path.join(tmp, f"{len(os.listdir(tmp))}_{name}")
     os.makedirs(d)
     obj = os.path.join(d, name + ".o")
     with open(os.path.join(tree, "lstc_vad_amd", "csrc", name + ".o"), "rb") as f, open(obj, "wb") as g:
@@ -42,11 +42,46 @@ def kernels(tree, name, tmp):
     return out
 
 
-def demangle(s):
+def demangle(syms):
     try:
-        return subprocess.run(["c++filt", s], capture_output=True, text=True).stdout.strip() or s
+        out = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")
     except OSError:
-        return s
+        out = []
+    return dict(zip(syms, out)) if len(out) >= len(syms) else {s: s for s in syms}
+
+
+def key(dem):
+    """One name per kernel whichever way its tree spells the masked instantiation: the demangled name without the parameter list,
+    with `X_masked_kernel<A>` (a twin of its own) and `X_kernel<A, true>` (a last template argument MASKED, which the NoMask in
+    the parameter list gives away) both as `X_kernel<A> [masked]`.  Every other kernel keeps its name.
+    This leans on how the mangling spells MaskArg<MASKED> (csrc/attention_common.h): as
+    `std::conditional<B, MaskParams, NoMask>::type`, so both instantiations name NoMask.  Another definition of MaskArg or
+    another demangler would leave the template form unrecognised: its kernels then come out MISSING / NEW, never as a false pass."""
+    depth, cut = 0, len(dem)
+    for i in range(len(dem) - 1, -1, -1):      # the parameter list is the last parenthesised group
+        depth += (dem[i] == ")") - (dem[i] == "(")
+        if depth == 0:
+            cut = i
+            break
+    name, params = dem[:cut], dem[cut:]
+    masked = False
+    if "NoMask" in params and name.endswith(">"):
+        m = re.match(r"^(.*), (true|false)>$", name)
+        if m:
+            name, masked = m.group(1) + ">", m.group(2) == "true"
+    elif "_masked_kernel<" in name:
+        name, masked = name.replace("_masked_kernel<", "_kernel<"), True
+    return name + (" [masked]" if masked else "")
+
+
+def keyed(kern):
+    dem = demangle(sorted(kern))
+    out = {}
+    for sym, body in kern.items():
+        k = key(dem[sym])
+        assert k not in out, f"two kernels named {k}"
+        out[k] = body
+    return out
 
 
 def main():
@@ -54,18 +89,18 @@ def main():
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for name in FILES:
-            a, b = kernels(old, name, tmp), kernels(new, name, tmp)
+            a, b = keyed(kernels(old, name, tmp)), keyed(kernels(new, name, tmp))
             print(f"== csrc/{name}.hip: {len(a)} kernels before, {len(b)} after")
             for k in sorted(a):
                 if k not in b:
-                    print(f"MISSING   {demangle(k)}"); bad += 1
+                    print(f"MISSING   {k}"); bad += 1
                 elif a[k] != b[k]:
-                    print(f"DIFFERS   {demangle(k)}  ({len(a[k])} -> {len(b[k])} instructions)"); bad += 1
+                    print(f"DIFFERS   {k}  ({len(a[k])} -> {len(b[k])} instructions)"); bad += 1
                 else:
-                    print(f"identical {demangle(k)}  ({len(a[k])} instructions)")
+                    print(f"identical {k}  ({len(a[k])} instructions)")
             for k in sorted(set(b) - set(a)):
-                print(f"new       {demangle(k)}  ({len(b[k])} instructions)")
-    print(f"== {bad} pre-existing attention kernel(s) missing or changed")
+                print(f"NEW       {k}  ({len(b[k])} instructions)"); bad += 1
+    print(f"== {bad} attention kernel(s) missing, changed or without a counterpart in the old tree")
     return 1 if bad else 0
 
 
