@@ -290,6 +290,47 @@ int lstc_attn_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* str
 int lstc_attn_cls_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);   /* query row 0: sq is ignored */
 int lstc_attn_cls_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);
 
+/* Rectangular attention (reference models/MultiHeadAttention.py:17-23, class ScaledDotProductAttention): the queries and the
+ * keys have lengths of their own and there is no relative bias (csrc/attention_x.hip).
+ *   A = (Q scale) K^T [N, H, Sq, Sk] ; A = mask byte == 0 ? -1e9f : A (m non-NULL) ; P = softmax(A, -1) ; Pd = dropout(P) ;
+ *   O = Pd V.  `probs` receives P before dropout; the dropout decision of element (n, h, i, j) is the counter hash at the flat
+ *   index ((n*H + h)*Sq + i)*Sk + j, so lstc_dropout_mask() over N*H*Sq*Sk elements with the same seed regenerates it.
+ *   backward: dV = Pd^T dO ; dP' = dO V^T with the dropout replayed ; dA = P*(dP' - rowsum(dP'*P)) ; dQ = dA K scale ;
+ *   dK = dA^T Q scale, all written (not accumulated).
+ * Operands: Q [N, H, Sq, dk], K [N, H, Sk, dk], V [N, H, Sk, dv], O [N, H, Sq, dv], f32, each addressed as
+ * base[n*sn + h*sh + t*st + feature] - the feature stride is 1.  Head-major [b, H, l, d] tensors ((H*l*d, l*d, d)) and the
+ * transpose(1, 2) view of a token-major [b, l, H*d] projection ((l*H*d, d, H*d)) run without a copy.  dO uses O's strides;
+ * dQ, dK, dV use those of Q, K, V.  Float4 loads are taken when the bases are 16-B aligned and the strides multiples of 4;
+ * results do not depend on it.
+ * Mask: LstcAttnMask as above, sq stepping over the query i < Sq and sk over the key j < Sk; m == NULL = no mask.  Masked keys
+ *   of a row that keeps a key get probability exactly 0.0; a fully masked row is uniform, 1/Sk in every column - no -inf, no
+ *   NaN; the dA that feeds dQ and dK is zero at masked positions; dV and the row sums are as unmasked (P carries the mask).
+ * Limits: 1 <= Sq <= 512 and 1 <= Sk <= 512 independently; dk and dv multiples of 16 up to 512, dk != dv allowed - any other
+ *   width returns LSTC_E_RANGE; N*H*Sq*Sk <= 2^32 - 1 (the dropout counter is 32 bits) and N*H <= 2^31 - 1, else LSTC_E_RANGE.
+ * Every product runs on the exact-f32 MFMA in every compute mode; softmax and dropout are f32.
+ * Checked before any launch: d, Q, K, V, probs, O (forward), dO / dQ / dK / dV (backward) or m->mask NULL: LSTC_E_NULL;
+ *   a non-positive size, a negative stride, dropout_p outside [0, 1], in the backward a stride of 0 of Q, K or V over an axis
+ *   longer than 1 (the gradient would have several writers per element): LSTC_E_SHAPE; then the limits.
+ * Bit-reproducible run to run, forward and backward: one writer per element, fixed summation order, no float atomics. */
+typedef struct LstcSdpaDesc {
+    int32_t N, H, Sq, Sk, dk, dv;
+    int64_t q_sn, q_sh, q_st;       /* element strides of Q (and dQ) over sequence, head, token */
+    int64_t k_sn, k_sh, k_st;       /* of K (and dK) */
+    int64_t v_sn, v_sh, v_st;       /* of V (and dV) */
+    int64_t o_sn, o_sh, o_st;       /* of O (and dO) */
+    float   scale;                  /* multiplies Q: 1 / temperature (:18) */
+    float   dropout_p;
+    uint64_t dropout_seed;
+    const void* Q; const void* K; const void* V;
+    void*  O;
+    float* probs;                   /* dense [N, H, Sq, Sk] f32: written by the forward, read by the backward */
+    /* backward only */
+    const void* dO;
+    void* dQ; void* dK; void* dV;
+} LstcSdpaDesc;
+int lstc_sdpa_fwd(const LstcSdpaDesc* d, const LstcAttnMask* mask_or_null, void* stream);
+int lstc_sdpa_bwd(const LstcSdpaDesc* d, const LstcAttnMask* mask_or_null, void* stream);
+
 /* Re-associated CLS attention of the last layer: with one query per (sequence, head) the key / value projections are
  * never materialised — score[n,h,j] = u[n,h].x[n,j] with u = (q_h*scale) Wk_h, and o[n,h] = Wv_h (sum_j p[n,h,j] x[n,j]) —
  * which removes the layer's two [N*S,d]x[d,H*dk] projection GEMMs and their four backward GEMMs (same reference lines

@@ -21,7 +21,7 @@ EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 
 EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
-    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_cls_dot", "lstc_cls_wsum",
+    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_cls_dot", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
@@ -63,6 +63,18 @@ class AttnDesc(C.Structure):
 class AttnMask(C.Structure):
     """LstcAttnMask (include/lstc_hip.h): a byte mask and its element strides over (n, h, query, key); 0 = broadcast."""
     _fields_ = [("mask", C.c_void_p), ("sn", C.c_int64), ("sh", C.c_int64), ("sq", C.c_int64), ("sk", C.c_int64)]
+
+
+class SdpaDesc(C.Structure):
+    """LstcSdpaDesc (include/lstc_hip.h): rectangular attention, Q / K / V / O through (sequence, head, token) element strides."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("Sq", C.c_int32), ("Sk", C.c_int32), ("dk", C.c_int32), ("dv", C.c_int32),
+                ("q_sn", C.c_int64), ("q_sh", C.c_int64), ("q_st", C.c_int64),
+                ("k_sn", C.c_int64), ("k_sh", C.c_int64), ("k_st", C.c_int64),
+                ("v_sn", C.c_int64), ("v_sh", C.c_int64), ("v_st", C.c_int64),
+                ("o_sn", C.c_int64), ("o_sh", C.c_int64), ("o_st", C.c_int64),
+                ("scale", C.c_float), ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64),
+                ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("probs", C.c_void_p),
+                ("dO", C.c_void_p), ("dQ", C.c_void_p), ("dK", C.c_void_p), ("dV", C.c_void_p)]
 
 
 class PackItem(C.Structure):
@@ -114,6 +126,8 @@ def load():
         "lstc_attn_bwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
         "lstc_attn_cls_fwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
         "lstc_attn_cls_bwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
+        "lstc_sdpa_fwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
+        "lstc_sdpa_bwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_cls_dot": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
         "lstc_cls_wsum": [vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_outer": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],

@@ -1002,21 +1002,23 @@ def attn_packed_inputs(N, S, H, dk, dv) -> bool:
             dk % 64 == 0 and dv % 64 == 0 and N * S * H * (2 * dk + dv) * 2 < 2 ** 31)
 
 
-def attn_mask_arg(mask, N, H, S, device=None):
+def attn_mask_arg(mask, N, H, S, device=None, Sk=None):
     """Normalise an attention mask for the ``*_masked`` entry points (include/lstc_hip.h, LstcAttnMask): anything torch broadcasts
     against [N, H, S, S] - [S, S], [1, 1, S, S], [N, 1, 1, S] (key padding), [N, 1, S, S], [N, H, S, S] - of any dtype, zero =
     masked (the reference's ``masked_fill(mask == 0, -1e9)``).  Returns ``(m, strides)``: ``m`` a uint8 view of shape
     [N, H, S, S] with values in {0, 1} over a buffer of the mask's OWN size (``expand``: a broadcast axis has stride 0, nothing
     is copied out to [N, H, S, S]), ``strides`` its four element strides.  Pure torch; runs on CPU tensors.  ``device``: where the
-    bytes should live (moved before the expand)."""
+    bytes should live (moved before the expand).  ``Sk``: the key length where it differs from the query length ``S`` (the
+    rectangular ``sdpa_*`` calls: the mask broadcasts against [N, H, S, Sk]); default the square case."""
     if not torch.is_tensor(mask):
         raise TypeError(f"attention mask: expected a tensor, got {type(mask).__name__}")
-    full = (int(N), int(H), int(S), int(S))
+    full = (int(N), int(H), int(S), int(S if Sk is None else Sk))
+    what = "[N, H, S, S]" if Sk is None else "[N, H, Sq, Sk]"
     if mask.dim() > 4:
-        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against [N, H, S, S] = {list(full)}")
+        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against {what} = {list(full)}")
     shape = (1,) * (4 - mask.dim()) + tuple(mask.shape)
     if any(a != b and a != 1 for a, b in zip(shape, full)):
-        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against [N, H, S, S] = {list(full)}")
+        raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast against {what} = {list(full)}")
     m8 = (mask != 0).to(torch.uint8).reshape(shape)
     if device is not None:
         m8 = m8.to(device)
@@ -1163,6 +1165,89 @@ def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, ou
         M = N * S
         return (Packed(bufs[0], M, H * dk, _lib.BF16P), Packed(bufs[1], M, H * dk, _lib.BF16P), Packed(bufs[2], M, H * dv, _lib.BF16P), dtable)
     return dq, dk_, dv_, dtable
+
+
+def _sdpa_operand(t):
+    """A [b, H, l, d] operand of the rectangular attention as the kernels address it: any strides over (sequence, head, token),
+    feature stride 1 - a copy only where that last one fails."""
+    if t.dim() != 4:
+        raise ValueError(f"sdpa: expected a [b, H, l, d] tensor, got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"sdpa: float32 operands only, got {t.dtype}")
+    return t if t.stride(3) == 1 else t.contiguous()
+
+
+def _sdpa_desc(q, k, v, o, probs, scale, p_drop, seed):
+    N, H, Sq, dk = q.shape
+    Sk, dv = k.shape[2], v.shape[3]
+    if k.shape[0] != N or k.shape[1] != H or v.shape[0] != N or v.shape[1] != H:
+        raise ValueError(f"sdpa: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} differ in batch or heads")
+    if k.shape[3] != dk:
+        raise ValueError(f"sdpa: d_k of q ({dk}) and k ({k.shape[3]}) differ")
+    if v.shape[2] != Sk:
+        raise ValueError(f"sdpa: len_k ({Sk}) and len_v ({v.shape[2]}) differ")
+    d = _lib.SdpaDesc()
+    d.N, d.H, d.Sq, d.Sk, d.dk, d.dv = N, H, Sq, Sk, dk, dv
+    d.q_sn, d.q_sh, d.q_st = q.stride(0), q.stride(1), q.stride(2)
+    d.k_sn, d.k_sh, d.k_st = k.stride(0), k.stride(1), k.stride(2)
+    d.v_sn, d.v_sh, d.v_st = v.stride(0), v.stride(1), v.stride(2)
+    d.o_sn, d.o_sh, d.o_st = o.stride(0), o.stride(1), o.stride(2)
+    d.scale, d.dropout_p, d.dropout_seed = float(scale), float(p_drop), int(seed)
+    d.Q, d.K, d.V, d.probs = dev_ptr(q), dev_ptr(k), dev_ptr(v), dev_ptr(probs)
+    return d
+
+
+def sdpa_fwd(q, k, v, scale, p_drop=0.0, seed=0, mask=None):
+    """Rectangular attention forward (lstc_sdpa_fwd): q [b, H, len_q, d_k], k [b, H, len_k, d_k], v [b, H, len_k, d_v] through their
+    own strides (head-major tensors and ``transpose(1, 2)`` views of token-major projections alike; ``.contiguous()`` only where
+    the feature stride is not 1).  ``mask``: a normalised mask (``attn_mask_arg(..., Sk=len_k)``) or None.  Returns
+    (O [b, H, len_q, d_v], P [b, H, len_q, len_k] before dropout), both contiguous."""
+    q, k, v = _sdpa_operand(q), _sdpa_operand(k), _sdpa_operand(v)
+    o = torch.empty((q.shape[0], q.shape[1], q.shape[2], v.shape[3]), device=q.device, dtype=torch.float32)
+    probs = torch.empty((q.shape[0], q.shape[1], q.shape[2], k.shape[2]), device=q.device, dtype=torch.float32)
+    d = _sdpa_desc(q, k, v, o, probs, scale, p_drop, seed)
+    d.O = dev_ptr(o)
+    check(_lib.load().lstc_sdpa_fwd(C.byref(d), C.byref(_mask_desc(mask)) if mask is not None else None, stream_ptr()), "lstc_sdpa_fwd")
+    return o, probs
+
+
+def sdpa_bwd(do, q, k, v, probs, scale, p_drop=0.0, seed=0, mask=None):
+    """Rectangular attention backward (lstc_sdpa_bwd) from the saved P: returns (dQ, dK, dV) with the strides of q, k, v.  ``do`` is
+    read through its own strides; ``mask``, ``p_drop`` and ``seed`` as the forward ran."""
+    q, k, v, do = _sdpa_operand(q), _sdpa_operand(k), _sdpa_operand(v), _sdpa_operand(do)
+    if tuple(do.shape) != (q.shape[0], q.shape[1], q.shape[2], v.shape[3]):
+        raise ValueError(f"sdpa_bwd: dO of shape {tuple(do.shape)} for q {tuple(q.shape)}, v {tuple(v.shape)}")
+    if not probs.is_contiguous() or tuple(probs.shape) != (q.shape[0], q.shape[1], q.shape[2], k.shape[2]):
+        raise RuntimeError("sdpa_bwd: probs must be the dense [b, H, len_q, len_k] tensor the forward returned")
+    # dQ, dK, dV take the strides of Q, K, V (one stride triple per operand in the descriptor); an expanded operand (stride 0)
+    # would give one gradient element several writers, so it is materialised first
+    q, k, v = (t.contiguous() if any(st == 0 and n > 1 for st, n in zip(t.stride(), t.shape)) else t for t in (q, k, v))
+    d = _sdpa_desc(q, k, v, do, probs, scale, p_drop, seed)
+    d.dO = dev_ptr(do)
+    grads = tuple(torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=torch.float32) for t in (q, k, v))
+    d.dQ, d.dK, d.dV = (dev_ptr(g) for g in grads)
+    check(_lib.load().lstc_sdpa_bwd(C.byref(d), C.byref(_mask_desc(mask)) if mask is not None else None, stream_ptr()), "lstc_sdpa_bwd")
+    return grads
+
+
+class SDPAFunction(torch.autograd.Function):
+    """``(q, k, v, mask, scale, p_drop, seed) -> (O, P)`` on the rectangular attention kernels; gradients to q, k and v.  ``mask`` is
+    a normalised mask or None; P (before dropout) is returned non-differentiable, as ``MHAFunction`` ignores ``_dprobs``."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, scale, p_drop, seed):
+        o, probs = sdpa_fwd(q, k, v, scale, p_drop, seed, mask)
+        ctx.save_for_backward(q, k, v, probs)
+        ctx.cfg = (mask, scale, p_drop, seed)
+        ctx.mark_non_differentiable(probs)
+        return o, probs
+
+    @staticmethod
+    def backward(ctx, do, _dprobs):
+        q, k, v, probs = ctx.saved_tensors
+        mask, scale, p_drop, seed = ctx.cfg
+        dq, dk_, dv_ = sdpa_bwd(do, q, k, v, probs, scale, p_drop, seed, mask)
+        return dq, dk_, dv_, None, None, None, None
 
 
 def _fused_qkv_weight(wq, wk, wv):

@@ -1,4 +1,5 @@
-"""Drop-in for the reference ``models/MultiHeadAttention.py`` (class surface: :28-30, forward :93-132).
+"""Drop-in for the reference ``models/MultiHeadAttention.py`` (class surfaces: ``ScaledDotProductAttention`` :9-23,
+``MultiHeadAttention`` :28-30, forward :93-132).
 
 Parameters keep the reference names (``w_qs/w_ks/w_vs/fc`` bias-free ``nn.Linear`` holders, ``layer_norm``,
 ``relative_position_bias_table`` + buffer ``relative_position_index``) so published checkpoints load; the
@@ -7,7 +8,8 @@ arithmetic runs in ``MHAFunction`` (GEMM -> fused attention core -> GEMM epilogu
 import torch
 from torch import nn
 
-from ..functional import MHAClsAssocFunction, MHAClsFunction, MHAFunction, PackedAct, attn_mask_arg
+from ..functional import (MHAClsAssocFunction, MHAClsFunction, MHAFunction, PackedAct, SDPAFunction, attn_mask_arg, dropout_apply,
+                          next_seed)
 
 
 def relative_position_index_3d(window_depth: int, window_size: int) -> torch.Tensor:
@@ -29,6 +31,39 @@ def relative_position_index_2d(window_size: int) -> torch.Tensor:
     dw = (t % window_size).view(-1, 1) - (t % window_size).view(1, -1)
     span = 2 * window_size - 1
     return ((dh + window_size - 1) * span + (dw + window_size - 1)).long()
+
+
+class ScaledDotProductAttention(nn.Module):
+    """The reference's scaled dot-product attention (:9-23) on the rectangular HIP kernels (csrc/attention_x.hip):
+    q [b, H, len_q, d_k], k [b, H, len_k, d_k], v [b, H, len_k, d_v], len_q and len_k independent (1..512 each), no relative bias.
+    ``dropout`` is the rate holder (state-less); the mask comes from the HIP RNG."""
+
+    def __init__(self, temperature, attn_dropout=0.1):
+        super().__init__()
+        self.temperature = temperature
+        self.dropout = nn.Dropout(attn_dropout)
+
+    def forward(self, q, k, v, mask=None, relative_pe=False, window_size=4):
+        """Returns ``(output [b, H, len_q, d_v], attn [b, H, len_q, len_k])``.  ``mask``: anything torch broadcasts against
+        [b, H, len_q, len_k], any dtype, zero = masked (:19-20).  ``attn`` is the softmax in ``eval()`` and the dropped, rescaled
+        probabilities in training (:21 returns ``dropout(softmax(...))``); it carries no gradient.  ``relative_pe`` and
+        ``window_size`` are accepted and unused, as upstream."""
+        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise ValueError(f"expected [b, H, len, d] tensors, got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+        if k.shape[3] != q.shape[3]:
+            raise ValueError(f"d_k of q ({q.shape[3]}) and k ({k.shape[3]}) differ")
+        if v.shape[2] != k.shape[2]:
+            raise ValueError(f"len_k ({k.shape[2]}) and len_v ({v.shape[2]}) differ")
+        if not (q.is_cuda and k.is_cuda and v.is_cuda):
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        if mask is not None:
+            mask = attn_mask_arg(mask, q.shape[0], q.shape[1], q.shape[2], device=q.device, Sk=k.shape[2])
+        p = self.dropout.p if self.training else 0.0
+        seed = next_seed() if p > 0 else 0
+        out, probs = SDPAFunction.apply(q, k, v, mask, 1.0 / self.temperature, p, seed)
+        if p > 0:
+            return out, dropout_apply(probs, p, seed)
+        return out, probs
 
 
 class MultiHeadAttention(nn.Module):
