@@ -106,9 +106,9 @@ typedef struct LstcGemmDesc {
                                        selects the persistent kernel); LSTC_F32 in the production library: 4 = the default loop
                                        without the row split, 8 = its fallback for unaligned operands (scalar epilogue: the
                                        reference of the bitwise tests), 11 = the 64x64 tail tile, 12 = the persistent walk of the
-                                       default loop (bit-identical, measured slower); anything else -> LSTC_E_UNSUPPORTED.  The
-                                       other tile variants (1-3, 5-7, 9, 10) and the timing-only ablations (13-15) exist only in
-                                       -DLSTC_TUNING builds (`make tuning`, tools/tuning/gemm_check), never in the production library.
+                                       default loop (bit-identical, measured slower); anything else -> LSTC_E_UNSUPPORTED.
+                                       LSTC_F32X3: 0 = 3 = the 128x128 two-stage kernel (256x128 tiles for long weight gradients),
+                                       2 = the 256x128-tile kernel; anything else -> LSTC_E_UNSUPPORTED.
                                        LSTC_BF16P: 0, or LSTC_VARIANT_NO_QTAIL = the product as ONE persistent launch of 256 x 256 tiles,
                                        without the quarter-tile kernel that otherwise takes the tiles behind the last whole round of
                                        workgroups (bit-identical results: the reference of the bitwise tests) */

@@ -15,22 +15,10 @@
 // sequences before one atomic flush.
 #include "attention_common.h"
 
-// Grid of the first / second generation kernels: one workgroup per (chunk of sequences, head).  ATTN_HEAD_FAST: the HEAD is the
-// fast grid index, so the workgroups dispatched together read the 8 heads' 1-KB column slices of the SAME token rows - whole 8-KB
-// rows of Q / K / V / dO per DRAM page - instead of one 1-KB slice out of every 8 KB of far-apart rows (A/B builds: 0 = chunk fast,
-// the order of rounds 1-3).  gridDim.y <= 65535 bounds the chunk count in that form.
-#ifndef ATTN_HEAD_FAST
-#define ATTN_HEAD_FAST 0
-#endif
-#if ATTN_HEAD_FAST
-#define ATTN_CHUNK ((int)blockIdx.y)
-#define ATTN_HEAD ((int)blockIdx.x)
-#define ATTN_GRID(chunks, H) dim3((unsigned)(H), (unsigned)(chunks))
-#else
+// Grid of the first / second generation kernels: one workgroup per (chunk of sequences, head), the chunk the fast grid index.
 #define ATTN_CHUNK ((int)blockIdx.x)
 #define ATTN_HEAD ((int)blockIdx.y)
 #define ATTN_GRID(chunks, H) dim3((unsigned)(chunks), (unsigned)(H))
-#endif
 
 namespace {
 using namespace lstc_attn;
@@ -191,7 +179,7 @@ __device__ __forceinline__ void lds_times_rows(const float* __restrict__ Alds, c
 // First-generation kernels (S <= 128), forward and backward.
 // MASKED: where the mask byte of (n, h, i, j) is 0 the scaled logit is replaced by ATTN_MASK_FILL before the bias is added; in the
 // backward the saved P carries the mask already, so dV and the row sums do not change.  The unmasked instantiation compiles to
-// what the kernel was before masks existed (tools/attn_isa_diff.py).
+// what the kernel was before masks existed (tools/isa_diff.py).
 template <int T, bool MASKED>
 __global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
     const DropKey dkn = drop_key_now(p.dkey);

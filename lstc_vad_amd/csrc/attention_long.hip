@@ -135,7 +135,7 @@ __device__ __forceinline__ void zero_acc(floatx16 (&acc)[DT]) {
 }
 
 // MASKED: the mask (attention_common.h MaskParams) as the second argument; the unmasked instantiation compiles to what the kernel
-// was before masks existed (tools/attn_isa_diff.py).
+// was before masks existed (tools/isa_diff.py).
 template <bool BF, int DT, bool MASKED>
 __global__ void __launch_bounds__(LNT, DT == 8 ? 1 : 2) attn_long_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
     const DropKey dkn = drop_key_now(p.dkey);

@@ -25,7 +25,6 @@
 //   U0 = A rows/features of every wave's FIRST 64 (read in phase 0), U1 = B first 32 (phase 0), U2 = B second 32 (phase 1),
 //   U3 = A second 64 (phase 2).  Issue at (tile t, phase p): p0 U2(t+1), p1 U3(t+1), p2 U0(t+2), p3 U1(t+2) - each region was
 //   last read >= 2 phases earlier (WAR), each unit lands >= 5 phases before its first read (RAW: vmcnt(4) at p3 + barrier).
-#include <cstdlib>
 #include <type_traits>
 #include "lstc_common.h"
 
@@ -35,26 +34,11 @@ typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4v __attribute__((ext_vector_type(4)));
 
-#ifndef P1_NT_S16
-#define P1_NT_S16 1                      // NT form on v_mfma_f32_16x16x32_bf16 (0: 32x32x16, A/B builds)
-#endif
-#ifndef P1_TR_S16
-#define P1_TR_S16 0                      // 1: the TR (weight-gradient) form on v_mfma_f32_16x16x32_bf16 too (A/B builds).  Measured, round 6:
-                                         // correct (tools/gemm_check check: ALL PASS) but the register allocator no longer fits the loop into
-                                         // 256 VGPRs (40 - 58 spills, scratch reloads inside the LOAD segments drain the LDS-DMA queue):
-                                         // 2048 x 2048 x 100352 924 TFLOP/s against 1122 on 32x32x16, 6144 x 2048 954 against 1254 - stays off
-#endif
-#ifndef P1_SPLIT_MAJOR
-#define P1_SPLIT_MAJOR 1                 // item order, see set_item (0 / 0: the round-3 order, A/B builds)
-#endif
-#ifndef P1_GROUP_M
-#define P1_GROUP_M 4
-#endif
-#ifndef P1_RPK_ASM
-#define P1_RPK_ASM 1                     // packed residual loads of the pipelined epilogue: 1 = inline asm with hand-counted waits (default);
-                                         // 0 = ordinary loads - the compiler then sinks them below the hand-placed waits and spills around
-                                         // them (scratch traffic counts in vmcnt too): wrong results with a bias, kept only as a warning
-#endif
+// The NT form runs on v_mfma_f32_16x16x32_bf16 (S16), the TR (weight-gradient) form on 32x32x16.  TR on 16x16x32 (the kernel text
+// still reads its fragments: S16 + TR) was measured, round 6: correct (tools/gemm_check check: ALL PASS) but the register allocator
+// no longer fits the loop into 256 VGPRs (40 - 58 spills, scratch reloads inside the LOAD segments drain the LDS-DMA queue):
+// 2048 x 2048 x 100352 924 TFLOP/s against 1122 on 32x32x16, 6144 x 2048 954 against 1254.
+constexpr int P1_GROUP_M = 4;            // item order, see set_item
 constexpr int NT8 = 512;                 // 8 waves
 constexpr int P1_TILE = 4096;            // bf16 elements of one packed tile (128 rows x 32 k = 8 KB)
 constexpr int P1_SLOT = 2048;            // 64 rows x 32 k (4 KB)
@@ -206,23 +190,18 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
     int item = first;
     int mb = 0, nb = 0, kt0 = 0, nkt = 0;
     // item -> (K split, tile).  Consecutive items run side by side on one XCD (32 per round), so they should SHARE operands:
-    //   P1_SPLIT_MAJOR: the split index is the slow one (items of one split are consecutive: the tiles of a split share the token
+    //   split-major: the split index is the slow one (items of one split are consecutive: the tiles of a split share the token
     //     slices of both packs; split-fastest put the four splits of ONE tile side by side, which share nothing - the weight-
     //     gradient form then fetched the X pack once per XCD: 3.6 GB of L2 misses for 0.82 GB of packs);
     //   P1_GROUP_M: inside the tile index, groups of P1_GROUP_M consecutive M panels are walked M fastest, so 32 consecutive tiles
     //     cover P1_GROUP_M panels x 32 / P1_GROUP_M N tiles whatever tilesN is (row-major: 32 / tilesN panels x tilesN tiles -
     //     1.3 x 24 for the fused Q|K|V projection, whose 12-MB weight then streamed through every XCD's L2 each round).
-    // Same-box A/B (tools/bf16p_order_ab.sh, round 4): weight gradients 2048 x 2048 x 100352 0.661 -> 0.625 ms, 6144 x 2048 1.789 ->
+    // Same-box A/B (round 4): weight gradients 2048 x 2048 x 100352 0.661 -> 0.625 ms, 6144 x 2048 1.789 ->
     // 1.657, 2048 x 4096 1.186 -> 1.113 (FETCH_SIZE x 2 of the first: 3.63 -> 1.22 GB); forward N = 4096 1.517 -> 1.470, N = 6144
     // 2.213 -> 2.123 (FETCH x 2 9.6 -> 4.5 GB); N = 2048 products unchanged (8 N tiles: both orders coincide).
     auto set_item = [&](int w) {
-#if P1_SPLIT_MAJOR
         const int ntiles = p.tilesM * p.tilesN;
         const int sp = w / ntiles, tile = w - sp * ntiles;
-#else
-        const int tile = w / p.splits, sp = w - tile * p.splits;
-#endif
-#if P1_GROUP_M
         {
             const int per_group = P1_GROUP_M * p.tilesN;
             const int gid = tile / per_group, first_m = gid * P1_GROUP_M;
@@ -231,9 +210,6 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
             mb = first_m + loc % gsz;
             nb = loc / gsz;
         }
-#else
-        mb = tile / p.tilesN; nb = tile - mb * p.tilesN;
-#endif
         kt0 = sp * p.steps_per_split;
         nkt = min(p.nsteps, kt0 + p.steps_per_split) - kt0;
     };
@@ -389,15 +365,8 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
         if (nkt > 1) { P1_DMA_UNIT(0, 1, 1); P1_DMA_UNIT(1, 1, 1); P1_DMA_UNIT(2, 1, 1); P1_DMA_UNIT(3, 1, 1); }
     };
 
-#ifndef P1_DMA_IN_COMPUTE
-#define P1_DMA_IN_COMPUTE 0
-#endif
-#ifndef P1_DMA_FIRST
-#define P1_DMA_FIRST 0        /* 1: a LOAD segment issues its LDS-DMA unit BEFORE its fragment reads */
-#endif
-/* MID: statement issued between the two halves of the phase's MFMA burst (P1_DMA_IN_COMPUTE: this phase's LDS-DMA unit, so that
-   the LOAD segment holds nothing but the fragment reads) */
-#define P1_MMA(ih, jj, rs, ...)                                                                                         \
+/* two sched_barriers between the halves of the phase's MFMA burst: with one, the TR loop's registers are allocated differently */
+#define P1_MMA(ih, jj, rs)                                                                                              \
     do {                                                                                                               \
         __builtin_amdgcn_s_setprio(1);                                                                                 \
         if constexpr (S16) {                                                                                           \
@@ -408,14 +377,14 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                             OPK ? fb[rs][2 * kk + ct] : fa[2 * kk + (rt >> 1)][rt & 1],                                 \
                             OPK ? fa[2 * kk + (rt >> 1)][rt & 1] : fb[rs][2 * kk + ct],                                 \
                             (HEAD && kk == 0) ? floatx4v{0.f, 0.f, 0.f, 0.f} : a4[4 * (ih) + rt][2 * (jj) + ct], 0, 0, 0); \
-                if (kk == 0) { __builtin_amdgcn_sched_barrier(0); __VA_ARGS__; __builtin_amdgcn_sched_barrier(0); }     \
+                if (kk == 0) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0); }                  \
             }                                                                                                          \
         } else {                                                                                                       \
             _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                             \
                 _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                                        \
                     acc[S16 ? 0 : 2 * (ih) + ii][S16 ? 0 : jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                 \
                         fa[q][ii], fb[rs][q], (HEAD && q == 0) ? floatx16{} : acc[S16 ? 0 : 2 * (ih) + ii][S16 ? 0 : jj], 0, 0, 0); \
-                if (q == 1) { __builtin_amdgcn_sched_barrier(0); __VA_ARGS__; __builtin_amdgcn_sched_barrier(0); }      \
+                if (q == 1) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_sched_barrier(0); }                   \
             }                                                                                                          \
         }                                                                                                              \
         __builtin_amdgcn_s_setprio(0);                                                                                 \
@@ -424,14 +393,14 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
    waves 0-3 is the opening barrier of waves 4-7, so a wait that must precede a read which waves 0-3 issue right after their
    closing barrier has to sit before the opening one (before the closing one it let waves 0-3 read pieces whose DMA waves 4-7 had
    not waited for yet: a rare mismatch of a weight gradient on a cold first launch). */
-#define P1_SYNC_COMPUTE(ih, jj, rs, vmw, ...)                                                                             \
+#define P1_SYNC_COMPUTE(ih, jj, rs, vmw)                                                                                  \
     do {                                                                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
         if constexpr ((vmw) >= 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm((vmw) >= 0 ? (vmw) : 0));                       \
         __builtin_amdgcn_s_barrier();                                                                                  \
         __builtin_amdgcn_s_waitcnt(0xC07F);          /* lgkmcnt(0): this phase's fragments are in registers */         \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
-        P1_MMA(ih, jj, rs, __VA_ARGS__);                                                                                         \
+        P1_MMA(ih, jj, rs);                                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
         __builtin_amdgcn_s_barrier();                                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
@@ -457,64 +426,44 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
             for (int q = 0; q < 4; ++q) fb[X][q] = S16 ? rd_b16(cur, q & 1, q >> 1) : rd_b(cur, 0, q);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (P1_DMA_FIRST) { if (!HEAD && has1) P1_DMA_UNIT(2, tl + 1, CUR ^ 1); }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             fa[q][0] = S16 ? rd_a16(cur, 0, 2 * (q & 1), q >> 1) : rd_a(cur, 0, q);
             fa[q][1] = S16 ? rd_a16(cur, 0, 2 * (q & 1) + 1, q >> 1) : rd_a(cur, 1, q);
         }
-        if constexpr (P1_DMA_IN_COMPUTE) {
-            P1_SYNC_COMPUTE(0, 0, X, -1, if (!HEAD && has1) P1_DMA_UNIT(2, tl + 1, CUR ^ 1));
-        } else {
-            if constexpr (!P1_DMA_FIRST) { if (!HEAD && has1) P1_DMA_UNIT(2, tl + 1, CUR ^ 1); }
-            P1_SYNC_COMPUTE(0, 0, X, -1, (void)0);
-        }
+        if (!HEAD && has1) P1_DMA_UNIT(2, tl + 1, CUR ^ 1);
+        P1_SYNC_COMPUTE(0, 0, X, -1);
         // ---- phase 1: (first 64 rows, second 32 cols)
-        if constexpr (P1_DMA_FIRST) { if (!HEAD && has1) P1_DMA_UNIT(3, tl + 1, CUR ^ 1); }
 #pragma unroll
         for (int q = 0; q < 4; ++q) fb[Y][q] = S16 ? rd_b16(cur, 2 + (q & 1), q >> 1) : rd_b(cur, 1, q);
-        if constexpr (P1_DMA_IN_COMPUTE) {
-            P1_SYNC_COMPUTE(0, 1, Y, -1, if (!HEAD && has1) P1_DMA_UNIT(3, tl + 1, CUR ^ 1));
-        } else {
-            if constexpr (!P1_DMA_FIRST) { if (!HEAD && has1) P1_DMA_UNIT(3, tl + 1, CUR ^ 1); }
-            P1_SYNC_COMPUTE(0, 1, Y, -1, (void)0);
-        }
+        if (!HEAD && has1) P1_DMA_UNIT(3, tl + 1, CUR ^ 1);
+        P1_SYNC_COMPUTE(0, 1, Y, -1);
         // ---- phase 2: (second 64 rows, second 32 cols).  Before its OPENING barrier: unit U1 of step t+1 (B cols 0-31, issued
         // >= 3 phases ago) has landed - younger operations: U2, U3 of t+1 (4), U0 of t+2 (2), the previous item's stores (HEAD)
-        if constexpr (P1_DMA_FIRST) { if (has2) P1_DMA_UNIT(0, tl + 2, CUR); }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             fa[q][0] = S16 ? rd_a16(cur, 1, 2 * (q & 1), q >> 1) : rd_a(cur, 2, q);
             fa[q][1] = S16 ? rd_a16(cur, 1, 2 * (q & 1) + 1, q >> 1) : rd_a(cur, 3, q);
         }
-        if constexpr (P1_DMA_IN_COMPUTE) {      // U0 of step t+2 is issued after the wait: younger ops are U2, U3 of t+1 only
-            P1_SYNC_COMPUTE(1, 1, Y, 4 + (HEAD ? PEND : 0), if (has2) P1_DMA_UNIT(0, tl + 2, CUR));
-        } else if (has2) {
-            if constexpr (!P1_DMA_FIRST) P1_DMA_UNIT(0, tl + 2, CUR);
-            P1_SYNC_COMPUTE(1, 1, Y, 6 + (HEAD ? PEND : 0), (void)0);
+        if (has2) {
+            P1_DMA_UNIT(0, tl + 2, CUR);
+            P1_SYNC_COMPUTE(1, 1, Y, 6 + (HEAD ? PEND : 0));
         } else {
-            P1_SYNC_COMPUTE(1, 1, Y, 4 + (HEAD ? PEND : 0), (void)0);
+            P1_SYNC_COMPUTE(1, 1, Y, 4 + (HEAD ? PEND : 0));
         }
         // ---- phase 3: (second 64 rows, first 32 cols): reads fb cols 0-31 of step t+1 into the set phase 2 just released; K step
         // t+1 must have landed whole before the next step's reads
-        if constexpr (P1_DMA_FIRST) { if (has2) P1_DMA_UNIT(1, tl + 2, CUR); }
         if (has1) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) fb[Y][q] = S16 ? rd_b16(nxt, q & 1, q >> 1) : rd_b(nxt, 0, q);
         }
-        if constexpr (P1_DMA_IN_COMPUTE) {      // U1 of step t+2 is issued after the wait: only U0 of t+2 (and the stores) may be open
-            if (has2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 + (HEAD ? PEND : 0)));
-            else __builtin_amdgcn_s_waitcnt(vmcnt_imm(HEAD ? PEND : 0));
-            P1_SYNC_COMPUTE(1, 0, X, -1, if (has2) P1_DMA_UNIT(1, tl + 2, CUR));
+        if (has2) {
+            P1_DMA_UNIT(1, tl + 2, CUR);
+            __builtin_amdgcn_s_waitcnt(vmcnt_imm(4 + (HEAD ? PEND : 0)));   // everything but U0, U1 of step t+2 (and the stores)
         } else {
-            if (has2) {
-                if constexpr (!P1_DMA_FIRST) P1_DMA_UNIT(1, tl + 2, CUR);
-                __builtin_amdgcn_s_waitcnt(vmcnt_imm(4 + (HEAD ? PEND : 0)));   // everything but U0, U1 of step t+2 (and the stores)
-            } else {
-                __builtin_amdgcn_s_waitcnt(vmcnt_imm(HEAD ? PEND : 0));
-            }
-            P1_SYNC_COMPUTE(1, 0, X, -1, (void)0);
+            __builtin_amdgcn_s_waitcnt(vmcnt_imm(HEAD ? PEND : 0));
         }
+        P1_SYNC_COMPUTE(1, 0, X, -1);
     };
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
@@ -819,8 +768,8 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                         } else if constexpr (RPK) {   /* the tile address is wave-uniform (SGPRs), the lane offset one of two VGPRs */ \
                             const bf16_t* rb_ = reinterpret_cast<const bf16_t*>(p.res) +                                  \
                                 ((size_t)(2 * cmb + wr) * p.res_kbp + cnb * 8 + wc * 2 + ((b) >> 2)) * P1_TILE + (2 * ((b) & 3) + (g_ >> 1)) * 512; \
-                            if constexpr (P1_RPK_ASM) asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(axr[RPK ? set : 0][RPK ? g_ : 0]) : "v"((g_ & 1) ? offP1 : offP0), "s"(rb_) : "memory"); \
-                            else axr[RPK ? set : 0][RPK ? g_ : 0] = *reinterpret_cast<const uint2v*>(reinterpret_cast<const char*>(rb_) + ((g_ & 1) ? offP1 : offP0)); \
+                            /* inline asm with hand-counted waits: as an ordinary load the compiler sinks it below the hand-placed waits and spills around it (scratch traffic counts in vmcnt too) - wrong results with a bias */ \
+                            asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(axr[RPK ? set : 0][RPK ? g_ : 0]) : "v"((g_ & 1) ? offP1 : offP0), "s"(rb_) : "memory"); \
                         } else {                                                                                        \
                             const float* ab_ = aux + (size_t)(urow0 + (2 * ((b) & 3) + (g_ >> 1)) * 16 + 4 * (g_ & 1)) * ldx + (ucol0 + 32 * ((b) >> 2)); \
                             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(ax[set][g_]) : "v"(offX), "s"(ab_) : "memory"); \
@@ -895,7 +844,7 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                     if (b == 0) { asm volatile("" : "+v"(fbias[0]), "+v"(fbias[1])); }
 #pragma unroll
                     for (int g_ = 0; g_ < 4; ++g_) {
-                        if constexpr (RPK && P1_RPK_ASM) asm volatile("" : "+v"(axr[RPK ? (b & 1) : 0][RPK ? g_ : 0]));
+                        if constexpr (RPK) asm volatile("" : "+v"(axr[RPK ? (b & 1) : 0][RPK ? g_ : 0]));
                         else if constexpr (!MPK) asm volatile("" : "+v"(ax[b & 1][g_]));
                     }
                     const int cp2 = b >> 2;
@@ -1119,16 +1068,12 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
 //     each, copied verbatim - one producer wave per tile, 8 x 1 KB.  Q_NS stages of 32 KB; the DMA of step s + Q_NS - 1 is issued when
 //     step s - 1's stage falls free, fragment registers are double-buffered (reads of step s + 1 beside the MFMAs of step s),
 //     ONE s_barrier per K step.
-#ifndef P1_QTAIL_ROUNDS
-#define P1_QTAIL_ROUNDS 2                 // rounds of quarter items a launch's tail may take (LSTC_P1_QTAIL overrides at run time; 0 = off)
-#endif
-#ifndef P1_Q_NS
-#define P1_Q_NS 4                         // 5 (all 160 KB of the CU, one more K step to land) measured: no change - 2048 x 2048 x 2048 0.024 ms, K = 4096
-#endif                                    // 0.046 either way.  The item is not latency-bound: a 16-tile product (64 workgroups, 192 CUs idle) takes the
+constexpr int P1_QTAIL_ROUNDS = 2;        // rounds of quarter items a launch's tail may take
+constexpr int Q_NS = 4;                   // stages (32 KB each); the DMA of a K step has Q_NS - 2 steps to land.
+                                          // 5 (all 160 KB of the CU, one more K step to land) measured: no change - 2048 x 2048 x 2048 0.024 ms, K = 4096
+                                          // 0.046 either way.  The item is not latency-bound: a 16-tile product (64 workgroups, 192 CUs idle) takes the
                                           // same 0.66 us per K step as a 64-tile one - 32 KB per step and CU = 48 GB/s per CU, the rate the 256 x 256
                                           // loop's 64 KB per 1.33 us comes to as well: the CU's LDS-DMA intake (profiles/r06_qtail5_ab.txt)
-constexpr int Q_NS = P1_Q_NS;             // stages (32 KB each); the DMA of a K step has Q_NS - 2 steps to land
-static_assert(Q_NS == 4 || Q_NS == 5, "quarter items: four or five stages");
 constexpr int Q_STAGE = 4 * P1_TILE;      // A k0 | A k1 | B k0 | B k1
 template <int EPK>
 __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, const int tile0) {
@@ -1145,7 +1090,6 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
     const int item = (nblk & 7) ? (int)blockIdx.x : ((int)(blockIdx.x & 7) * (nblk >> 3) + (int)(blockIdx.x >> 3));
     const int tile = tile0 + (item >> 2), qr = (item >> 1) & 1, qc = item & 1;
     int mb, nb;
-#if P1_GROUP_M
     {
         const int per_group = P1_GROUP_M * p.tilesN;
         const int gid = tile / per_group, first_m = gid * P1_GROUP_M;
@@ -1154,9 +1098,6 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
         mb = first_m + loc % gsz;
         nb = loc / gsz;
     }
-#else
-    mb = tile / p.tilesN; nb = tile - mb * p.tilesN;
-#endif
     const int nkt = p.nsteps;
     const uint32_t lane_off = (uint32_t)lane * 16u;
     // producer wave pw copies pack tile pw of a stage: 0 / 1 = A (row block 2 mb + qr), k tiles 2 s / 2 s + 1; 2 / 3 = B (2 nb + qc)
@@ -1456,7 +1397,7 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
 #else
         const int tile_variant = d->variant & ~LSTC_VARIANT_NO_QTAIL;
 #endif
-        if (tr || splits > 1 || !P1_NT_S16 || d->M % 256 || d->N % 256 || (d->flags & LSTC_EPI_ACCUM) || tile_variant != 0 ||
+        if (tr || splits > 1 || d->M % 256 || d->N % 256 || (d->flags & LSTC_EPI_ACCUM) || tile_variant != 0 ||
             (p.mask_kbp && (!(d->flags & LSTC_EPI_RELU_MASK) || (d->flags & LSTC_EPI_RESIDUAL)))) return LSTC_E_UNSUPPORTED;
         if (p.out_kbp && !aligned16(d->C)) return LSTC_E_ALIGN;
         // one per-element operand stream per epilogue (the hand-counted loads): residual OR ReLU mask, never both
@@ -1510,7 +1451,7 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
         n_cu_dev[dev_ & 63].store(n > 0 ? n : 256, std::memory_order_relaxed);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<true, P1_TR_S16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<false, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel<false, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1531,14 +1472,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
     // time: two rounds of them still beat one round of tiles, three do not).  NT form on 16x16x32, no K split, 16-B epilogue accesses.
     const int epk_ = p.res_kbp ? 4 : p.out_kbp ? (p.mask_kbp ? 2 : 1) : (p.mask_kbp ? 3 : 0);
     int q_tiles = 0;
-    if (!tr && P1_NT_S16 && eff_splits == 1 && p.vec_epi && epk_ != 3 && !no_qtail && variant_ == 0 && n_cu > 0) {
-        static const int q_rounds = [] {
-            const char* e = getenv("LSTC_P1_QTAIL");            // 0 = off (A/B runs), 1 .. 3 = rounds of quarter items allowed
-            const int v = e ? atoi(e) : P1_QTAIL_ROUNDS;
-            return v < 0 ? 0 : v > 3 ? 3 : v;
-        }();
+    if (!tr && eff_splits == 1 && p.vec_epi && epk_ != 3 && !no_qtail && variant_ == 0 && n_cu > 0) {
         const int tail = p.total_items % n_cu;
-        if (tail > 0 && 4 * tail <= q_rounds * n_cu) { q_tiles = tail; p.total_items -= tail; }
+        if (tail > 0 && 4 * tail <= P1_QTAIL_ROUNDS * n_cu) { q_tiles = tail; p.total_items -= tail; }
     }
     const int grid = p.total_items < n_cu ? p.total_items : n_cu;
     if (q_tiles) {
@@ -1558,16 +1494,15 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
         else hipLaunchKernelGGL((gemm_bf16p_q_kernel<4>), dim3(4 * q_tiles), dim3(NT8), q_lds, st, p, tile0);
         return lstc_launch_status();
     }
-    if (tr) hipLaunchKernelGGL((gemm_bf16p_kernel<true, P1_TR_S16 != 0>), dim3(grid), dim3(NT8), lds, st, p);
-    else if (P1_NT_S16) {
-        const int epk = p.res_kbp ? 4 : p.out_kbp ? (p.mask_kbp ? 2 : 1) : (p.mask_kbp ? 3 : 0);
+    if (tr) hipLaunchKernelGGL((gemm_bf16p_kernel<true, false>), dim3(grid), dim3(NT8), lds, st, p);
+    else {
+        const int epk = epk_;
         if (epk == 0) hipLaunchKernelGGL((gemm_bf16p_kernel<false, true, 0>), dim3(grid), dim3(NT8), lds, st, p);
         else if (epk == 1) hipLaunchKernelGGL((gemm_bf16p_kernel<false, true, 1>), dim3(grid), dim3(NT8), lds, st, p);
         else if (epk == 2) hipLaunchKernelGGL((gemm_bf16p_kernel<false, true, 2>), dim3(grid), dim3(NT8), lds, st, p);
         else if (epk == 4) hipLaunchKernelGGL((gemm_bf16p_kernel<false, true, 4>), dim3(grid), dim3(NT8), lds, st, p);
         else hipLaunchKernelGGL((gemm_bf16p_kernel<false, true, 3>), dim3(grid), dim3(NT8), lds, st, p);
     }
-    else hipLaunchKernelGGL((gemm_bf16p_kernel<false, false>), dim3(grid), dim3(NT8), lds, st, p);
     return lstc_launch_status();
 }
 

@@ -27,19 +27,11 @@
 #include "lstc_common.h"
 #include <type_traits>
 
-#ifndef LSTC_F32_GROUP_M
-#define LSTC_F32_GROUP_M 8          /* grouped tile order inside an XCD's run, see the tile map (0: row-major, the order of rounds 1-3) */
-#endif
 namespace {
 
+constexpr int LSTC_F32_GROUP_M = 8;   // grouped tile order inside an XCD's run, see the tile map
 constexpr int BK = 32;
 constexpr int LDK = 36;   // padded K stride of K-contiguous LDS images
-#ifndef LSTC_KCT
-#define LSTC_KCT 0
-#endif
-// LSTC_KCT = 1: K-contiguous operands are TRANSPOSED while they are written to LDS ([32][rows+1] image, 4 ds_write_b32 per
-// staged float4, conflict-free because rows+1 = 1 mod 32) and read back like k-major operands with ds_read_b32.
-constexpr bool KCT = LSTC_KCT != 0;
 
 struct GemmParams {
     const float* A;
@@ -56,7 +48,7 @@ struct GemmParams {
     int ktiles, ktiles_per_split;
     long long batch_stride_a, batch_stride_b, batch_stride_c;   // elements between consecutive problems of a batch (grid.z)
     unsigned int a_bytes, b_bytes;   // operand extents for the buffer descriptors of PIPE 5 (operands < 4 GiB)
-    int debug;     // timing-only ablations (tools/gemm_check): 1 = no global loads in the loop, 2 = no LDS writes, 4 = no barrier
+    int unused_ = 0;   // keeps the kernel-argument offsets of the two fields below, and with them every kernel's machine code, as they were
     int row_off;   // first row of this launch inside the caller's matrix (dropout counter of a row-split product)
     int epi_f4;    // 0: scalar epilogue; 1 / 2: float4 epilogue allowed, without / with ONE per-element operand (epilogue_f4)
 };
@@ -154,13 +146,7 @@ struct Stager {
     __device__ __forceinline__ void store_one(int i, float* __restrict__ lds) const {
         const int t = threadIdx.x;
         if (KC) {
-            if (KCT) {
-                const int r = (t >> 3) + i * (NT / 8), c = (t & 7) * 4;
-                lds[(c + 0) * (R + 1) + r] = v[i].x; lds[(c + 1) * (R + 1) + r] = v[i].y;
-                lds[(c + 2) * (R + 1) + r] = v[i].z; lds[(c + 3) * (R + 1) + r] = v[i].w;
-            } else {
-                *reinterpret_cast<float4*>(lds + ((t >> 3) + i * (NT / 8)) * LDK + (t & 7) * 4) = v[i];
-            }
+            *reinterpret_cast<float4*>(lds + ((t >> 3) + i * (NT / 8)) * LDK + (t & 7) * 4) = v[i];
         } else {
             constexpr int CPR = R / 4;
             *reinterpret_cast<float4*>(lds + (t / CPR + i * (NT / CPR)) * R + (t % CPR) * 4) = v[i];
@@ -174,12 +160,7 @@ struct Stager {
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int r = (t >> 3) + i * (NT / 8);
-                if (KCT) {
-                    lds[(c + 0) * (R + 1) + r] = v[i].x; lds[(c + 1) * (R + 1) + r] = v[i].y;
-                    lds[(c + 2) * (R + 1) + r] = v[i].z; lds[(c + 3) * (R + 1) + r] = v[i].w;
-                } else {
-                    *reinterpret_cast<float4*>(lds + r * LDK + c) = v[i];
-                }
+                *reinterpret_cast<float4*>(lds + r * LDK + c) = v[i];
             }
         } else {
             constexpr int CPR = R / 4;
@@ -194,16 +175,12 @@ struct Stager {
 };
 
 template <int R, bool KC>
-constexpr int stage_floats() { return KC ? (KCT ? ((BK * (R + 1) + 3) / 4) * 4 : R * LDK) : BK * R; }
+constexpr int stage_floats() { return KC ? R * LDK : BK * R; }
 
 // Reads this lane's 8 k-values (k = 16*h + 8*half + j) of operand row `row` from the LDS image.
 template <int R, bool KC>
 __device__ __forceinline__ void read_frag(const float* __restrict__ lds, int row, int h, int half, float (&f)[8]) {
-    if (KC && KCT) {
-        const float* p = lds + (16 * h + 8 * half) * (R + 1) + row;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = p[j * (R + 1)];
-    } else if (KC) {
+    if (KC) {
         const float4* p = reinterpret_cast<const float4*>(lds + row * LDK + 16 * h + 8 * half);
         const float4 a = p[0], b = p[1];
         f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
@@ -215,15 +192,14 @@ __device__ __forceinline__ void read_frag(const float* __restrict__ lds, int row
     }
 }
 
-template <int BM, int BN, int WGM, int WGN, int PIPE_ABL, bool A_KC, bool B_KC, bool VA, bool VB>
+template <int BM, int BN, int WGM, int WGN, int PIPE, bool A_KC, bool B_KC, bool VA, bool VB>
 __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParams p_in) {
     GemmParams p = p_in;
     p.dk = drop_key_now(p.dk);          // graph replays: seed + device offset (lstc_dropout_seed_device)
     p.A += (size_t)blockIdx.z * p.batch_stride_a;
     p.B += (size_t)blockIdx.z * p.batch_stride_b;
     p.C += (size_t)blockIdx.z * p.batch_stride_c;
-    constexpr int PIPE = PIPE_ABL & 15;
-    constexpr int ABL = PIPE_ABL >> 4;     // timing-only ablation of the PIPE 3 body: 1 no global loads, 2 no LDS writes, 4 no barrier
+    static_assert(PIPE == 0 || PIPE == 3 || PIPE == 5, "the three pipeline forms of launch_layout");
     constexpr int NT = WGM * WGN * 64;
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -241,10 +217,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
         const int q = nwg >> 3, r = nwg & 7;
         pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-#if LSTC_F32_GROUP_M
     // grouped order: inside the linear tile index, groups of GROUP_M consecutive M panels are walked M fastest, so the 64 tiles
     // resident on an XCD cover 8 panels x 8 N tiles instead of 4 x 16 (N = 2048): per K step they touch 8 + 8 operand chunks
-    // instead of 4 + 16.  Same-box A/B (tools/f32_group_ab.sh, round 4), 100352 x 2048 x 2048: FETCH_SIZE 3.61e6 -> 2.41e6 KB (HBM-side
+    // instead of 4 + 16.  Same-box A/B (round 4), 100352 x 2048 x 2048: FETCH_SIZE 3.61e6 -> 2.41e6 KB (HBM-side
     // traffic per launch 8.04 -> 5.64 GB), L2 hit rate 70.6 -> 79.4 %, 5.62 -> 5.60 ms (NT), 5.65 -> 5.61 (NN), N = 4096 11.27 -> 11.21
     int mt, nt;
     {
@@ -256,9 +231,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
         mt = first_m + loc % gsz;
         nt = loc / gsz;
     }
-#else
-    const int mt = pid / p.tilesN, nt = pid % p.tilesN;
-#endif
     const int m0 = mt * BM, n0 = nt * BN;
     const int kt0 = blockIdx.y * p.ktiles_per_split;
     const int kt1 = min(p.ktiles, kt0 + p.ktiles_per_split);
@@ -296,130 +268,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
     //   barrier: publishes tile t+1 and retires every read of tile t's stage
     //   phase 2: LDS-read the 1st-half fragments of tile t+1   -> hidden behind the 2nd-half MFMAs of tile t
     // so a wave reaches each MFMA block with its operands already in registers; only barrier skew is exposed.
-    if constexpr (PIPE == 4) {
-        // ---- LDS-DMA staging (global_load_lds_dwordx4): operand tiles go HBM/L2 -> LDS without passing through
-        // VGPRs, so the steady state has no ds_write (2.6 % of the PIPE 3 time) and no staging registers.
-        // A DMA wave-instruction writes 1 KB lane-linearly (base + 16*lane), so the LDS images are UNPADDED:
-        //   K-contiguous operand: [rows][32 floats]; bank conflicts of the ds_read_b128 fragment reads are removed
-        //     by XOR-ing the 16-B chunk index with (row>>1)&7 — applied to the per-lane SOURCE address of the DMA and
-        //     to the read address (cdna_hip_programming rule 21: same involution on both sides, linear destination);
-        //   k-major operand: [32][rows], naturally lane-linear (one piece = 2 k rows of 128 floats).
-        // Pipeline: tile t+2 is DMA'd into the stage tile t just vacated, right after the mid-tile barrier of
-        // iteration t; __syncthreads() of iteration t+1 (which carries s_waitcnt vmcnt(0)) publishes it.
-        static_assert(VA && VB, "LDS-DMA path needs 16-B aligned rows");
-        constexpr int ST = 32 * BM, STB = 32 * BN;          // floats per stage
-        float* const A4 = smem;
-        float* const B4 = smem + 2 * ST;
-        constexpr int PA = BM / 32, PB = BN / 32;           // 1-KB pieces per wave per stage (NT = 256: 4 waves)
-        static_assert(NT == 256, "piece assignment assumes 4 waves");
-        // per-lane source pointers of this wave's pieces at k = 0 (rows clamped; k advances by pointer arithmetic)
-        const float* ga[PA];
-        const float* gb[PB];
-#pragma unroll
-        for (int j = 0; j < PA; ++j) {
-            const int pi = wave * PA + j;
-            if (A_KC) {
-                const int row = pi * 8 + (lane >> 3), cp = lane & 7;
-                ga[j] = p.A + (size_t)min(m0 + row, p.M - 1) * p.lda + ((cp ^ ((row >> 1) & 7)) << 2);
-            } else {
-                const int f = pi * 256 + lane * 4;
-                ga[j] = p.A + (size_t)(f / BM) * p.lda + min(m0 + f % BM, p.M - 4);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-            const int pi = wave * PB + j;
-            if (B_KC) {
-                const int row = pi * 8 + (lane >> 3), cp = lane & 7;
-                gb[j] = p.B + (size_t)min(n0 + row, p.N - 1) * p.ldb + ((cp ^ ((row >> 1) & 7)) << 2);
-            } else {
-                const int f = pi * 256 + lane * 4;
-                gb[j] = p.B + (size_t)(f / BN) * p.ldb + min(n0 + f % BN, p.N - 4);
-            }
-        }
-        const size_t a_kstep = A_KC ? (size_t)BK : (size_t)BK * p.lda;     // floats per K tile
-        const size_t b_kstep = B_KC ? (size_t)BK : (size_t)BK * p.ldb;
-        typedef __attribute__((address_space(1))) const void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
-        auto dma_a = [&](int j, int kt, int stage) {
-            __builtin_amdgcn_global_load_lds((gptr_t)(ga[j] + (size_t)kt * a_kstep),
-                                             (lptr_t)(A4 + stage * ST + (wave * PA + j) * 256), 16, 0, 0);
-        };
-        auto dma_b = [&](int j, int kt, int stage) {
-            __builtin_amdgcn_global_load_lds((gptr_t)(gb[j] + (size_t)kt * b_kstep),
-                                             (lptr_t)(B4 + stage * STB + (wave * PB + j) * 256), 16, 0, 0);
-        };
-        // fragment read from the unpadded images
-        auto frag = [&](const float* lds, bool kc, int R, int row, int half, float (&f)[8]) {
-            if (kc) {
-                const int c0 = 4 * h + 2 * half, sw = (row >> 1) & 7;
-                const float4 a = *reinterpret_cast<const float4*>(lds + row * 32 + ((c0 ^ sw) << 2));
-                const float4 b = *reinterpret_cast<const float4*>(lds + row * 32 + (((c0 + 1) ^ sw) << 2));
-                f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-            } else {
-                const float* q = lds + (16 * h + 8 * half) * R + row;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f[j] = q[j * R];
-            }
-        };
-        float fa0[TM][8], fb0[TN][8], fa1[TM][8], fb1[TN][8];
-        if (nkt > 0) {
-#pragma unroll
-            for (int j = 0; j < PA; ++j) dma_a(j, kt0, 0);
-#pragma unroll
-            for (int j = 0; j < PB; ++j) dma_b(j, kt0, 0);
-            if (nkt > 1) {
-#pragma unroll
-                for (int j = 0; j < PA; ++j) dma_a(j, kt0 + 1, 1);
-#pragma unroll
-                for (int j = 0; j < PB; ++j) dma_b(j, kt0 + 1, 1);
-            }
-        }
-        __syncthreads();
-        if (nkt > 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) frag(A4, A_KC, BM, wm * WTM + i * 32 + l31, 0, fa0[i]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) frag(B4, B_KC, BN, wn * WTN + j * 32 + l31, 0, fb0[j]);
-        }
-        for (int it = 0; it < nkt; ++it) {
-            const int cur = it & 1;
-            const float* a_lds = A4 + cur * ST;
-            const float* b_lds = B4 + cur * STB;
-            const float* a_nx = A4 + (cur ^ 1) * ST;
-            const float* b_nx = B4 + (cur ^ 1) * STB;
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {           // phase 1: 2nd-half fragments of tile t behind its 1st-half MFMAs
-                if (kk < TM) frag(a_lds, A_KC, BM, wm * WTM + kk * 32 + l31, 1, fa1[kk < TM ? kk : 0]);
-                else if (kk - TM < TN) frag(b_lds, B_KC, BN, wn * WTN + (kk - TM) * 32 + l31, 1, fb1[kk - TM < TN ? kk - TM : 0]);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[i][kk], fb0[j][kk], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();                           // tile t+1 landed (vmcnt(0)) and every read of tile t retired
-            const bool more1 = it + 1 < nkt, more2 = it + 2 < nkt;
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {           // phase 2: DMA tile t+2 into the freed stage; frags of tile t+1
-                if (more2) {
-                    if (kk < PA) dma_a(kk < PA ? kk : 0, kt0 + it + 2, cur);
-                    else if (kk - PA < PB) dma_b(kk - PA < PB ? kk - PA : 0, kt0 + it + 2, cur);
-                }
-                if (more1) {
-                    if (kk < TM) frag(a_nx, A_KC, BM, wm * WTM + kk * 32 + l31, 0, fa0[kk < TM ? kk : 0]);
-                    else if (kk - TM < TN) frag(b_nx, B_KC, BN, wn * WTN + (kk - TM) * 32 + l31, 0, fb0[kk - TM < TN ? kk - TM : 0]);
-                }
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[i][kk], fb1[j][kk], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    } else
     if constexpr (PIPE == 0) {
         // Plain double buffering: global loads of tile t+1 issued before the MFMAs of tile t, LDS write after them,
         // one barrier at the end of the tile (fragment reads of the next tile are exposed after the barrier).
@@ -432,7 +280,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
         for (int it = 0; it < nkt; ++it) {
             const int cur = it & 1;
             const bool more = it + 1 < nkt;
-            if (more && !(p.debug & 1)) gload(kt0 + it + 1);
+            if (more) gload(kt0 + it + 1);
             const float* a_lds = As + cur * A_ST;
             const float* b_lds = Bs + cur * B_ST;
 #pragma unroll
@@ -450,11 +298,11 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
                         for (int j = 0; j < TN; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][kk], bf[j][kk], acc[i][j], 0, 0, 0);
             }
-            if (more && !(p.debug & 2)) {
+            if (more) {
                 sa.store(As + (cur ^ 1) * A_ST);
                 sb.store(Bs + (cur ^ 1) * B_ST);
             }
-            if (!(p.debug & 4)) __syncthreads();
+            __syncthreads();
         }
     } else {
     float fa0[TM][8], fb0[TN][8], fa1[TM][8], fb1[TN][8];
@@ -471,11 +319,10 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
 #pragma unroll
         for (int j = 0; j < TN; ++j) read_frag<BN, B_KC>(Bs, wn * WTN + j * 32 + l31, h, 0, fb0[j]);
     }
-    // One K tile.  STEADY (compile-time): tiles it+1 and it+2 exist and are full -> branch-free body whose memory
-    // instructions are interleaved with the MFMAs by sched_group_barrier (PIPE == 2): a wave-level global load that
-    // touches 8 separate 128-B lines holds the issue port for tens of cycles; clustered at the top of the tile they
-    // delayed the MFMA stream of BOTH waves of the SIMD (measured: -11 % on the NT layout), spread two MFMAs apart
-    // they disappear in the 64-cycle shadow of each MFMA.
+    // One K tile.  STEADY (compile-time): tiles it+1 and it+2 exist and are full -> branch-free, hand-interleaved body:
+    // a wave-level global load that touches 8 separate 128-B lines holds the issue port for tens of cycles; clustered
+    // at the top of the tile they delayed the MFMA stream of BOTH waves of the SIMD (measured: -11 % on the NT layout),
+    // spread over the k steps they disappear in the 64-cycle shadow of each MFMA.
     // PIPE 5 = PIPE 3 with fewer non-MFMA instructions in the steady loop (tools/mfma_issue_probe: every companion
     // instruction costs the MFMA pipe ~7 idle cycles even at two waves per SIMD; PIPE 3 carried 72 per 64 MFMAs):
     // global loads become buffer_load_dwordx4 with a loop-invariant per-lane voffset and a scalar K offset (no 64-bit
@@ -504,7 +351,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
         const int cur = CC >= 0 ? CC : (it & 1);
         const float* a_lds = As + cur * A_ST;
         const float* b_lds = Bs + cur * B_ST;
-        if constexpr (STEADY && (PIPE == 3 || PIPE == 5)) {
+        if constexpr (STEADY) {
             // Hand-interleaved steady state: each group of TM*TN independent MFMAs (one k step, all accumulators)
             // carries at most one LDS write, one global load and one fragment read, pinned by sched_barrier so the
             // compiler neither clusters the memory instructions nor chains MFMAs on one accumulator.
@@ -529,7 +376,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
                 for (int q = 0; q < 2 * MPK; ++q) {
                     const int e = (kk & 3) * 2 * MPK + q;
                     if (kk < 4) {
-                        if constexpr (!(ABL & 2) && HAS1) {
+                        if constexpr (HAS1) {
                             if (e < NVA) sa.store_one(e, a_st);
                             else if (e - NVA < NVB) sb.store_one(e - NVA, b_st);
                         }
@@ -537,7 +384,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
                         if constexpr (PIPE == 5) {
                             if (e < NVA) sa.load_buf(e, rsrc_a, voff_a[e < NVA ? e : 0], soff_a);
                             else if (e - NVA < NVB) sb.load_buf(e - NVA, rsrc_b, voff_b[e - NVA < NVB ? e - NVA : 0], soff_b);
-                        } else if constexpr (!(ABL & 1)) {
+                        } else {
                             if (e < NVA) sa.load_one(e, p.A, p.lda, m0, p.M, k_next);
                             else if (e - NVA < NVB) sb.load_one(e - NVA, p.B, p.ldb, n0, p.N, k_next);
                         }
@@ -552,7 +399,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[i][kk], fb0[j][kk], acc[i][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (!(ABL & 4)) __syncthreads();
+            __syncthreads();
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk) {
                 if constexpr (HAS1) {
@@ -568,21 +415,17 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
             }
             return;
         }
-        if (STEADY || it + 1 < nkt) {
+        // generic body (STEADY is false here): runtime conditions and checked loads, for the K tail
+        if (it + 1 < nkt) {
             sa.store(As + (cur ^ 1) * A_ST);
             sb.store(Bs + (cur ^ 1) * B_ST);
         }
-        if (STEADY) {
-            sa.template load<false>(p.A, p.lda, m0, p.M, (kt0 + it + 2) * BK, p.K);
-            sb.template load<false>(p.B, p.ldb, n0, p.N, (kt0 + it + 2) * BK, p.K);
-        } else if (it + 2 < nkt) {
-            gload(kt0 + it + 2);
-        }
+        if (it + 2 < nkt) gload(kt0 + it + 2);
 #pragma unroll
         for (int i = 0; i < TM; ++i) read_frag<BM, A_KC>(a_lds, wm * WTM + i * 32 + l31, h, 1, fa1[i]);
 #pragma unroll
         for (int j = 0; j < TN; ++j) read_frag<BN, B_KC>(b_lds, wn * WTN + j * 32 + l31, h, 1, fb1[j]);
-        if (!(STEADY && PIPE == 2)) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk)
 #pragma unroll
@@ -590,26 +433,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[i][kk], fb0[j][kk], acc[i][j], 0, 0, 0);
-        if constexpr (STEADY && PIPE == 2 && VA && VB) {
-            constexpr int NRD = (A_KC ? 2 * TM : 8 * TM) + (B_KC ? 2 * TN : 8 * TN);     // fragment reads
-            constexpr int NWR = Stager<BM, NT, A_KC, VA>::NV + Stager<BN, NT, B_KC, VB>::NV;   // ds_write_b128 == global loads
-            constexpr int NMF = TM * TN * 8;
-            constexpr int PER = NMF / (2 * NWR) > 0 ? NMF / (2 * NWR) : 1;
-            __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);              // fragment reads first (needed after the barrier)
-#pragma unroll
-            for (int q = 0; q < NWR; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);            // ds_write  (tile it+1)
-                __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);          // MFMA
-            }
-#pragma unroll
-            for (int q = 0; q < NWR; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);            // global load (tile it+2)
-                __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-            }
-        }
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
-        if (STEADY || it + 1 < nkt) {
+        if (it + 1 < nkt) {
             const float* a_nx = As + (cur ^ 1) * A_ST;
             const float* b_nx = Bs + (cur ^ 1) * B_ST;
 #pragma unroll
@@ -617,7 +443,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
 #pragma unroll
             for (int j = 0; j < TN; ++j) read_frag<BN, B_KC>(b_nx, wn * WTN + j * 32 + l31, h, 0, fb0[j]);
         }
-        if (!(STEADY && PIPE == 2)) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk)
 #pragma unroll
@@ -651,7 +477,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
     }
 
     // ---- epilogue
-    if constexpr (TM <= 2 && TN <= 2 && (PIPE_ABL & 15) == 5) {
+    if constexpr (TM <= 2 && TN <= 2 && PIPE == 5) {
         if (p.epi_f4 && gridDim.y == 1) {                       // float4 form (host checked alignment and the operand count)
             const EpiArgs ea = LSTC_EPI_ARGS(p);
             if (p.epi_f4 == 2) epilogue_f4<TM, TN, true>(ea, acc, m0 + wm * WTM, n0 + wn * WTN, lane);
@@ -907,8 +733,8 @@ int launch_cfg(const GemmParams& p, bool va, bool vb, int splits, hipStream_t st
         }                                                                                                   \
         hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                  \
     } while (0)
-    if constexpr ((PIPE & 15) == 4 || (PIPE & 15) == 5) {
-        LSTC_GO(true, true);               // LDS-DMA / buffer-load paths: aligned operands only (caller guarantees va && vb)
+    if constexpr (PIPE == 5) {
+        LSTC_GO(true, true);               // buffer-load path: aligned operands only (caller guarantees va && vb)
     } else {
         if (va && vb) LSTC_GO(true, true);
         else if (va) LSTC_GO(true, false);
@@ -921,33 +747,20 @@ int launch_cfg(const GemmParams& p, bool va, bool vb, int splits, hipStream_t st
 
 template <bool A_KC, bool B_KC>
 int launch_layout(GemmParams& p, bool va, bool vb, int splits, int variant, hipStream_t st) {
-    variant &= 15;
     // variant: 0 = library default.  Measured on MI355X, LTN shapes, TFLOP/s NT / NN / TN(split-K 4)
-    // (profiles/r01_gemm_variants.log, tools/gemm_check):
-    //   1 = 128x128, plain double buffering (PIPE 0)                              117 / 129 / 134
-    //   7 = 128x128, mid-barrier software pipeline (PIPE 1)                       126 / 127 / 128
-    //   3 = 128x128, pipeline + sched_group_barrier interleave (PIPE 2)           136 / 131 / 129
-    //   8 = 128x128, pipeline + hand-interleaved k-step groups (PIPE 3)           138 / 136 / 138   (fallback of 4)
-    //   4 = PIPE 3 + buffer loads with scalar K offset, K loop unrolled x2 (PIPE 5) 145 / 143 / 151   <- default
+    // (profiles/r01_gemm_variants.log, tools/gemm_check; the forms that lost are in DESIGN 3.1):
+    //   8 = 128x128, mid-barrier pipeline with hand-interleaved k-step groups (PIPE 3)   138 / 136 / 138   (fallback of 4)
+    //   4 = PIPE 3 + buffer loads with scalar K offset, K loop unrolled x2 (PIPE 5)      145 / 143 / 151   <- default
     //       (steady loop: 49 instead of 72 non-MFMA instructions per 64 MFMAs; needs 16-B aligned operands < 4 GiB)
-    //   9 = 256x128, 4 waves x (128x64), one wave per SIMD, PIPE 3                125 / 124 / 134
-    //  11 = 64x64, 4 waves x (32x32), plain double buffering: same k order per output element as every other variant, used for
-    //       the last rows of a product whose 128x128 tile count leaves the final round of workgroup slots mostly empty
-    //  10 = 128x128, LDS-DMA staging (global_load_lds, swizzled unpadded images)  105 / 119 / 134   (correct, slower:
-    //       the swizzled per-lane source addresses of K-contiguous operands and the one-iteration latency budget cost
-    //       more than the ds_write + staging registers they remove)
-    //   2, 6, 5 = 256x128 with 8 waves (PIPE 1 / 2 / 0)                           115-126, never the best
-    //  13-15 = (-DLSTC_TUNING builds only) timing-only ablations of variant 8 (NT): no loads 142, no loads/LDS writes 146,
-    //          +no barrier 146.5.  12 is the persistent kernel in EVERY build.
-    // The PRODUCTION library (`make all`) holds 0 = 4, 8 (the default's fallback), 11 and 12; variants 1-3, 5-7, 9, 10 are compiled into
-    // `make tuning` builds only (tools/tuning/liblstc_hip.so) and refused here otherwise.
+    //  11 = 64x64, 4 waves x (32x32), plain double buffering (PIPE 0): same k order per output element as every other variant,
+    //       used for the last rows of a product whose 128x128 tile count leaves the final round of workgroup slots mostly empty
+    //  12 = persistent PIPE 5 (gemm_f32_persist_kernel): next tile's first loads before the epilogue, float4 epilogue
     if (variant == 0) variant = 4;
-    const int BM = (variant == 2 || variant == 5 || variant == 6 || variant == 9) ? 256 : variant == 11 ? 64 : 128, BN = variant == 11 ? 64 : 128;
+    const int BM = variant == 11 ? 64 : 128, BN = BM;
     p.tilesM = (p.M + BM - 1) / BM;
     p.tilesN = (p.N + BN - 1) / BN;
     switch (variant) {
         case 11: return launch_cfg<64, 64, 2, 2, 0, A_KC, B_KC>(p, va, vb, splits, st);    // small tile: the tail rows of a row-split product
-        //  12 = persistent PIPE 5 (gemm_f32_persist_kernel): next tile's first loads before the epilogue, float4 epilogue
         case 12: if (va && vb && p.a_bytes && p.b_bytes && splits == 1 && p.batch == 1 && p.K % BK == 0 && p.ktiles >= 4 && p.epi_f4)
                  {
                      const int rc_ = launch_persist<A_KC, B_KC>(p, st);
@@ -958,21 +771,6 @@ int launch_layout(GemmParams& p, bool va, bool vb, int splits, int variant, hipS
         case 8: return launch_cfg<128, 128, 2, 2, 3, A_KC, B_KC>(p, va, vb, splits, st);   // = the default's fallback for unaligned operands
         case 4: if (va && vb && p.a_bytes && p.b_bytes) return launch_cfg<128, 128, 2, 2, 5, A_KC, B_KC>(p, true, true, splits, st);
                 return launch_cfg<128, 128, 2, 2, 3, A_KC, B_KC>(p, va, vb, splits, st);   // buffer path: aligned, < 4 GiB operands
-#ifdef LSTC_TUNING      // `make tuning` only (VERDICT r5 upkeep): the tile variants the product never selects - ~110 kernel instantiations,
-                        // half of the production library's size and build time - and the timing-only ablations (wrong products by construction)
-        case 1: return launch_cfg<128, 128, 2, 2, 0, A_KC, B_KC>(p, va, vb, splits, st);
-        case 3: return launch_cfg<128, 128, 2, 2, 2, A_KC, B_KC>(p, va, vb, splits, st);
-        case 6: return launch_cfg<256, 128, 4, 2, 2, A_KC, B_KC>(p, va, vb, splits, st);
-        case 2: return launch_cfg<256, 128, 4, 2, 1, A_KC, B_KC>(p, va, vb, splits, st);
-        case 5: return launch_cfg<256, 128, 4, 2, 0, A_KC, B_KC>(p, va, vb, splits, st);
-        case 7: return launch_cfg<128, 128, 2, 2, 1, A_KC, B_KC>(p, va, vb, splits, st);
-        case 9: return launch_cfg<256, 128, 4, 2, 3, A_KC, B_KC>(p, va, vb, splits, st);   // 8 waves x (64x64), PIPE 3
-        case 10: if (va && vb && p.K % BK == 0) return launch_cfg<128, 128, 2, 2, 4, A_KC, B_KC>(p, true, true, splits, st);
-                 return launch_cfg<128, 128, 2, 2, 3, A_KC, B_KC>(p, va, vb, splits, st);   // LDS-DMA needs aligned rows, full K tiles
-        case 13: if constexpr (A_KC && B_KC) return launch_cfg<128, 128, 2, 2, 3 + 16 * 1, A_KC, B_KC>(p, va, vb, splits, st); return LSTC_E_UNSUPPORTED;
-        case 14: if constexpr (A_KC && B_KC) return launch_cfg<128, 128, 2, 2, 3 + 16 * 3, A_KC, B_KC>(p, va, vb, splits, st); return LSTC_E_UNSUPPORTED;
-        case 15: if constexpr (A_KC && B_KC) return launch_cfg<128, 128, 2, 2, 3 + 16 * 7, A_KC, B_KC>(p, va, vb, splits, st); return LSTC_E_UNSUPPORTED;
-#endif
         default: return LSTC_E_UNSUPPORTED;
     }
 }
@@ -1003,14 +801,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32_impl(const LstcGemmDesc*
     if (p.batch > 65535) return LSTC_E_RANGE;
     p.ktiles = (d->K + BK - 1) / BK;
     p.ktiles_per_split = (p.ktiles + splits - 1) / splits;
-#ifdef LSTC_TUNING
-    p.debug = d->variant >> 4;          // tools/gemm_check ablations (no loads / no LDS writes / no barrier): wrong products
-#else
-    // the production library accepts the documented tile variants only: garbage in this public field must not select a
-    // timing ablation or an undefined tile (LstcGemmDesc.variant, include/lstc_hip.h)
+    // the documented tile variants only: garbage in this public field must not select an undefined tile
+    // (LstcGemmDesc.variant, include/lstc_hip.h)
     if (!(d->variant == 0 || d->variant == 4 || d->variant == 8 || d->variant == 11 || d->variant == 12)) return LSTC_E_UNSUPPORTED;
-    p.debug = 0;
-#endif
     const size_t a_ext = ((size_t)((d->transA ? d->K : d->M) - 1) * d->lda + (d->transA ? d->M : d->K)) * sizeof(float) + p.batch_stride_a * sizeof(float) * (size_t)(p.batch - 1) * 0;
     const size_t b_ext = ((size_t)((d->transB ? d->N : d->K) - 1) * d->ldb + (d->transB ? d->K : d->N)) * sizeof(float);
     const bool fits32 = a_ext < 0xffffffffull && b_ext < 0xffffffffull;

@@ -16,12 +16,13 @@
 // 16 distinct 16-B slots (MI355X_MICROARCH, LDS table).  Transposition happens in the pack pass too, so forward (X W^T)
 // and input-gradient (dY W) products share ONE NT kernel; weight gradients (dY^T X) reuse those very packs through
 // ds_read_b64_tr_b16 (TR form).  The GEMM streams tiles with global_load_lds_dwordx4 (1 KB contiguous per
-// wave-instruction, no staging registers, no ds_write) into a 3-stage LDS ring: tile t+3 is requested during the second
-// half of tile t, two K tiles ahead of its use.
+// wave-instruction, no staging registers, no ds_write) into a ring of LDS stages: two for the 128x128 kernel (tile t+2 is
+// requested during the second half of tile t), three for the 256x128 one (tile t+3, two K tiles ahead of its use).
 //
-// Schedule per K tile and wave (one wave per SIMD, 4 waves, 128x128 tile, 64x64 per wave): phase 1 = 12 MFMAs on k-step 0
-// fragments while the k-step 1 fragments are read; s_waitcnt vmcnt(8) + raw s_barrier (tile t+1 published, stage t free);
-// phase 2 = 12 MFMAs on k-step 1 while tile t+3 is requested and the k-step 0 fragments of tile t+1 are read.
+// Schedule per K tile and wave (4 waves, 128x128 tile, 64x64 per wave): phase 1 = 12 MFMAs on k-step 0 fragments while the
+// k-step 1 fragments are read; s_waitcnt + raw s_barrier (tile t+1 published, stage t free: __syncthreads() would add a
+// fence that drains EVERY LDS-DMA in flight); phase 2 = 12 MFMAs on k-step 1 while the next tile is requested and the
+// k-step 0 fragments of tile t+1 are read.
 #include "lstc_common.h"
 
 namespace {
@@ -33,7 +34,6 @@ constexpr int NT = 256;
 constexpr int PK_IMG = 4096;            // f16 elements of one plane image (128 rows x 32 k)
 constexpr int PK_TILE = 2 * PK_IMG;     // one packed tile: planes h, l
 constexpr int PK_STAGE = 2 * PK_TILE;   // A tile then B tile
-constexpr int PK_NSTAGE = 3;
 constexpr int PK_TRAILER = 256;         // bytes after the tiles: [0] absmax bits (u32), [1] 1/scale (f32)
 
 __device__ __forceinline__ void split2(float v, float scale, pk_t& h, pk_t& l) {
@@ -170,27 +170,20 @@ struct PkParams {
     int epi_f4;          // 0: scalar epilogue; 1 / 2: float4 epilogue (lstc_common.h, epilogue_f4) without / with one per-element operand
 };
 
-#ifndef PK_GROUP_M
-#define PK_GROUP_M 8          /* grouped tile order inside an XCD's run (as csrc/gemm_f32.hip); 0 = row-major, the order of rounds 1-3.
+constexpr int PK_GROUP_M = 8; /* grouped tile order inside an XCD's run (as csrc/gemm_f32.hip); 0 = row-major, the order of rounds 1-3.
                                  Same-box A/B, round 4: 100352 x 4096 x 2048 4.44 -> 4.13 ms, x 2048 x 2048 2.16 -> 2.14, weight gradient
                                  2.22 -> 2.15, f32x3 LTN step 117.1 / 117.2 -> 115.6 / 115.7 ms; bit-identical products.  Round 5: 2 / 4 / 16 against 8 on the
                                  step's four forward shapes: within 2 % of each other (16 is 8 % slower at K = 4096) although the launch
                                  moves 7.3 GB for 1.7 GB of operands (profiles/r05_gemm_pk_pmc.txt): the re-fetches are Infinity-Cache hits */
-#endif
-// linear tile index (after the XCD remap) -> (M tile, N tile): row-major, or groups of PK_GROUP_M consecutive M tiles walked M
+// linear tile index (after the XCD remap) -> (M tile, N tile): groups of PK_GROUP_M consecutive M tiles walked M
 // fastest - the 64 tiles resident on an XCD then cover 8 x 8 tiles instead of 4 x 16 and share twice as much per K step
 __device__ __forceinline__ void pk_tile_of(int pid, int tilesM, int tilesN, int& mb, int& nb) {
-#if PK_GROUP_M
     const int per_group = PK_GROUP_M * tilesN;
     const int gid = pid / per_group, first_m = gid * PK_GROUP_M;
     const int gsz = min(tilesM - first_m, PK_GROUP_M);
     const int loc = pid - gid * per_group;
     mb = first_m + loc % gsz;
     nb = loc / gsz;
-#else
-    mb = pid / tilesN;
-    nb = pid % tilesN;
-#endif
 }
 
 
@@ -201,214 +194,14 @@ __device__ __forceinline__ constexpr int pb(int q) { return q == 1 ? 1 : 0; }
 template <int SMODE, int CUR>
 struct StepTag { static constexpr int smode = SMODE, cur = CUR; };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 128x128 tile, two LDS stages, two workgroups per CU (64 KB of LDS and <= 256 registers per workgroup): the prologue
+// (tile requests before the first MFMA) and the epilogue of one workgroup overlap the K loop of the other, which matters
+// for the K = 2048 products (64 K steps per workgroup).
 // TR = false: operands packed as [M, K] / [N, K] (K along the 32-wide tile dimension), fragments by ds_read_b128.
 // TR = true (weight gradients, C = dY^T X): operands are the packs of the SOURCE matrices [K = tokens, M] / [K, N] as the
 // forward / input-gradient products already made them; a K step is 32 tokens = a contiguous 2-KB slice of each plane image,
 // and the fragments (8 consecutive tokens of one feature) come out of ds_read_b64_tr_b16, the hardware transpose read.
-template <bool TR>
-__global__ void __launch_bounds__(NT, 1) gemm_pk_kernel(const PkParams p) {
-    const DropKey dkn = drop_key_now(p.dk);
-    extern __shared__ __attribute__((aligned(16))) pk_t smem_pk[];
-    pk_t* const smem = smem_pk;
-    int pid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, xcd = pid & 7, idx = pid >> 3, q = nwg >> 3, r = nwg & 7;
-        pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    int mb, nb;
-    pk_tile_of(pid, (int)gridDim.x / p.tilesN, p.tilesN, mb, nb);
-    const int kt0 = blockIdx.y * p.ktiles_per_split;
-    const int nkt = min(p.KB, kt0 + p.ktiles_per_split) - kt0;
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, h = lane >> 5;
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    typedef __attribute__((address_space(1))) const void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    // a stage is 32 pieces of 1 KB: pieces 0..15 = the A tile, 16..31 = the B tile; wave w moves pieces 8w .. 8w+7
-    // (waves 0,1: A; waves 2,3: B).  gbase is wave-uniform (SGPRs); the lane adds 16 B * lane.
-    //   TR = false: the 16 KB of a packed tile are contiguous; piece j = 4 * (j / 4) + (j % 4), the low part rides in
-    //     the instruction's immediate offset (it applies to the global and the LDS side alike).
-    //   TR = true: K step kt = tokens 32 kt .. 32 kt + 31 = slice (kt % 4) of token block kt / 4; for each of the wave's
-    //     two 32-feature blocks and two planes one 2-KB slice = 2 pieces (immediate offset 0 / 1024).
-    const int opb = wave < 2 ? mb : nb, fb = wave < 2 ? p.fbA : p.fbB;
-    const pk_t* gbase = TR ? (wave < 2 ? p.A : p.B) + ((size_t)opb * 4 + (wave & 1) * 2) * PK_TILE
-                             : (wave < 2 ? p.A + ((size_t)mb * p.KB + kt0) * PK_TILE : p.B + ((size_t)nb * p.KB + kt0) * PK_TILE) +
-                                   (size_t)(wave & 1) * 8 * 512;
-    const int ldst = wave * 8 * 512;
-    auto koff = [&](int kt) -> size_t {      // element offset of K step kt (relative to kt0 for TR = false)
-        if (TR) { const int k = kt0 + kt; return ((size_t)(k >> 2) * fb) * PK_TILE + (size_t)(k & 3) * 1024; }
-        return (size_t)kt * PK_TILE;
-    };
-    // TR = true issues the DMA through inline asm: with the builtin the compiler knows these instructions write LDS, cannot
-    // tell the ds_read_b64_tr_b16 fragment reads apart from their destinations and drains vmcnt(0) before every read
-    // (2.7x slower).  All vmcnt waits of this kernel are explicit anyway (s_waitcnt before the barriers).
-#define DMA_ONE(j, kt, stage)                                                                                          \
-    do {                                                                                                               \
-        if (TR) {                                                                                                      \
-            const pk_t* g_ = gbase + koff(kt) + ((j) >> 2) * PK_TILE + (((j) & 3) >> 1) * PK_IMG + lane * 8;            \
-            const uint32_t l_ = (uint32_t)(((stage) * PK_STAGE + ldst + ((j) >> 1) * 1024) * 2);                        \
-            asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off offset:%2"                               \
-                         :: "v"(g_), "s"(l_), "n"(((j) & 1) * 1024) : "memory");                                       \
-        } else                                                                                                         \
-            __builtin_amdgcn_global_load_lds((gptr_t)(gbase + koff(kt) + ((j) >> 2) * 2048 + lane * 8),                 \
-                                             (lptr_t)(smem + (stage) * PK_STAGE + ldst + ((j) >> 2) * 2048), 16, ((j) & 3) * 1024, 0); \
-    } while (0)
-#define DMA_TILE(kt, stage)                                                                                            \
-    do {                                                                                                               \
-        DMA_ONE(0, kt, stage); DMA_ONE(1, kt, stage); DMA_ONE(2, kt, stage); DMA_ONE(3, kt, stage);                    \
-        DMA_ONE(4, kt, stage); DMA_ONE(5, kt, stage); DMA_ONE(6, kt, stage); DMA_ONE(7, kt, stage);                    \
-    } while (0)
-    // TR = false: fragment of k-step ks = row tile0 + l31, logical 16-B chunk 2h + ks (any K permutation shared by A, B).
-    // TR = true: stage layout per operand [feature block 0..3][plane][32 tokens x 64 B]; lane (h, g = 16-lane group & 1,
-    //   q, pp) addresses token 16 ks + 8 h + q (+4), features 16 g + 4 pp .. + 3 and receives feature lane & 31.
-    const int rowa0 = wm * 64 + l31, rowb0 = wn * 64 + l31;
-    const int trq = (lane >> 2) & 3, trchunk = 2 * ((lane >> 4) & 1) + ((lane & 3) >> 1), trsub = (lane & 1) * 4;
-    auto rd = [&](const pk_t* img, int row, int ks) -> pkx8 {
-        return *reinterpret_cast<const pkx8*>(img + (row * 4 + ((2 * h + ks) ^ ((row >> 2) & 3))) * 8);
-    };
-    auto rd_tr = [&](const pk_t* img, int ks) -> pkx8 {
-        typedef short short4v __attribute__((ext_vector_type(4)));
-        typedef short short8v __attribute__((ext_vector_type(8)));
-        typedef short4v __attribute__((address_space(3))) * lds_ptr;
-        const int t0 = 16 * ks + 8 * h + trq, t1 = t0 + 4;
-        const pk_t* a0 = img + t0 * 32 + ((trchunk ^ ((t0 >> 2) & 3)) * 8) + trsub;
-        const pk_t* a1 = img + t1 * 32 + ((trchunk ^ ((t1 >> 2) & 3)) * 8) + trsub;
-        const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(a0));
-        const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(a1));
-        short8v f;
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        return __builtin_bit_cast(pkx8, f);
-    };
-    pkx8 f0a[2][2], f0b[2][2], f1a[2][2], f1b[2][2];
-    // read order = order of first use by the plane-pair rounds (lh, hl, hh): A.l, B.h, A.h, B.l
-    auto frag_one = [&](int e, const pk_t* s, int ks, pkx8 (&fa)[2][2], pkx8 (&fb)[2][2]) {
-        const int g = e >> 1, i = e & 1;
-        const int pl = (g == 0 || g == 3) ? 1 : 0;
-        if (TR) {
-            if ((g & 1) == 0) fa[pl][i] = rd_tr(s + ((2 * wm + i) * 2 + pl) * 1024, ks);
-            else fb[pl][i] = rd_tr(s + PK_TILE + ((2 * wn + i) * 2 + pl) * 1024, ks);
-        } else {
-            if ((g & 1) == 0) fa[pl][i] = rd(s + pl * PK_IMG, rowa0 + i * 32, ks);
-            else fb[pl][i] = rd(s + (2 + pl) * PK_IMG, rowb0 + i * 32, ks);
-        }
-    };
-    // ---- prologue: tiles 0, 1, 2 -> stages 0, 1, 2 (K index clamped: the in-order vmcnt bookkeeping is then the same on
-    // every path into the loop; sched_barriers keep the issue order)
-    DMA_TILE(0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    DMA_TILE(min(1, nkt - 1), 1);
-    __builtin_amdgcn_sched_barrier(0);
-    DMA_TILE(min(2, nkt - 1), 2);
-    __builtin_amdgcn_s_waitcnt(0x4F70);              // vmcnt(16): tile 0 landed (this wave's pieces)
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) frag_one(e, smem, 0, f0a, f0b);
-
-    auto step = [&](int it, auto tag) {
-        // SMODE 1: tiles t+1..t+3 exist; 4: t+1, t+2 exist (nothing more to request); 2: only t+1; 3: last tile
-        constexpr int SMODE = decltype(tag)::smode;
-        constexpr int CUR = decltype(tag)::cur;              // stage of tile t (0..2)
-        constexpr int NXT = (CUR + 1) % 3;
-        constexpr bool HAS1 = SMODE != 3, HAS3 = SMODE == 1;
-        const pk_t* s_cur = smem + CUR * PK_STAGE;
-        const pk_t* s_nxt = smem + NXT * PK_STAGE;
-#define PK_MMA(FA, FB, q)                                                                                  \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)               \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(FA[pa(q)][i], FB[pb(q)][j], acc[i][j], 0, 0, 0);   \
-    __builtin_amdgcn_sched_barrier(0)
-    // three rounds of 4 MFMAs per phase; the 8 fragment reads / 8 DMA pieces of a phase are dealt 3, 3, 2
-#define PK_R1(r)                                                                                            \
-    frag_one(3 * (r), s_cur, 1, f1a, f1b); frag_one(3 * (r) + 1, s_cur, 1, f1a, f1b);                        \
-    if ((r) < 2) frag_one(3 * (r) + 2, s_cur, 1, f1a, f1b);                                                  \
-    PK_MMA(f0a, f0b, 2 - (r))
-#define PK_R2(r)                                                                                            \
-    if (HAS3) { DMA_ONE(3 * (r), it + 3, CUR); DMA_ONE(3 * (r) + 1, it + 3, CUR); }                          \
-    if (HAS3 && (r) < 2) { DMA_ONE(((r) < 2 ? 3 * (r) + 2 : 0), it + 3, CUR); }                              \
-    if (HAS1) { frag_one(3 * (r), s_nxt, 0, f0a, f0b); frag_one(3 * (r) + 1, s_nxt, 0, f0a, f0b); }          \
-    if (HAS1 && (r) < 2) frag_one(3 * (r) + 2, s_nxt, 0, f0a, f0b);                                          \
-    PK_MMA(f1a, f1b, 2 - (r))
-        PK_R1(0); PK_R1(1); PK_R1(2);
-        // tile t+1 must have landed (requested two K tiles ago); tile t+2's 8 requests may stay in flight.
-        // Raw s_barrier: __syncthreads() adds a fence that drains EVERY LDS-DMA in flight (vmcnt(0)).
-        if (SMODE == 1 || SMODE == 4) __builtin_amdgcn_s_waitcnt(0x0078);     // vmcnt(8) lgkmcnt(0)
-        else __builtin_amdgcn_s_waitcnt(0x0070);                              // vmcnt(0) lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        PK_R2(0); PK_R2(1); PK_R2(2);
-#undef PK_MMA
-#undef PK_R1
-#undef PK_R2
-    };
-    int it = 0;
-    for (; it + 5 < nkt; it += 3) {
-        step(it, StepTag<1, 0>{});
-        step(it + 1, StepTag<1, 1>{});
-        step(it + 2, StepTag<1, 2>{});
-    }
-    for (; it < nkt; it += 3) {      // tail (it % 3 == 0): 1..5 tiles left
-        const int rem = nkt - it;
-        if (rem >= 4) step(it, StepTag<1, 0>{}); else if (rem == 3) step(it, StepTag<4, 0>{}); else if (rem == 2) step(it, StepTag<2, 0>{}); else step(it, StepTag<3, 0>{});
-        if (rem >= 5) step(it + 1, StepTag<1, 1>{}); else if (rem == 4) step(it + 1, StepTag<4, 1>{}); else if (rem == 3) step(it + 1, StepTag<2, 1>{}); else if (rem == 2) step(it + 1, StepTag<3, 1>{});
-        if (rem >= 6) step(it + 2, StepTag<1, 2>{}); else if (rem == 5) step(it + 2, StepTag<4, 2>{}); else if (rem == 4) step(it + 2, StepTag<2, 2>{}); else if (rem == 3) step(it + 2, StepTag<3, 2>{});
-    }
-#undef DMA_ONE
-#undef DMA_TILE
-
-    // ---- epilogue (semantics of gemm_f32.hip)
-    const int flags = p.flags;
-    const bool atomic = gridDim.y > 1 && p.split_stride == 0;      // split_stride != 0: split z owns C + z * split_stride
-    float* const Cz = p.C + (size_t)blockIdx.y * p.split_stride;
-    const float alpha = p.alpha * p.inv_a[0] * p.inv_b[0];
-    if (p.epi_f4 && !atomic) {                 // float4 form (host checked alignment and the operand count)
-        EpiArgs ea = make_epi_args(Cz, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu, flags, 0, alpha, dkn);
-        if (p.epi_f4 == 2) epilogue_f4<2, 2, true>(ea, acc, mb * 128 + wm * 64, nb * 128 + wn * 64, lane);
-        else epilogue_f4<2, 2, false>(ea, acc, mb * 128 + wm * 64, nb * 128 + wn * 64, lane);
-        return;
-    }       // undo the operands' power-of-two scales (exact)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = nb * 128 + wn * 64 + j * 32 + l31;
-        if (col >= p.N) continue;
-        const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rbase = mb * 128 + wm * 64 + i * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row >= p.M) continue;
-                float v = acc[i][j][r] * alpha;
-                float* cp = Cz + (size_t)row * p.ldc + col;
-                if (atomic) {
-                    atomicAdd(cp, v);
-                    continue;
-                }
-                v += bv;
-                if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                if (flags & LSTC_EPI_DROPOUT) {
-                    const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                    v = drop_keep(idx, dkn) ? v * dkn.scale : 0.f;
-                }
-                if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                if (flags & LSTC_EPI_ACCUM) v += *cp;
-                *cp = v;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Two-stage, two-workgroups-per-CU form of the 128x128 kernel (64 KB of LDS and <= 256 registers per workgroup): the
-// prologue (tile requests before the first MFMA) and the epilogue of one workgroup overlap the K loop of the other,
-// which matters for the K = 2048 products (64 K steps per workgroup).
-
 template <bool TR>
 __global__ void __launch_bounds__(NT, 2) gemm_pk2s_kernel(const PkParams p) {
     const DropKey dkn = drop_key_now(p.dk);
@@ -433,7 +226,10 @@ __global__ void __launch_bounds__(NT, 2) gemm_pk2s_kernel(const PkParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // pieces as in gemm_pk_kernel: a stage = [A tile 16 KB][B tile 16 KB]; wave w moves 8 pieces of its operand's tile
+    // a stage is 32 pieces of 1 KB: pieces 0..15 = the A tile, 16..31 = the B tile; wave w moves pieces 8w .. 8w+7
+    // (waves 0,1: A; waves 2,3: B).  gbase is wave-uniform (SGPRs); the lane adds 16 B * lane.
+    //   TR = true: K step kt = tokens 32 kt .. 32 kt + 31 = slice (kt % 4) of token block kt / 4; for each of the wave's
+    //     two 32-feature blocks and two planes one 2-KB slice = 2 pieces (immediate offset 0 / 1024).
     const int opb = wave < 2 ? mb : nb, fb = wave < 2 ? p.fbA : p.fbB;
     const pk_t* gbase = TR ? (wave < 2 ? p.A : p.B) + ((size_t)opb * 4 + (wave & 1) * 2) * PK_TILE
                            : (wave < 2 ? p.A + ((size_t)mb * p.KB + kt0) * PK_TILE : p.B + ((size_t)nb * p.KB + kt0) * PK_TILE) +
@@ -444,7 +240,10 @@ __global__ void __launch_bounds__(NT, 2) gemm_pk2s_kernel(const PkParams p) {
         return (size_t)kt * PK_TILE;
     };
     // piece j (0..7).  NT: contiguous, j = 4 (j / 4) + (j % 4) with the low part as immediate offset.  TR: feature block
-    // j / 4, plane (j % 4) / 2, half j % 2.  SGPR base + 32-bit lane offset (saddr form), inline asm (see gemm_pk_kernel).
+    // j / 4, plane (j % 4) / 2, half j % 2.  SGPR base + 32-bit lane offset (saddr form).  Inline asm: with the builtin the
+    // compiler knows these instructions write LDS, cannot tell the ds_read_b64_tr_b16 fragment reads apart from their
+    // destinations and drains vmcnt(0) before every read (2.7x slower).  All vmcnt waits of this kernel are explicit anyway
+    // (s_waitcnt before the barriers).
     const uint32_t lane_off = (uint32_t)lane * 16u;
 #define S2_DMA(j, kt, stage)                                                                                           \
     do {                                                                                                               \
@@ -785,6 +584,7 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32x3_impl(const LstcGemmDes
     if (!d->A || !d->B || !d->C) return LSTC_E_NULL;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->ldc < d->N) return LSTC_E_SHAPE;
     if (d->batch > 1) return LSTC_E_UNSUPPORTED;
+    if (!(d->variant == 0 || d->variant == 2 || d->variant == 3)) return LSTC_E_UNSUPPORTED;   // 2: 256x128 tiles, 3 = 0: 128x128
     if ((d->flags & LSTC_EPI_BIAS) && !d->bias) return LSTC_E_NULL;
     if ((d->flags & LSTC_EPI_RESIDUAL) && (!d->residual || d->ldr < d->N)) return LSTC_E_NULL;
     if ((d->flags & LSTC_EPI_RELU_MASK) && (!d->relu_src || d->ld_relu < d->N)) return LSTC_E_NULL;
@@ -844,30 +644,18 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32x3_impl(const LstcGemmDes
     const int tilesM = (d->M + 127) / 128;
     p.tilesN = (d->N + 127) / 128;
     // default (variant 0 / 3): the two-stage kernel, two workgroups per CU - 2.44 / 4.30 / 4.93 ms against 2.63 / 4.56 /
-    // 5.39 ms of the three-stage one (variant 1) on the 100352 x {2048 x 2048, 2048 x 4096, 4096 x 2048} forward shapes
-    if (d->variant != 1) {
-        constexpr size_t lds3 = (size_t)2 * PK_STAGE * sizeof(pk_t);
-        static LstcDevOnce attr3;
-        const int dev3 = attr3.begin();
-        if (dev3 >= 0) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk2s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk2s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            attr3.end(dev3);
-        }
-        if (tr) hipLaunchKernelGGL(gemm_pk2s_kernel<true>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds3, st, p);
-        else hipLaunchKernelGGL(gemm_pk2s_kernel<false>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds3, st, p);
-        return lstc_launch_status();
+    // 5.39 ms of a three-stage, one-workgroup-per-CU form on the 100352 x {2048 x 2048, 2048 x 4096, 4096 x 2048} forward
+    // shapes; that form is gone
+    constexpr size_t lds2 = (size_t)2 * PK_STAGE * sizeof(pk_t);
+    static LstcDevOnce attr2;
+    const int dev2 = attr2.begin();
+    if (dev2 >= 0) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk2s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk2s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+        attr2.end(dev2);
     }
-    constexpr size_t lds = (size_t)PK_NSTAGE * PK_STAGE * sizeof(pk_t);
-    static LstcDevOnce attr_done;
-    const int dev_ = attr_done.begin();
-    if (dev_ >= 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done.end(dev_);
-    }
-    if (tr) hipLaunchKernelGGL(gemm_pk_kernel<true>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds, st, p);
-    else hipLaunchKernelGGL(gemm_pk_kernel<false>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds, st, p);
+    if (tr) hipLaunchKernelGGL(gemm_pk2s_kernel<true>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds2, st, p);
+    else hipLaunchKernelGGL(gemm_pk2s_kernel<false>, dim3(tilesM * p.tilesN, eff_splits), dim3(NT), lds2, st, p);
     return lstc_launch_status();
 }
 

@@ -632,10 +632,8 @@ __global__ void __launch_bounds__(NT) cls_concat_fwd_vec4_kernel(const float4* _
         h[0] = (__bf16)w.x; h[1] = (__bf16)w.y; h[2] = (__bf16)w.z; h[3] = (__bf16)w.w;
         *reinterpret_cast<bf16x4v*>(packed + p1_offset(row, 4 * c4, KBp)) = h;
     };
-#ifndef CLS_CONCAT_UNROLL
-#define CLS_CONCAT_UNROLL 8      /* loads in flight per thread: 4 -> 8 took the kernel 319 -> 286 us (f32 only), 480 -> 395 us (with the pack); 16: 303 / 387 */
-#endif
-#pragma unroll CLS_CONCAT_UNROLL
+    // 8 loads in flight per thread: 4 -> 8 took the kernel 319 -> 286 us (f32 only), 480 -> 395 us (with the pack); 16: 303 / 387
+#pragma unroll 8
     for (int t = 0; t < S - 1; ++t) {
         float4 v;
         if constexpr (GATHER) v = x[(ci[t / P] * P + t % P) * (int64_t)d4 + c4];

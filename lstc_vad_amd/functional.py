@@ -73,7 +73,7 @@ def set_compute_dtype(name: str):
     csrc/gemm_pk.hip; small GEMMs stay on the exact-f32 kernel) or "bf16" (operands rounded to bf16 RNE, f32 accumulate and
     f32 storage everywhere: BASELINE.json configs 3 / 5; large products run on packed bf16 tiles - lstc_pack1 +
     csrc/gemm_bf16p.hip - small or batched ones convert while staging, csrc/gemm_bf16c.hip; the attention products Q K^T, P V
-    and their gradients round their operands to bf16 the same way, LstcAttnDesc.dtype = LSTC_BF16, unless LSTC_ATTN_F32=1).
+    and their gradients round their operands to bf16 the same way, LstcAttnDesc.dtype = LSTC_BF16).
     Softmax, LayerNorm, loss and Adagrad stay f32."""
     global _compute_dtype
     if name in ("fp32", "f32", "float32"):
@@ -192,16 +192,10 @@ _pack_prof = None          # list of (bytes_in, start_event, end_event) while be
 _wepoch = 0
 _memo_stack = []           # activation packs made inside one autograd-node body are shared by the GEMMs of that body
 _x3_min = (256, 256, 1 << 30)   # min(M, N), K, M*N*K from which a product goes to the packed kernel
-_BF16P_MIN_MNK = int(os.environ.get("LSTC_BF16P_MIN_MNK", str(1 << 28)))      # the M*N*K bound of the packed bf16 kernel (A/B: 1073741824 = rounds 2 - 5)
-_CLS_PACK = os.environ.get("LSTC_CLS_PACK", "1") != "0"             # A/B hook: 0 = the CLS-only layer reads f32 rows (round 5's first form)
-_ATTN_F32 = os.environ.get("LSTC_ATTN_F32", "0") == "1"          # bf16 mode: keep the attention products on the exact-f32 MFMA
+_BF16P_MIN_MNK = 1 << 28          # the M*N*K bound of the packed bf16 kernel
 _ATTN_VARIANT = int(os.environ.get("LSTC_ATTN_VARIANT", "0"))     # 1: first-generation attention kernels (A/B measurements)
 _BWD_NPW = int(os.environ.get("LSTC_ATTN_BWD_NPW", "0"))       # measurement hook: sequences per workgroup of the attention backward
 _ATTN_PACKED_IN = os.environ.get("LSTC_ATTN_PACKED_IN", "1") != "0"   # bf16 mode: Q | K | V / dO reach the attention core as packs
-_WGRAD_COST_MODEL = os.environ.get("LSTC_WGRAD_COST_MODEL", "0") == "1"     # opt-in (measured, round 6: profiles/r06_wgrad_split_ab.txt): the cost-model split of the
-# packed bf16 weight gradients gains 3 % on the UCF / STN rank shapes (4352 - 4864 tokens) and nothing elsewhere; it stays off by default - fewer partial
-# buffers move the peak-memory comparison of tests/test_act16_gpu.py (both activation dtypes lose the same transient, the f32-activation run more)
-_DETERMINISTIC_WGRAD = os.environ.get("LSTC_ATOMIC_SPLITK", "0") != "1"   # split-K weight gradients: partials + ordered sum, not atomics
 
 
 def set_x3_threshold(min_mn=256, min_k=256, min_mnk=1 << 30):
@@ -533,7 +527,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, trans_a=False, trans_b=False, out:
             raise RuntimeError(f"gemm(out_pack=True): [{M}, {N}] x K={K} does not qualify (bf16 packed product on whole 256-tiles)")
         pbuf = torch.empty((int(_lib.load().lstc_pack1_bytes(M, N)),), device=dev, dtype=torch.uint8)
     if out is None and not out_pack:
-        if split_k > 1 and packed and _DETERMINISTIC_WGRAD:
+        if split_k > 1 and packed:
             # K splits of the packed kernel into separate partials, summed in a fixed order afterwards (no atomics).  The
             # library launches lstc_gemm_splits() slices, possibly fewer than asked for: size and sum exactly that many
             split_k = int(_lib.load().lstc_gemm_splits(dtype, K, split_k))
@@ -662,28 +656,6 @@ def _wgrad_split(m_out: int, n_out: int, tile: int = 128) -> int:
     return best
 
 
-def _wgrad_split_bf16p(m_out: int, n_out: int, tokens: int) -> int:
-    """Split-K factor of a weight gradient on the packed bf16 kernel (256 x 256 tiles, one workgroup per CU) from a cost model instead
-    of round filling alone: rounds(s) x (K steps per item x 1.84 us + ~8 us of item prologue / partial-tile epilogue) + the ordered sum
-    of the s partials ((s + 1) x 4 m n bytes at ~4 TB/s; none for s = 1).  At the headline token counts it picks what `_wgrad_split`
-    picks (the K loops dominate: 4 / 2 / 4 / 8 for dW_qkv, dW_1 / dW_2, dW_fc and UBnormal's dW_qkv); with a few thousand tokens - one
-    rank of an 8-GPU split of the STN / UCF configs - the fixed costs and the partial sums decide: the STN rank's [3072, 2048] x 4352
-    tokens ran 8 splits of 8.5 K steps each at 576 TFLOP/s (profiles/r06_rank_gemm_launch_table_bf16.txt era), two splits model 1.5x faster."""
-    tiles = -(-m_out // 256) * -(-n_out // 256)
-    steps = -(-tokens // 64)
-    best, best_t = 1, None
-    for s in (1, 2, 4, 8, 16):
-        if s > 1 and steps // s < 8:
-            break
-        rounds = -(-(tiles * s) // 256)
-        t = rounds * (-(-steps // s) * 1.84 + 8.0)
-        if s > 1:
-            t += (s + 1) * 4.0 * m_out * n_out / 4.0e6
-        if best_t is None or t < best_t - 1e-9:
-            best, best_t = s, t
-    return best
-
-
 # ---- gradient sinks (data parallel).  dist.GradAllReducer keeps every gradient of a bucket in ONE flat buffer that RCCL reduces in
 # place.  Letting autograd ACCUMULATE into views of that buffer costs a 407-MB fill per step plus a read-add-write of every weight
 # gradient after the kernel that produced it.  Instead the reducer hangs a sink on each large weight -
@@ -743,10 +715,7 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, x_pack: Optional[Packed] = None, ou
         raise RuntimeError(f"wgrad: out must be a contiguous float32 [{O}, {I}] tensor")
     pkind = _packed_kind()
     # split-K factor: 256x256 output tiles on the packed bf16 kernel, 128x128 everywhere else
-    if pkind == _lib.BF16P and _WGRAD_COST_MODEL:
-        s = _wgrad_split_bf16p(O, I, T) if T >= 4096 else 1       # (below 4096 tokens: one launch, no partial buffers - as rounds 2 - 5)
-    else:
-        s = _wgrad_split(O, I, 256 if pkind == _lib.BF16P else 128) if T >= 4096 else 1
+    s = _wgrad_split(O, I, 256 if pkind == _lib.BF16P else 128) if T >= 4096 else 1
     tr_ok = T % 128 == 0 and (pkind == _lib.BF16P or (O % 128 == 0 and I % 128 == 0))
     # a gradient that already IS a packed operand (layernorm_bwd_branch emits df packed whenever [rows, d_model] fills the tile
     # grid, whatever the width of its partner) always takes the packed TR form; the partner is packed on demand (the TR kernel
@@ -761,25 +730,23 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, x_pack: Optional[Packed] = None, ou
         # library may launch fewer slices than asked for (132 K tiles / 16 -> 15 slices): allocate and sum exactly those,
         # an extra row would add uninitialised memory into the gradient
         s = int(_lib.load().lstc_gemm_splits(pkind, T, s))
-        det = s > 1 and _DETERMINISTIC_WGRAD
         if s == 1 and out is not None:
             part = out.view(1, O * I)
         else:
-            part = torch.empty((s, O * I), device=dev, dtype=torch.float32) if (det or s == 1) else \
-                torch.zeros((1, O * I), device=dev, dtype=torch.float32)
+            part = torch.empty((s, O * I), device=dev, dtype=torch.float32)
         d = GemmDesc()
         d.M, d.N, d.K, d.lda, d.ldb, d.ldc = O, I, T, O, I, I
         d.transA, d.transB, d.dtype, d.flags, d.alpha, d.split_k = 1, 0, pkind, 0, 1.0, s
-        d.batch_stride_c = O * I if (s > 1 and _DETERMINISTIC_WGRAD) else 0
+        d.batch_stride_c = O * I if s > 1 else 0
         d.A, d.B, d.C = dev_ptr(ap.buf), dev_ptr(bp.buf), dev_ptr(part)
         _launch_gemm(d, 2.0 * O * I * T)
-        return (colsum(part, out=None if out is None else out.view(O * I)) if det else part).view(O, I)
+        return (colsum(part, out=None if out is None else out.view(O * I)) if s > 1 else part).view(O, I)
     if isinstance(dy, Packed):
         raise RuntimeError(f"wgrad: packed gradient [{T}, {O}] x [{T}, {I}] does not qualify for the packed kernel")
     x3_big = pkind is not None and min(O, I) >= _x3_min[0] and T >= _x3_min[1] and T * O * I >= _x3_min[2]
     if pkind == _lib.BF16P and not x3_big:
         s = _wgrad_split(O, I, 128) if T >= 4096 else 1       # not a packed product after all: 128x128-tile kernel
-    if s > 1 and (_compute_dtype == F32 or (_compute_dtype == _lib.F32X3 and not x3_big)) and _DETERMINISTIC_WGRAD and \
+    if s > 1 and (_compute_dtype == F32 or (_compute_dtype == _lib.F32X3 and not x3_big)) and \
             T % s == 0 and dy.stride(1) == 1 and x.stride(1) == 1:
         # exact-f32 kernel (also the small products of f32x3 mode): the s K-chunks are ONE batched launch into [s, O, I] partials, summed in a fixed order by
         # lstc_colsum - same parallelism as the atomic split-K, but the step is bit-reproducible run to run
@@ -977,7 +944,7 @@ def layernorm_bwd_act(dz, y: Packed, gamma, mean, rstd, p: float, seed: int, wan
 
 def _attn_dtype():
     """LstcAttnDesc.dtype of the current compute mode: bf16 mode contracts bf16-rounded operands on the bf16 MFMA."""
-    return _lib.BF16 if (_compute_dtype == _lib.BF16 and not _ATTN_F32) else F32
+    return _lib.BF16 if _compute_dtype == _lib.BF16 else F32
 
 
 def attn_fwd_pack(N, S, H, dv) -> bool:
@@ -998,7 +965,7 @@ def _qkv_pack_desc(d, qkv: "Packed", H, dk, dv):
 
 def attn_packed_inputs(N, S, H, dk, dv) -> bool:
     """bf16 mode: the attention core can read Q | K | V (and dO) as packed bf16 operands (include/lstc_hip.h, in_pack_cols)."""
-    return (attn_fwd_pack(N, S, H, dv) and attn_bwd_packs(N, S, H, dk, dv) and _ATTN_PACKED_IN and not _ATTN_F32 and S <= 96 and
+    return (attn_fwd_pack(N, S, H, dv) and attn_bwd_packs(N, S, H, dk, dv) and _ATTN_PACKED_IN and S <= 96 and
             dk % 64 == 0 and dv % 64 == 0 and N * S * H * (2 * dk + dv) * 2 < 2 ** 31)
 
 
@@ -1550,7 +1517,7 @@ def unpack1_rows(pk: "Packed", row0: int = 0, step: int = 1, n: Optional[int] = 
 
 def cls_pack_ok(N: int, S: int, H: int, dm: int) -> bool:
     """Can the CLS-only layer read its [N, S, dm] input as a pack (include/lstc_hip.h, lstc_cls_dot_pack)?"""
-    return _ACT16 and _CLS_PACK and H <= 8 and S <= 128 and act_rows_ok(N * S, dm)
+    return _ACT16 and H <= 8 and S <= 128 and act_rows_ok(N * S, dm)
 
 
 def cls_dot_pack(u, xp: "Packed", N, S, mode, probs=None, p_drop=0.0, seed=0):

@@ -67,9 +67,8 @@ def test_production_library_refuses_tuning_variants(lib):
     d.M = d.N = d.K = 128
     d.lda = d.ldb = d.ldc = 128
     d.transB = 1
-    # f32: the production library holds 0 = 4 (default), 8 (its fallback), 11 (64x64 tail tile), 12 (persistent); the other tile variants
-    # (1-3, 5-7, 9, 10) live in `make tuning` builds only since round 6
-    for dtype, bad in ((0, (1, 2, 3, 5, 6, 7, 9, 10, 13, 14, 15, 16, 4 + 16, 1 << 20, -1)), (3, (1, 16, 32, (1 << 30) | 1))):      # LSTC_BF16P: 0 or LSTC_VARIANT_NO_QTAIL (1 << 30) alone
+    # f32: the library holds 0 = 4 (default), 8 (its fallback), 11 (64x64 tail tile), 12 (persistent); f32x3: 0 = 3 and 2
+    for dtype, bad in ((0, (1, 2, 3, 5, 6, 7, 9, 10, 13, 14, 15, 16, 4 + 16, 1 << 20, -1)), (2, (1, 4, 16)), (3, (1, 16, 32, (1 << 30) | 1))):      # LSTC_BF16P: 0 or LSTC_VARIANT_NO_QTAIL (1 << 30) alone
         d.dtype = dtype
         for v in bad:
             d.variant = v

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of liblstc_hip.so + gemm_check into build/<name>/ with extra -D flags on ONE source file:
-#   tools/build_variant.sh nt gemm_bf16p '-DP1_STORE_MOD=" nt"'
+#   tools/build_variant.sh tuned gemm_bf16p -DLSTC_TUNING
 set -e
 cd "$(dirname "$0")/.."
 name=$1; src=$2; shift 2

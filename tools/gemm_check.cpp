@@ -61,9 +61,9 @@ static int check(const Case& c) {
         CK(hipMalloc(&pA, trc ? packb(K, M) : packb(M, K))); CK(hipMalloc(&pB, trc ? packb(K, N) : packb(N, K)));
         CK(hipMemset(pA, 0xff, trc ? packb(K, M) : packb(M, K))); CK(hipMemset(pB, 0xff, trc ? packb(K, N) : packb(N, K)));   // NaN-fill: padding must be written by the pack
         int r1, r2;
-        if (c.variant >= 7 && c.variant <= 9) {            // weight-gradient form (7: three-stage kernel, 8: 256x128-tile kernel, 9: two-stage kernel): packs of the SOURCES [K, M], [K, N] + transposed reads
+        if (c.variant >= 7 && c.variant <= 9) {            // weight-gradient form (8: 256x128-tile kernel, 7 / 9: the default kernel): packs of the SOURCES [K, M], [K, N] + transposed reads
             r1 = packf(dA, K, M, lda, 0, pA); r2 = packf(dB, K, N, ldb, 0, pB);
-            d.transA = 1; d.transB = 0; d.variant = p1 ? 0 : c.variant == 8 ? 2 : c.variant == 9 ? 3 : 1;   /* 7 -> three-stage kernel */
+            d.transA = 1; d.transB = 0; d.variant = p1 ? 0 : c.variant == 8 ? 2 : 3;
         } else {
             r1 = packf(dA, M, K, lda, c.tA ? 1 : 0, pA); r2 = packf(dB, N, K, ldb, c.tB ? 0 : 1, pB);
             d.transA = 0; d.transB = 1; if (p1) d.variant = 0;
@@ -112,7 +112,7 @@ static int check(const Case& c) {
 }
 
 static void timeit(int M, int N, int K, int tA, int tB, int variant, int split, int flags, int iters, int pad_a = 0, int pad_b = 0, int dtype = 0) {
-    const int v15 = variant & 15;          // the tile / form selector; the bits above it select tuning ablations (LSTC_TUNING builds)
+    const int v15 = variant & 15;          // the tile / form selector; the bits above it select the bf16p tuning instruments (LSTC_TUNING builds)
     const int lda = (tA ? M : K) + pad_a, ldb = (tB ? K : N) + pad_b;
     const size_t na = (size_t)(tA ? K : M) * lda, nb = (size_t)(tB ? N : K) * ldb, nc = (size_t)M * N;
     float *dA, *dB, *dC, *dbias;
@@ -150,7 +150,7 @@ static void timeit(int M, int N, int K, int tA, int tB, int variant, int split, 
                             (p1 ? 6.0 : 12.0) * M * K / (msa * 1e-3) / 1e12, N, K, tB ? "" : " k-major", msb);
         }
         d.A = pA; d.B = pB;
-        if (v15 >= 7 && v15 <= 9) { d.transA = 1; d.transB = 0; d.variant = p1 ? (variant & ~15) : v15 == 8 ? 2 : v15 == 9 ? 3 : 1; } else { d.transA = 0; d.transB = 1; if (p1) d.variant = variant & ~15; }
+        if (v15 >= 7 && v15 <= 9) { d.transA = 1; d.transB = 0; d.variant = p1 ? (variant & ~15) : v15 == 8 ? 2 : 3; } else { d.transA = 0; d.transB = 1; if (p1) d.variant = variant & ~15; }
     }
     void *pC = nullptr, *pR = nullptr;
     if (p1 && (flags & LSTC_EPI_OUT_PACK)) {                // timing of the packed-output / packed-residual epilogues (bf16 activation stream)
@@ -250,13 +250,9 @@ int main(int argc, char** argv) {
     int fails = 0;
     if (!time_only) {
         const int ALL = LSTC_EPI_BIAS | LSTC_EPI_RELU | LSTC_EPI_RESIDUAL | LSTC_EPI_RELU_MASK | LSTC_EPI_ACCUM;
-        // production library: 0 (default; padded lds -> the PIPE 3 scalar-load fallback), 8 (PIPE 3 itself), 4 (PIPE 5, aligned), 12 (persistent;
-        // padded lds -> its fallback); `make tuning` builds also hold 2 / 6 (256x128 tiles) and 10 (LDS-DMA staging)
-#ifdef LSTC_TUNING
-        for (int variant : {0, 8, 4, 12, 2, 6, 10}) {
-#else
+        // 0 (default; padded lds -> the PIPE 3 scalar-load fallback), 8 (PIPE 3 itself), 4 (PIPE 5, aligned), 12 (persistent;
+        // padded lds -> its fallback)
         for (int variant : {0, 8, 4, 12}) {
-#endif
             fails += check({300, 200, 100, 0, 1, 0, variant, 1});
             fails += check({257, 131, 67, 0, 1, ALL, variant, 1});
             fails += check({300, 200, 100, 0, 0, LSTC_EPI_RELU_MASK, variant, 1});
@@ -264,20 +260,10 @@ int main(int argc, char** argv) {
             fails += check({130, 260, 515, 1, 0, 0, variant, 3});
             fails += check({64, 1, 32, 0, 1, LSTC_EPI_BIAS, variant, 1});
         }
-#ifdef LSTC_TUNING
-        // aligned (vector-path) tuning variants: variant id odd -> no ld padding in check()
-        for (int variant : {1, 3, 5, 7, 9}) {
-            fails += check({256, 256, 128, 0, 1, 0, variant, 1});
-            fails += check({256, 256, 128, 0, 0, 0, variant, 1});
-            fails += check({256, 256, 128, 1, 0, 0, variant, 1});
-            fails += check({384, 132, 260, 1, 0, 0, variant, 2});
-        }
-#endif
         // the persistent walk on aligned operands (alignc: 16-B epilogue path - what variant 12 needs to run its own kernel)
         fails += check({1024, 512, 256, 0, 1, LSTC_EPI_BIAS | LSTC_EPI_RELU, 12, 1, 0, 1});
         fails += check({1024, 512, 256, 0, 0, LSTC_EPI_RESIDUAL, 12, 1, 0, 1});
-        // LDS-DMA variant (10): aligned leading dims (odd variant id would pad; 10 is even -> use sizes whose padded lds
-        // stay multiples of 4 is impossible, so these go through variant 11 = same kernel, no padding)
+        // the 64x64 tail tile (variant 11: odd id -> no ld padding in check(), aligned leading dims)
         for (int tb : {1, 0}) {
             fails += check({256, 256, 128, 0, tb, 0, 11, 1});
             fails += check({300, 200, 96, 0, tb, ALL, 11, 1});
@@ -305,15 +291,15 @@ int main(int argc, char** argv) {
         }
         for (int split : {1, 3}) {             // packed f32x3 kernel: every layout goes through lstc_pack3
             fails += check({300, 200, 100, 0, 1, 0, 0, 1, LSTC_F32X3});
-            fails += check({257, 131, 67, 0, 1, ALLB, 1, 1, LSTC_F32X3});
+            fails += check({257, 131, 67, 0, 1, ALLB, 3, 1, LSTC_F32X3});
             fails += check({300, 200, 132, 0, 0, LSTC_EPI_RELU_MASK, 0, 1, LSTC_F32X3});
-            fails += check({130, 260, 515, 1, 0, 0, 1, split, LSTC_F32X3});
+            fails += check({130, 260, 515, 1, 0, 0, 3, split, LSTC_F32X3});
             fails += check({64, 1, 32, 0, 1, LSTC_EPI_BIAS, 0, 1, LSTC_F32X3});
-            fails += check({256, 384, 32 * (3 + split), 0, 1, 0, 1, 1, LSTC_F32X3});
-            fails += check({128, 128, 64, 0, 1, 0, 1, 1, LSTC_F32X3});
-            fails += check({500, 260, 1000, 1, 0, 0, 1, split + 1, LSTC_F32X3});
-            fails += check({256, 128, 384, 1, 0, 0, 7, split, LSTC_F32X3});
-            fails += check({128, 384, 1152, 1, 0, 0, 7, split + 1, LSTC_F32X3});
+            fails += check({256, 384, 32 * (3 + split), 0, 1, 0, 3, 1, LSTC_F32X3});
+            fails += check({128, 128, 64, 0, 1, 0, 3, 1, LSTC_F32X3});
+            fails += check({500, 260, 1000, 1, 0, 0, 3, split + 1, LSTC_F32X3});
+            fails += check({256, 128, 384, 1, 0, 0, 9, split, LSTC_F32X3});
+            fails += check({128, 384, 1152, 1, 0, 0, 9, split + 1, LSTC_F32X3});
             fails += check({256, 384, 640, 1, 0, 0, 9, split, LSTC_F32X3});                  // 2-stage kernel, TR
             fails += check({512, 256, 640, 1, 0, 0, 8, split, LSTC_F32X3});                  // 256x128-tile kernel, TR
             fails += check({300, 520, 100 + 32 * split, 0, 1, ALLB, 2, 1, LSTC_F32X3});     // 256x128-tile kernel, ragged NT
@@ -353,11 +339,7 @@ int main(int argc, char** argv) {
     // LTN headline shapes: tokens M = 2048*49 = 100352, d = 2048, Hd = 2048, F = 4096.  A smaller M (25088)
     // is timed first to keep the table quick; TFLOP/s is what matters.
     const int Mtok = 100352;
-#ifdef LSTC_TUNING
-    for (int variant : {0, 1, 2, 5}) {
-#else
     for (int variant : {0, 12}) {
-#endif
         timeit(Mtok, 2048, 2048, 0, 1, variant, 1, 0, 6);
         timeit(Mtok, 4096, 2048, 0, 1, variant, 1, LSTC_EPI_BIAS | LSTC_EPI_RELU, 5);
         timeit(Mtok, 2048, 4096, 0, 1, variant, 1, LSTC_EPI_BIAS | LSTC_EPI_DROPOUT | LSTC_EPI_RESIDUAL, 5);

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 machine code of the attention kernels of two builds, symbol by symbol.
+"""Compare the gfx950 machine code of the kernels of two builds, symbol by symbol.
 
-    python tools/attn_isa_diff.py OLD_TREE NEW_TREE [> profiles/attn_template_isa_diff.txt]
+    python tools/isa_diff.py OLD_TREE NEW_TREE [OBJECT ...] [> profiles/attn_template_isa_diff.txt]
 
-Each tree must have been built with `make` (the per-file objects lstc_vad_amd/csrc/attention*.o are read: one offload bundle
+OBJECT names files of lstc_vad_amd/csrc without their suffix (gemm_f32, rowops, ...); the default is the attention files.
+Each tree must have been built with `make` (the per-file objects lstc_vad_amd/csrc/OBJECT.o are read: one offload bundle
 each).  Every kernel of OLD is looked up in NEW by its demangled name (key(): the two spellings of a masked instantiation count
 as one) and its disassembly compared as text after the addresses are stripped (instruction words and operands stay).  Exit
 status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
@@ -88,7 +89,7 @@ def main():
     old, new = sys.argv[1], sys.argv[2]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
-        for name in FILES:
+        for name in sys.argv[3:] or FILES:
             a, b = keyed(kernels(old, name, tmp)), keyed(kernels(new, name, tmp))
             print(f"== csrc/{name}.hip: {len(a)} kernels before, {len(b)} after")
             for k in sorted(a):
@@ -100,7 +101,7 @@ def main():
                     print(f"identical {k}  ({len(a[k])} instructions)")
             for k in sorted(set(b) - set(a)):
                 print(f"NEW       {k}  ({len(b[k])} instructions)"); bad += 1
-    print(f"== {bad} attention kernel(s) missing, changed or without a counterpart in the old tree")
+    print(f"== {bad} kernel(s) missing, changed or without a counterpart in the old tree")
     return 1 if bad else 0
 
 
