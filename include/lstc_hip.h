@@ -330,6 +330,10 @@ typedef struct LstcSdpaDesc {
 } LstcSdpaDesc;
 int lstc_sdpa_fwd(const LstcSdpaDesc* d, const LstcAttnMask* mask_or_null, void* stream);
 int lstc_sdpa_bwd(const LstcSdpaDesc* d, const LstcAttnMask* mask_or_null, void* stream);
+/* Sq <= lstc_sdpa_few_query_max() (the compile-time constant SDPA_FEWQ_MAX of csrc/attention_x.hip, 1 .. 16; 0 = compiled out)
+ * runs the few-query kernels behind the two calls above: one workgroup per (sequence, head), the [Sq][Sk] block in LDS, K and V
+ * read once each.  Same contract, limits, return codes and bit-reproducibility; longer Sq runs the 32-row-tile kernels. */
+int lstc_sdpa_few_query_max(void);
 
 /* Re-associated CLS attention of the last layer: with one query per (sequence, head) the key / value projections are
  * never materialised — score[n,h,j] = u[n,h].x[n,j] with u = (q_h*scale) Wk_h, and o[n,h] = Wv_h (sum_j p[n,h,j] x[n,j]) —

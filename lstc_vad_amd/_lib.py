@@ -21,7 +21,7 @@ EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 
 EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
-    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_cls_dot", "lstc_cls_wsum",
+    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
@@ -174,6 +174,7 @@ def load():
         "lstc_pack1_bytes": [i64, i64],
         "lstc_gemm_splits": [i32, i32, i32],
         "lstc_version": [],
+        "lstc_sdpa_few_query_max": [],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -22,6 +22,9 @@
 // waves; (Q) query blocks over the waves.  Static wave -> block assignment, one writer per output element, every sum in a fixed
 // order, no atomics: two runs are bitwise equal.
 // Every product is the exact-f32 MFMA; softmax and dropout are f32.  Static LDS only (forward 16.5 KB, backward 18.5 KB).
+//
+// Sq <= SDPA_FEWQ_MAX (<= 16) runs the few-query kernels at the end of this file instead: one workgroup per (sequence, head), the
+// [Sq][Sk] block in LDS, K and V read once each, explicit fmaf chains (exact f32 as well).
 #include "attention_common.h"
 
 namespace lstc_attn {
@@ -49,6 +52,7 @@ struct SdpaParams {
     DropKey dkey;
     int has_drop;
     int vec_qk, vec_v;                 // float4 operand loads allowed for the d_k / d_v contractions
+    int vec_dk, vec_dv;                // few-query backward: float4 stores of dK / dV rows allowed
 };
 
 __device__ __forceinline__ floatx16 xmma8(const float* a, const float* b, floatx16 acc) {
@@ -439,6 +443,8 @@ int sdpa_fill(const LstcSdpaDesc* d, const LstcAttnMask* m, bool bwd, SdpaParams
     // float4 loads: Q and K rows in the forward (over d_k), dO and V rows in the backward's dP' (over d_v)
     p.vec_qk = aligned16(d->Q) && aligned16(d->K) && stride4(p.q) && stride4(p.k);
     p.vec_v = aligned16(d->V) && (!bwd || aligned16(d->dO)) && stride4(p.v) && stride4(p.o);
+    p.vec_dk = bwd && aligned16(d->dK) && stride4(p.k);
+    p.vec_dv = bwd && aligned16(d->dV) && stride4(p.v);
     if (m) { mk.m = m->mask; mk.sn = m->sn; mk.sh = m->sh; mk.sq = m->sq; mk.sk = m->sk; }
     return 0;
 }
@@ -470,6 +476,311 @@ struct BwdLaunch {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ few-query kernels
+// 1 <= Sq <= SDPA_FEWQ_MAX (<= 16): a 32-row query tile would be mostly padding, so these run one workgroup of four waves per
+// (sequence, head) with the whole [Sq][Sk] block of logits (forward) or of Pd / dP' / dA (backward) in LDS as f32, and read K
+// and V from HBM once each.  QB = Sq rounded up to a power of two is the number of query rows held in registers, DB = 256 or 512
+// the row pitch of the small LDS operand (Q scale in the forward, dO in the backward).  Three building blocks:
+//   f_rowdot  X[i][j] = A_lds[i] . B[j]     keys over groups of four lanes (each lane every fourth float4 of the row), queries
+//                                           in registers; the four partial sums are added by two lane exchanges
+//   f_xt_rows out[j] = sum_i X[i][j] g[i]   keys over the waves, float4 columns over the lanes (g in registers): dV, dK
+//   f_x_rows  out[i] = sum_j X[i][j] B[j]   keys j = wave (mod 4), float4 columns over the lanes; the four waves' partial rows
+//                                           are added in wave order through LDS: O, dQ
+// Every product is an explicit fmaf in a fixed order that depends on neither alignment nor on whether float4 accesses were
+// taken; one writer per element, no atomics.  Static LDS: (max(QB DB, 1024 max(QB / 4, 1)) + 512 QB) * 4 bytes - the first term is the
+// staged operand or the four waves' partial rows, whichever is larger: 6 KB at QB = 1, 8 KB at QB = 2, 48 KB at QB = 16, DB = 256,
+// 64 KB at QB = 16, DB = 512.
+#ifndef SDPA_FEWQ_MAX
+#define SDPA_FEWQ_MAX 16               // largest Sq the few-query kernels take; 0 compiles the dispatch out
+#endif
+static_assert(SDPA_FEWQ_MAX >= 0 && SDPA_FEWQ_MAX <= 16, "the few-query kernels hold at most 16 query rows");
+#if SDPA_FEWQ_MAX > 0
+
+constexpr int FCOLS = 256;             // output columns per pass of f_xt_rows / f_x_rows: one float4 per lane
+
+__device__ __forceinline__ float4 f_ld4(const float* __restrict__ p, bool vec) {
+    if (vec) return *reinterpret_cast<const float4*>(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+__device__ __forceinline__ void f_st4(float* __restrict__ p, const float4 v, bool vec) {
+    if (vec) { *reinterpret_cast<float4*>(p) = v; return; }
+    p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+}
+__device__ __forceinline__ void f_fma4(float4& acc, float s, const float4 v) {
+    acc.x = fmaf(s, v.x, acc.x); acc.y = fmaf(s, v.y, acc.y); acc.z = fmaf(s, v.z, acc.z); acc.w = fmaf(s, v.w, acc.w);
+}
+
+template <int QB, int DB>
+constexpr int f_ar_floats() {
+    constexpr int rb = QB >= 4 ? QB / 4 : 1;
+    return QB * DB > XNW * rb * FCOLS ? QB * DB : XNW * rb * FCOLS;
+}
+
+// ar[i][c] = src[i][c] * s for i < nrows, c < kdim; zero rows up to QB
+template <int QB, int DB>
+__device__ __forceinline__ void f_stage(float* ar, const float* __restrict__ src, int64_t ld, int nrows, int kdim, float s) {
+    for (int idx = threadIdx.x; idx < QB * DB; idx += XNT) {
+        const int i = idx / DB, c = idx % DB;
+        ar[idx] = (i < nrows && c < kdim) ? src[(int64_t)i * ld + c] * s : 0.f;
+    }
+}
+
+template <int QB, int DB>
+__device__ __forceinline__ void f_rowdot(const float* ar, const float* __restrict__ B, int64_t ldb, int nb, int kdim, bool vec,
+                                         float (*X)[XMAXS]) {
+    const int slice = threadIdx.x & 3;
+#pragma unroll 1
+    for (int j0 = 0; j0 < nb; j0 += XNT / 4) {
+        const int j = j0 + (int)(threadIdx.x >> 2);
+        const float* pb = B + (int64_t)min(j, nb - 1) * ldb;
+        float acc[QB];
+#pragma unroll
+        for (int i = 0; i < QB; ++i) acc[i] = 0.f;
+#pragma unroll 4
+        for (int c = 4 * slice; c < kdim; c += 16) {
+            const float4 b = f_ld4(pb + c, vec);
+#pragma unroll
+            for (int i = 0; i < QB; ++i) {
+                const float4 a = *reinterpret_cast<const float4*>(ar + i * DB + c);
+                acc[i] = fmaf(a.x, b.x, acc[i]); acc[i] = fmaf(a.y, b.y, acc[i]);
+                acc[i] = fmaf(a.z, b.z, acc[i]); acc[i] = fmaf(a.w, b.w, acc[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < QB; ++i) {
+            float v = acc[i];
+            v += __shfl_xor(v, 1, 64);
+            v += __shfl_xor(v, 2, 64);
+            if (slice == 0 && j < nb) X[i][j] = v;
+        }
+    }
+}
+
+// G(i, col, active) -> the float4 of row i at columns col .. col + 3 (zero for i >= Sq or an inactive lane)
+template <int QB, typename G>
+__device__ __forceinline__ void f_xt_rows(const float (*X)[XMAXS], G g_of, float* __restrict__ Out, int64_t ldo, int nk, int ncols,
+                                          float s, bool vec) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+    for (int c0 = 0; c0 < ncols; c0 += FCOLS) {
+        const int col = c0 + 4 * lane;
+        const bool active = col < ncols;                  // widths are multiples of 16: col < ncols covers col + 3
+        float4 g[QB];
+#pragma unroll
+        for (int i = 0; i < QB; ++i) g[i] = g_of(i, col, active);
+#pragma unroll 2
+        for (int j = wave; j < nk; j += XNW) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int i = 0; i < QB; ++i) f_fma4(acc, X[i][j], g[i]);
+            acc.x *= s; acc.y *= s; acc.z *= s; acc.w *= s;
+            if (active) f_st4(Out + (int64_t)j * ldo + col, acc, vec);
+        }
+    }
+}
+
+template <int QB>
+__device__ __forceinline__ void f_x_rows(const float (*X)[XMAXS], float* ar, const float* __restrict__ B, int64_t ldb, int nk,
+                                         int ncols, bool vec, float* __restrict__ Out, int64_t ldo, int nrows, float s) {
+    constexpr int RB = QB >= 4 ? QB / 4 : 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+    for (int c0 = 0; c0 < ncols; c0 += FCOLS) {
+        const int col = c0 + 4 * lane;
+        const bool active = col < ncols;
+        float4 acc[QB];
+#pragma unroll
+        for (int i = 0; i < QB; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+        for (int j = wave; j < nk; j += XNW) {
+            const float4 b = active ? f_ld4(B + (int64_t)j * ldb + col, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int i = 0; i < QB; ++i) f_fma4(acc[i], X[i][j], b);
+        }
+#pragma unroll
+        for (int pass = 0; pass < QB / RB; ++pass) {
+            __syncthreads();                              // ar is free: its last readers are behind a barrier
+#pragma unroll
+            for (int r = 0; r < RB; ++r) *reinterpret_cast<float4*>(ar + (wave * RB + r) * FCOLS + 4 * lane) = acc[pass * RB + r];
+            __syncthreads();
+            for (int idx = threadIdx.x; idx < RB * FCOLS; idx += XNT) {
+                const int r = idx / FCOLS, c = idx % FCOLS, i = pass * RB + r;
+                const float v = ((ar[r * FCOLS + c] + ar[(RB + r) * FCOLS + c]) + ar[(2 * RB + r) * FCOLS + c]) + ar[(3 * RB + r) * FCOLS + c];
+                if (i < nrows && c0 + c < ncols) Out[(int64_t)i * ldo + c0 + c] = v * s;
+            }
+        }
+    }
+}
+
+template <int QB, int DB, bool MASKED>
+__global__ void __launch_bounds__(XNT) sdpa_fewq_fwd_kernel(const SdpaParams p, const MaskArg<MASKED> mk) {
+    const DropKey dkn = drop_key_now(p.dkey);
+    __shared__ __attribute__((aligned(16))) float ar[f_ar_floats<QB, DB>()];   // Q scale, then the waves' partial O rows
+    __shared__ float X[QB][XMAXS];                                             // logits, then Pd
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Sq = p.Sq, Sk = p.Sk;
+    const int h = (int)(blockIdx.x % (uint32_t)p.H), n = (int)(blockIdx.x / (uint32_t)p.H);
+    const float* Kb = p.K + n * p.k.sn + h * p.k.sh;
+    const float* Vb = p.V + n * p.v.sn + h * p.v.sh;
+    float* pr_base = p.probs + ((size_t)n * p.H + h) * (size_t)Sq * Sk;
+    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)Sq * (uint32_t)Sk;
+    const uint8_t* mk_nh = nullptr;
+    if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
+
+    f_stage<QB, DB>(ar, p.Q + n * p.q.sn + h * p.q.sh, p.q.st, Sq, p.dk, p.scale);
+    __syncthreads();
+    f_rowdot<QB, DB>(ar, Kb, p.k.st, Sk, p.dk, p.vec_qk, X);
+    __syncthreads();
+
+    // softmax of row i by wave i mod 4: lane partial sums over j = lane + 64 t in t order, then the butterfly.  A fully masked
+    // row has every logit ATTN_MASK_FILL and comes out uniform; a masked key of a row that keeps a key adds exp(-1e9 - m) = 0.
+#pragma unroll 1
+    for (int i = wave; i < QB; i += XNW) {
+        if (i >= Sq) {                                    // padding rows take no part in O
+            for (int j = lane; j < Sk; j += 64) X[i][j] = 0.f;
+            continue;
+        }
+        float x[XMAXS / 64];
+        float m = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < XMAXS / 64; ++t) {
+            const int j = lane + 64 * t;
+            float v = -INFINITY;
+            if (j < Sk) {
+                v = X[i][j];
+                if constexpr (MASKED) v = mk_nh[(int64_t)i * mk.sq + (int64_t)j * mk.sk] ? v : ATTN_MASK_FILL;
+            }
+            x[t] = v;
+            m = fmaxf(m, v);
+        }
+        m = wave_max(m);
+        float l = 0.f;
+#pragma unroll
+        for (int t = 0; t < XMAXS / 64; ++t) {
+            x[t] = lane + 64 * t < Sk ? expf(x[t] - m) : 0.f;
+            l += x[t];
+        }
+        l = wave_sum(l);
+#pragma unroll
+        for (int t = 0; t < XMAXS / 64; ++t) {
+            const int j = lane + 64 * t;
+            if (j < Sk) {
+                const float pv = x[t] / l;
+                pr_base[(size_t)i * Sk + j] = pv;
+                float pd = pv;
+                if (p.has_drop) pd = drop_keep(flat0 + (uint32_t)i * (uint32_t)Sk + (uint32_t)j, dkn) ? pv * dkn.scale : 0.f;
+                X[i][j] = pd;
+            }
+        }
+    }
+    __syncthreads();
+    f_x_rows<QB>(X, ar, Vb, p.v.st, Sk, p.dv, p.vec_v, p.O + n * p.o.sn + h * p.o.sh, p.o.st, Sq, 1.f);
+}
+
+template <int QB, int DB, bool MASKED>
+__global__ void __launch_bounds__(XNT) sdpa_fewq_bwd_kernel(const SdpaParams p, const MaskArg<MASKED> mk) {
+    const DropKey dkn = drop_key_now(p.dkey);
+    __shared__ __attribute__((aligned(16))) float ar[f_ar_floats<QB, DB>()];   // dO, then the waves' partial dQ rows
+    __shared__ float X[QB][XMAXS];                                             // Pd, then dP', then dA
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Sq = p.Sq, Sk = p.Sk;
+    const int h = (int)(blockIdx.x % (uint32_t)p.H), n = (int)(blockIdx.x / (uint32_t)p.H);
+    const float* Qb = p.Q + n * p.q.sn + h * p.q.sh;
+    const float* Kb = p.K + n * p.k.sn + h * p.k.sh;
+    const float* Vb = p.V + n * p.v.sn + h * p.v.sh;
+    const float* Pb = p.probs + ((size_t)n * p.H + h) * (size_t)Sq * Sk;
+    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)Sq * (uint32_t)Sk;
+    const uint8_t* mk_nh = nullptr;
+    if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
+    auto keep_scale = [&](int i, int j) -> float {
+        if (!p.has_drop) return 1.f;
+        return drop_keep(flat0 + (uint32_t)i * (uint32_t)Sk + (uint32_t)j, dkn) ? dkn.scale : 0.f;
+    };
+
+    // X = Pd (zero rows past Sq); dO into LDS
+    f_stage<QB, DB>(ar, p.dO + n * p.o.sn + h * p.o.sh, p.o.st, Sq, p.dv, 1.f);
+#pragma unroll 1
+    for (int i = wave; i < QB; i += XNW)
+        for (int j = lane; j < Sk; j += 64) X[i][j] = i < Sq ? Pb[(size_t)i * Sk + j] * keep_scale(i, j) : 0.f;
+    __syncthreads();
+    // dV = Pd^T dO
+    f_xt_rows<QB>(X, [&](int i, int col, bool active) {
+        return active ? *reinterpret_cast<const float4*>(ar + i * DB + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }, p.dV + n * p.v.sn + h * p.v.sh, p.v.st, Sk, p.dv, 1.f, p.vec_dv);
+    __syncthreads();
+    // X = dP' = dO V^T
+    f_rowdot<QB, DB>(ar, Vb, p.v.st, Sk, p.dv, p.vec_v, X);
+    __syncthreads();
+    // X = dA = P (dP' keep - rowsum(dP' keep P)), zero at masked positions and in the padding rows
+#pragma unroll 1
+    for (int i = wave; i < QB; i += XNW) {
+        if (i >= Sq) {
+            for (int j = lane; j < Sk; j += 64) X[i][j] = 0.f;
+            continue;
+        }
+        float pv[XMAXS / 64], dpk[XMAXS / 64];
+        float part = 0.f;
+#pragma unroll
+        for (int t = 0; t < XMAXS / 64; ++t) {
+            const int j = lane + 64 * t;
+            pv[t] = dpk[t] = 0.f;
+            if (j < Sk) {
+                pv[t] = Pb[(size_t)i * Sk + j];
+                dpk[t] = X[i][j] * keep_scale(i, j);
+            }
+            part += dpk[t] * pv[t];
+        }
+        const float rs = wave_sum(part);
+#pragma unroll
+        for (int t = 0; t < XMAXS / 64; ++t) {
+            const int j = lane + 64 * t;
+            if (j < Sk) {
+                float da = pv[t] * (dpk[t] - rs);
+                if constexpr (MASKED) da = mk_nh[(int64_t)i * mk.sq + (int64_t)j * mk.sk] ? da : 0.f;
+                X[i][j] = da;
+            }
+        }
+    }
+    __syncthreads();
+    // dK = dA^T Q scale
+    f_xt_rows<QB>(X, [&](int i, int col, bool active) {
+        return (active && i < Sq) ? f_ld4(Qb + (int64_t)i * p.q.st + col, p.vec_qk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }, p.dK + n * p.k.sn + h * p.k.sh, p.k.st, Sk, p.dk, p.scale, p.vec_dk);
+    // dQ = dA K scale
+    f_x_rows<QB>(X, ar, Kb, p.k.st, Sk, p.dk, p.vec_qk, p.dQ + n * p.q.sn + h * p.q.sh, p.q.st, Sq, p.scale);
+}
+
+template <bool BWD, int QB, int DB, bool M>
+void fewq_launch(const SdpaParams& p, const MaskArg<M>& mk, hipStream_t st) {
+    const dim3 grid((unsigned)(p.N * p.H));
+    if constexpr (BWD) hipLaunchKernelGGL((sdpa_fewq_bwd_kernel<QB, DB, M>), grid, XNT, 0, st, p, mk);
+    else hipLaunchKernelGGL((sdpa_fewq_fwd_kernel<QB, DB, M>), grid, XNT, 0, st, p, mk);
+}
+template <bool BWD, int QB, bool M>
+void fewq_width(const SdpaParams& p, const MaskArg<M>& mk, hipStream_t st) {
+    if ((BWD ? p.dv : p.dk) <= 256) fewq_launch<BWD, QB, 256, M>(p, mk, st);
+    else fewq_launch<BWD, QB, 512, M>(p, mk, st);
+}
+template <bool BWD, bool M>
+void fewq_rows(const SdpaParams& p, const MaskArg<M>& mk, hipStream_t st) {
+    if (p.Sq <= 1) fewq_width<BWD, 1, M>(p, mk, st);
+    else if (p.Sq <= 2) fewq_width<BWD, 2, M>(p, mk, st);
+    else if (p.Sq <= 4) fewq_width<BWD, 4, M>(p, mk, st);
+    else if (p.Sq <= 8) fewq_width<BWD, 8, M>(p, mk, st);
+    else fewq_width<BWD, 16, M>(p, mk, st);
+}
+// true: Sq <= SDPA_FEWQ_MAX and the few-query kernel was launched
+template <bool BWD>
+bool fewq_run(const SdpaParams& p, const MaskParams* mk, hipStream_t st) {
+    if (p.Sq > SDPA_FEWQ_MAX) return false;
+    if (mk) fewq_rows<BWD, true>(p, *mk, st); else fewq_rows<BWD, false>(p, NoMask{}, st);
+    return true;
+}
+#else       // compiled out: neither the kernels nor their dispatch exist in this build
+template <bool BWD>
+bool fewq_run(const SdpaParams&, const MaskParams*, hipStream_t) { return false; }
+#endif
+
 }  // namespace
 }  // namespace lstc_attn
 
@@ -481,6 +792,7 @@ int lstc_sdpa_fwd(const LstcSdpaDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
     const int rc = sdpa_fill(d, m, false, p, mk);
     if (rc) return rc;
+    if (fewq_run<false>(p, m ? &mk : nullptr, (hipStream_t)stream)) return lstc_launch_status();
     const uint64_t waves = (uint64_t)p.N * p.H * ((p.Sq + 31) / 32);
     sdpa_dispatch<FwdLaunch>(sdpa_dt(p.dk, p.dv), p, m ? &mk : nullptr, dim3((unsigned)((waves + XNW - 1) / XNW)), (hipStream_t)stream);
     return lstc_launch_status();
@@ -492,8 +804,11 @@ int lstc_sdpa_bwd(const LstcSdpaDesc* d, const LstcAttnMask* m, void* stream) {
     MaskParams mk;
     const int rc = sdpa_fill(d, m, true, p, mk);
     if (rc) return rc;
+    if (fewq_run<true>(p, m ? &mk : nullptr, (hipStream_t)stream)) return lstc_launch_status();
     sdpa_dispatch<BwdLaunch>(sdpa_dt(p.dk, p.dv), p, m ? &mk : nullptr, dim3((unsigned)(p.N * p.H)), (hipStream_t)stream);
     return lstc_launch_status();
 }
+
+int lstc_sdpa_few_query_max(void) { return SDPA_FEWQ_MAX; }
 
 }  // extern "C"

@@ -1164,13 +1164,17 @@ def _sdpa_desc(q, k, v, o, probs, scale, p_drop, seed):
     return d
 
 
-def sdpa_fwd(q, k, v, scale, p_drop=0.0, seed=0, mask=None):
+def sdpa_fwd(q, k, v, scale, p_drop=0.0, seed=0, mask=None, out=None):
     """Rectangular attention forward (lstc_sdpa_fwd): q [b, H, len_q, d_k], k [b, H, len_k, d_k], v [b, H, len_k, d_v] through their
     own strides (head-major tensors and ``transpose(1, 2)`` views of token-major projections alike; ``.contiguous()`` only where
     the feature stride is not 1).  ``mask``: a normalised mask (``attn_mask_arg(..., Sk=len_k)``) or None.  Returns
-    (O [b, H, len_q, d_v], P [b, H, len_q, len_k] before dropout), both contiguous."""
+    (O [b, H, len_q, d_v], P [b, H, len_q, len_k] before dropout), both contiguous.  ``out``: a float32 [b, H, len_q, d_v]
+    destination for O with feature stride 1 (e.g. the ``transpose(1, 2)`` view of a token-major buffer), returned as it is."""
     q, k, v = _sdpa_operand(q), _sdpa_operand(k), _sdpa_operand(v)
-    o = torch.empty((q.shape[0], q.shape[1], q.shape[2], v.shape[3]), device=q.device, dtype=torch.float32)
+    oshape = (q.shape[0], q.shape[1], q.shape[2], v.shape[3])
+    if out is not None and (tuple(out.shape) != oshape or out.dtype != torch.float32 or out.stride(3) != 1):
+        raise RuntimeError(f"sdpa_fwd: out must be a float32 {list(oshape)} tensor with feature stride 1")
+    o = out if out is not None else torch.empty(oshape, device=q.device, dtype=torch.float32)
     probs = torch.empty((q.shape[0], q.shape[1], q.shape[2], k.shape[2]), device=q.device, dtype=torch.float32)
     d = _sdpa_desc(q, k, v, o, probs, scale, p_drop, seed)
     d.O = dev_ptr(o)
@@ -1454,6 +1458,126 @@ class MHAFunction(torch.autograd.Function):
                 gemm(dv_, wv, out=dx, accumulate=True)
                 dx = dx.view(N, S, -1)
         return dx, dwq, dwk, dwv, dwfc, dln_w, dln_b, dtable, None, None
+
+
+def _fused_kv_weight(wk, wv):
+    """[rows_k + rows_v, d] view over the key and value projection weights when they are consecutive slices of one buffer
+    (MultiHeadAttention.fuse_qkv_), else None; kept on ``wk`` and refreshed like ``_fused_qkv_weight``'s view."""
+    try:
+        same = wk.untyped_storage().data_ptr() == wv.untyped_storage().data_ptr()
+    except Exception:
+        return None
+    if not (same and wk.is_contiguous() and wv.is_contiguous() and wk.shape[1] == wv.shape[1]):
+        return None
+    if wv.storage_offset() != wk.storage_offset() + wk.numel():
+        return None
+    rows = wk.shape[0] + wv.shape[0]
+    hit = wk.__dict__.get("_lstc_fused_kv_view")
+    if hit is not None and hit.data_ptr() == wk.data_ptr() and hit.shape == (rows, wk.shape[1]) and hit.device == wk.device:
+        return hit
+    view = torch.as_strided(wk.detach(), (rows, wk.shape[1]), (wk.shape[1], 1), wk.storage_offset())
+    view._lstc_weight_view = True
+    view.__dict__["_lstc_view_of"] = wk
+    wk.__dict__["_lstc_fused_kv_view"] = view
+    _weight_views.add(view)
+    return view
+
+
+class MHACrossFunction(torch.autograd.Function):
+    """models/MultiHeadAttention.py:93-132 with three inputs (cross-attention) as one autograd node: xq [N, Sq, d], xk and xv
+    [N, Sk, d], f32 rows only.
+
+    forward:  Q = xq Wq^T, K = xk Wk^T, V = xv Wv^T (K | V as one product when xk is xv and the two weights are adjacent) ->
+              attention core -> dropout(O Wfc^T) + xq -> [LayerNorm].  Sq == Sk runs the square kernels (lstc_attn_*: relative
+              bias, mask), Sq != Sk the rectangular ones (lstc_sdpa_*: mask, no bias; few-query kernels for short Sq) on the
+              transpose(1, 2) views of the token-major projections, O written token-major through the same kind of view.
+    backward: the unfused branch of MHAFunction.backward with one contraction per input; the three weight gradients go to
+              their own sinks (they contract over different inputs).  Returns (out [N, Sq, d], P before dropout)."""
+
+    @staticmethod
+    def forward(ctx, xq, xk, xv, wq, wk, wv, wfc, ln_w, ln_b, table, index, cfg):
+        N, Sq, dm = xq.shape
+        Sk = xk.shape[1]
+        H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
+        training = cfg["training"]
+        p_attn = cfg["attn_dropout"] if training else 0.0
+        p_fc = cfg["fc_dropout"] if training else 0.0
+        mask = cfg.get("mask")
+        xq2 = xq.contiguous().view(N * Sq, dm)
+        same_kv = xk is xv
+        xk2 = xk.contiguous().view(N * Sk, dm)
+        xv2 = xk2 if same_kv else xv.contiguous().view(N * Sk, dm)
+        xqp, xkp = maybe_pack(xq2), maybe_pack(xk2)
+        xvp = xkp if same_kv else maybe_pack(xv2)
+        q = gemm(xqp if xqp is not None else xq2, wq, trans_b=True)
+        wkv = _fused_kv_weight(wk, wv) if same_kv else None
+        if wkv is not None:          # one product over the shared input: X is read once
+            kv = gemm(xkp if xkp is not None else xk2, wkv, trans_b=True)
+            k, v = kv[:, : H * dk], kv[:, H * dk:]
+        else:
+            k = gemm(xkp if xkp is not None else xk2, wk, trans_b=True)
+            v = gemm(xvp if xvp is not None else xv2, wv, trans_b=True)
+        seed_a = next_seed() if p_attn > 0 else 0
+        seed_f = next_seed() if p_fc > 0 else 0
+        if p_attn > 0:
+            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, Sq, Sk))
+        if p_fc > 0:
+            _note(cfg["site"] + "dropout", p_fc, seed_f, (N, Sq, dm))
+        square = Sq == Sk
+        if square:
+            o, probs = attn_fwd(q, k, v, N, Sq, H, dk, dv, table, index, p_attn, seed_a, mask=mask)
+        else:
+            if table is not None:
+                raise RuntimeError("MHACrossFunction: the relative bias needs len_q == len_k")
+            o = torch.empty((N * Sq, H * dv), device=xq.device, dtype=torch.float32)
+            _, probs = sdpa_fwd(q.view(N, Sq, H, dk).transpose(1, 2), k.view(N, Sk, H, dk).transpose(1, 2),
+                                v.view(N, Sk, H, dv).transpose(1, 2), 1.0 / (dk ** 0.5), p_attn, seed_a, mask,
+                                out=o.view(N, Sq, H, dv).transpose(1, 2))
+        op = maybe_pack(o)
+        y = gemm(op if op is not None else o, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xq2)
+        if cfg["layer_norm"]:
+            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6, pack=True)
+        else:
+            z, mean, rstd = y, None, None
+        ctx.packs = (xqp, xkp, xvp, op) if training else (None, None, None, None)
+        ctx.cfg = dict(cfg, N=N, Sq=Sq, Sk=Sk, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, square=square, same_kv=same_kv)
+        ctx.save_for_backward(xq2, xk2, None if same_kv else xv2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs,
+                              y if cfg["layer_norm"] else None, mean, rstd)
+        ctx.mark_non_differentiable(probs)
+        return z.view(N, Sq, dm), probs
+
+    @staticmethod
+    def backward(ctx, dz, _dprobs):
+        xq2, xk2, xv2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs, y, mean, rstd = ctx.saved_tensors
+        c = ctx.cfg
+        N, Sq, Sk, H, dk, dv = c["N"], c["Sq"], c["Sk"], c["n_head"], c["d_k"], c["d_v"]
+        if c["same_kv"]:
+            xv2 = xk2
+        mask = c.get("mask")
+        dz2 = dz.contiguous().view(N * Sq, -1)
+        dy, df, dln_w, dln_b, _ = layernorm_bwd_branch(dz2, y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"], False)
+        xqp, xkp, xvp, op = ctx.packs
+        dwfc = deliver(wfc, wgrad(df, o, op, out=grad_sink(wfc)))
+        do = gemm(df, wfc)                                   # [N*Sq, H*dv]
+        if c["square"]:
+            # dQ, dK, dV with the row strides of Q, K, V (K and V may be the two column blocks of one product)
+            outs = tuple(torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=torch.float32) for t in (q, k, v))
+            dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, Sq, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
+                                            out=outs, mask=mask)
+        else:
+            dq4, dk4, dv4 = sdpa_bwd(do.view(N, Sq, H, dv).transpose(1, 2), q.view(N, Sq, H, dk).transpose(1, 2),
+                                     k.view(N, Sk, H, dk).transpose(1, 2), v.view(N, Sk, H, dv).transpose(1, 2), probs,
+                                     1.0 / (dk ** 0.5), c["p_attn"], c["seed_a"], mask)
+            # back to token-major rows: views, with the row pitch of the projection they belong to
+            dq, dk_, dv_ = (g.transpose(1, 2).reshape(g.shape[0] * g.shape[2], H * g.shape[3]) for g in (dq4, dk4, dv4))
+            dtable = None
+        dwq = deliver(wq, wgrad(dq, xq2, xqp, out=grad_sink(wq)))
+        dwk = deliver(wk, wgrad(dk_, xk2, xkp, out=grad_sink(wk)))
+        dwv = deliver(wv, wgrad(dv_, xv2, xvp, out=grad_sink(wv)))
+        dxq = gemm(dq, wq, residual=dy).view(N, Sq, -1) if ctx.needs_input_grad[0] else None
+        dxk = gemm(dk_, wk).view(N, Sk, -1) if ctx.needs_input_grad[1] else None
+        dxv = gemm(dv_, wv).view(N, Sk, -1) if ctx.needs_input_grad[2] else None
+        return dxq, dxk, dxv, dwq, dwk, dwv, dwfc, dln_w, dln_b, dtable, None, None
 
 
 def gemm_batched(a, b, c, M, N, K, lda, ldb, ldc, trans_a, trans_b, batch, sa, sb, sc, alpha=1.0, a_off=0, b_off=0, c_off=0):

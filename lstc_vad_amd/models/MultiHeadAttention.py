@@ -8,7 +8,7 @@ arithmetic runs in ``MHAFunction`` (GEMM -> fused attention core -> GEMM epilogu
 import torch
 from torch import nn
 
-from ..functional import (MHAClsAssocFunction, MHAClsFunction, MHAFunction, PackedAct, SDPAFunction, attn_mask_arg, dropout_apply,
+from ..functional import (MHAClsAssocFunction, MHAClsFunction, MHACrossFunction, MHAFunction, PackedAct, SDPAFunction, attn_mask_arg, dropout_apply,
                           next_seed)
 
 
@@ -147,8 +147,8 @@ class MultiHeadAttention(nn.Module):
         """``mask``: anything torch broadcasts against [N, H, S, S], any dtype, zero = masked (reference :105-106: the logit of a
         masked position is -1e9 before the relative bias and the softmax; a fully masked row comes out uniform)."""
         if not (q is k and k is v):
-            raise NotImplementedError("only self-attention (q is k is v): the attention kernels have one sequence length, and the "
-                                      "reference's relative-bias slice needs len_q == len_k anyway")
+            raise NotImplementedError("only self-attention (q is k is v) here: three different inputs, with lengths of their own, "
+                                      "go through forward_cross")
         has_bias = self.relative_pe or self.relative_pe_2D
         if self.relative_pe_2D and q.shape[1] - 1 != self.window_size ** 2:
             raise RuntimeError("relative_pe_2D needs window_size**2 patch tokens (models/MultiHeadAttention.py:114)")
@@ -178,6 +178,58 @@ class MultiHeadAttention(nn.Module):
             from ..functional import gemm
             vv = gemm(q.contiguous().view(N * S, -1), self.w_vs.weight, trans_b=True)
             return out, probs, vv.view(N, S, self.n_head, self.d_v).transpose(1, 2)
+        if not return_attn:
+            return out, None
+        return out, probs
+
+    def forward_cross(self, q, k, v, mask=None, return_attn=False, return_attn_v=False):
+        """Cross-attention, the reference's ``forward`` for three different inputs (:93-132): q [N, len_q, d_model], k and v
+        [N, len_k, d_model]; the residual is the query input.  Returns ``forward``'s tuple: ``(out [N, len_q, d_model], attn)`` with
+        ``attn`` [N, H, len_q, len_k] the probabilities before dropout (None unless asked for), and with ``return_attn_v`` a third
+        value [N, H, len_k, d_v], the projection of the key-side input ``v``.
+        ``mask``: anything torch broadcasts against [N, H, len_q, len_k], any dtype, zero = masked.
+        len_q == len_k runs the square kernels (relative bias and mask as in ``forward``), len_q != len_k the rectangular ones
+        (the few-query kernels for short len_q); passing one tensor as k and v projects it once when the weights are fused.
+        ``relative_pe`` / ``relative_pe_2D`` need len_q == len_k: the reference adds its bias slice [:len_q-1, :len_q-1] to
+        ``attn[:, :, 1:, 1:]``, which does not broadcast otherwise.  Its one accident, len_q == 2 (a 1 x 1 bias spread over every
+        key), is refused like every other unequal pair.  Every refusal is raised before any launch."""
+        if any(isinstance(t, PackedAct) for t in (q, k, v)):
+            raise NotImplementedError("forward_cross takes f32 activations (no PackedAct inputs)")
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+            raise ValueError(f"expected [N, len, d_model] tensors, got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+        if not (q.shape[0] == k.shape[0] == v.shape[0]):
+            raise ValueError(f"batch sizes differ: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+        if not (q.shape[2] == k.shape[2] == v.shape[2] == self.d_model):
+            raise ValueError(f"d_model is {self.d_model}: got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+        if k.shape[1] != v.shape[1]:
+            raise ValueError(f"len_k ({k.shape[1]}) and len_v ({v.shape[1]}) differ")
+        N, len_q, len_k = q.shape[0], q.shape[1], k.shape[1]
+        has_bias = self.relative_pe or self.relative_pe_2D
+        if has_bias and len_q != len_k:
+            raise ValueError(f"the relative position bias needs len_q == len_k (got {len_q} and {len_k}): the reference's bias slice "
+                             "does not broadcast over a rectangular attention")
+        if self.relative_pe_2D and len_q - 1 != self.window_size ** 2:
+            raise RuntimeError("relative_pe_2D needs window_size**2 patch tokens (models/MultiHeadAttention.py:114)")
+        if has_bias and len_q - 1 > self.relative_position_index.shape[0]:
+            raise ValueError(f"len_q - 1 = {len_q - 1} patch tokens exceed the relative position index "
+                             f"({self.relative_position_index.shape[0]} tokens)")
+        cfg = dict(n_head=self.n_head, d_k=self.d_k, d_v=self.d_v, layer_norm=self.layerNorm_flag,
+                   attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
+                   site=self._site)
+        if mask is not None:
+            cfg.update(mask=attn_mask_arg(mask, N, self.n_head, len_q, device=q.device, Sk=len_k))
+        if not (q.is_cuda and k.is_cuda and v.is_cuda):
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        out, probs = MHACrossFunction.apply(
+            q, k, v, self.w_qs.weight, self.w_ks.weight, self.w_vs.weight, self.fc.weight,
+            self.layer_norm.weight if self.layerNorm_flag else None,
+            self.layer_norm.bias if self.layerNorm_flag else None,
+            self.relative_position_bias_table if has_bias else None,
+            self.relative_position_index if has_bias else None, cfg)
+        if return_attn_v:
+            from ..functional import gemm
+            vv = gemm(v.contiguous().view(N * len_k, -1), self.w_vs.weight, trans_b=True)
+            return out, probs, vv.view(N, len_k, self.n_head, self.d_v).transpose(1, 2)
         if not return_attn:
             return out, None
         return out, probs
