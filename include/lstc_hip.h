@@ -57,8 +57,12 @@ enum { LSTC_F32 = 0, LSTC_BF16 = 1, LSTC_F32X3 = 2, LSTC_BF16P = 3 };
  *         dropout(fc(o)) + residual  models/MultiHeadAttention.py:123-124
  * Dropout keeps element i = m*N+n iff hash(seed, i) >= p*2^32 and scales kept values by
  * 1/(1-p); lstc_dropout_mask() / lstc_dropout_apply() regenerate the same mask.
- * dtype LSTC_F32: exact f32 MFMA (v_mfma_f32_32x32x2_f32) — bitwise a k-ordered fmaf chain.
- * dtype LSTC_BF16: A/B bf16, f32 accumulate; C bf16 unless LSTC_EPI_OUT_F32.
+ * dtype LSTC_F32: exact f32 MFMA (v_mfma_f32_32x32x2_f32) — bitwise an fmaf chain (acc = fmaf(a_k, b_k, acc) from 0, one rounding per
+ *   term), NOT in ascending k: inside every 32-deep K tile the order is 0, 16, 1, 17, ... 7, 23, 8, 24, ... 15, 31 (the two lane
+ *   halves of an issue hold k = j and k = 16 + j, the lower half is added first).  Every variant, tile size and the row split share
+ *   that order, so they agree bit for bit (tests/test_gemm_f64_gpu.py compares each with that chain).
+ * dtype LSTC_BF16: A, B, C stay f32 in memory; the operands are rounded to bf16 (RNE) while they are staged, f32 accumulate, C and
+ *   the epilogue f32 (csrc/gemm_bf16c.hip).  There is no bf16 output: LSTC_EPI_OUT_F32 is accepted and changes nothing.
  * dtype LSTC_F32X3: f32-accurate product on the 16-bit matrix cores (3 f16 plane products per f32 product); A and B are PACKED operands produced by lstc_pack3
  *   (lda/ldb ignored).  (transA, transB) = (0, 1): packs of the [M,K] and [N,K] matrices (lstc_pack3 transposes k-major
  *   sources on the way).  (1, 0): packs of the k-major SOURCES [K,M] and [K,N] themselves - the weight-gradient product

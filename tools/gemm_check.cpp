@@ -21,7 +21,7 @@ static std::vector<float> rnd(size_t n, unsigned seed) {
     return v;
 }
 
-struct Case { int M, N, K, tA, tB, flags, variant, split, dtype = 0, alignc = 0; };   // alignc: C / residual / mask leading dims multiples of 4 (16-B epilogue path)
+struct Case { int M, N, K, tA, tB, flags, variant, split, dtype = 0, alignc = 0; float p = 0.f; int batch = 0; };   // alignc: C / residual / mask leading dims multiples of 4 (16-B epilogue path); p: dropout_p (with LSTC_EPI_DROPOUT); batch: problems (0 = one)
 
 static float bf16_round(float x) {   // RNE to bfloat16, back to float (host model of the kernel's operand rounding)
     uint32_t u; memcpy(&u, &x, 4);
@@ -29,15 +29,39 @@ static float bf16_round(float x) {   // RNE to bfloat16, back to float (host mod
     float y; memcpy(&y, &u, 4); return y;
 }
 
+// f16 planes of lstc_pack3 on the host: s = the power of two that puts absmax in [2^14, 2^15), h = f16(x s), l = f16(x s - h)
+static float pack3_scale(const std::vector<float>& v, size_t rows, size_t cols, size_t ld) {
+    float m = 0.f;
+    for (size_t r = 0; r < rows; ++r) for (size_t c = 0; c < cols; ++c) m = std::fmax(m, std::fabs(v[r * ld + c]));
+    if (m == 0.f) return 1.f;
+    return std::ldexp(1.f, 14 - std::ilogb(m));
+}
+static void split2(float x, float s, float& h, float& l) {
+    const float xs = x * s;
+    h = (float)(_Float16)xs;
+    l = (float)(_Float16)(xs - h);
+}
+
+// The bound of a case is the one rule of tests/util_rowops.py (tol), formed on the host from the reference side alone:
+//   8 * max(e32, e_fmt, 4 * 2^-24 * B)
+// e32 = the error of a plain float32 evaluation (k-ordered float loop + the epilogue in float) against the double reference on the same
+// operands, B = the largest sum of |terms| added into one output element, e_fmt (f32x3 only) = the error of the f16-plane format itself
+// (the three plane products hh + hl + lh in double).  The bf16 dtypes are referenced on the bf16-rounded operands: the kernels
+// accumulate in f32, so the same rule holds with no bf16 allowance.
 static int check(const Case& c) {
     const int M = c.M, N = c.N, K = c.K;
+    const int batch = c.batch > 1 ? c.batch : 1;
+    const float alpha = 0.75f;
+    const uint64_t seed = 20250;
     const bool pad = (c.variant % 2 == 0) && c.variant != 4 && !(c.dtype == 0 && c.variant == 12 && c.alignc);     // padded lds exercise the scalar-load path
     const int lda = (c.tA ? M : K) + (pad ? 3 : 0);
     const int ldb = (c.tB ? K : N) + (pad ? 1 : 0);
     const int ldc = c.alignc ? N + 4 : N + 2, ldr = c.alignc ? N + 8 : N + 1, ldm = N;
-    const size_t na = (size_t)(c.tA ? K : M) * lda, nb = (size_t)(c.tB ? N : K) * ldb;
+    const size_t na1 = (size_t)(c.tA ? K : M) * lda, nb1 = (size_t)(c.tB ? N : K) * ldb, nc1 = (size_t)M * ldc;
+    const size_t sa = na1 + 8, sb = nb1 + 4, sc = nc1 + 12;              // batch strides: not the dense ones
+    const size_t na = batch > 1 ? sa * batch : na1, nb = batch > 1 ? sb * batch : nb1, nc = batch > 1 ? sc * batch : nc1;
     auto hA = rnd(na, 1), hB = rnd(nb, 2), hbias = rnd(N, 3), hres = rnd((size_t)M * ldr, 4), hmask = rnd((size_t)M * ldm, 5);
-    std::vector<float> hC((size_t)M * ldc, 0.5f);
+    std::vector<float> hC(nc, 0.5f);
     float *dA, *dB, *dC, *dbias, *dres, *dmask;
     CK(hipMalloc(&dA, na * 4)); CK(hipMalloc(&dB, nb * 4)); CK(hipMalloc(&dC, hC.size() * 4));
     CK(hipMalloc(&dbias, N * 4)); CK(hipMalloc(&dres, hres.size() * 4)); CK(hipMalloc(&dmask, hmask.size() * 4));
@@ -49,8 +73,9 @@ static int check(const Case& c) {
     CK(hipMemcpy(dC, hC.data(), hC.size() * 4, hipMemcpyHostToDevice));
     LstcGemmDesc d; memset(&d, 0, sizeof(d));
     d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.ldc = ldc; d.transA = c.tA; d.transB = c.tB;
-    d.dtype = c.dtype; d.flags = c.flags; d.alpha = 0.75f; d.dropout_p = 0.f; d.ldr = ldr; d.ld_relu = ldm;
+    d.dtype = c.dtype; d.flags = c.flags; d.alpha = alpha; d.dropout_p = c.p; d.dropout_seed = seed; d.ldr = ldr; d.ld_relu = ldm;
     d.split_k = c.split; d.variant = c.variant; d.A = dA; d.B = dB; d.C = dC; d.bias = dbias; d.residual = dres; d.relu_src = dmask;
+    if (batch > 1) { d.batch = batch; d.batch_stride_a = (int64_t)sa; d.batch_stride_b = (int64_t)sb; d.batch_stride_c = (int64_t)sc; }
     void *pA = nullptr, *pB = nullptr;
     const bool p1 = c.dtype == LSTC_BF16P;
     auto packf = [&](const float* s_, int64_t r_, int64_t k_, int64_t ld_, int km_, void* d_) {
@@ -76,36 +101,89 @@ static int check(const Case& c) {
     CK(hipDeviceSynchronize());
     std::vector<float> out(hC.size());
     CK(hipMemcpy(out.data(), dC, out.size() * 4, hipMemcpyDeviceToHost));
-    double maxerr = 0;
-    for (int m = 0; m < M; ++m)
-        for (int n = 0; n < N; ++n) {
-            double s = 0;
-            for (int k = 0; k < K; ++k) {
-                float af = c.tA ? hA[(size_t)k * lda + m] : hA[(size_t)m * lda + k];
-                float bf = c.tB ? hB[(size_t)n * ldb + k] : hB[(size_t)k * ldb + n];
-                if (c.dtype == LSTC_BF16 || c.dtype == LSTC_BF16P) { af = bf16_round(af); bf = bf16_round(bf); }
-                s += (double)af * (double)bf;
-            }
-            double v = s * 0.75;
-            if (c.split <= 1) {
-                if (c.flags & LSTC_EPI_BIAS) v += hbias[n];
-                if (c.flags & LSTC_EPI_RELU) v = v > 0 ? v : 0;
-                if (c.flags & LSTC_EPI_RESIDUAL) v += hres[(size_t)m * ldr + n];
-                if (c.flags & LSTC_EPI_RELU_MASK) v = hmask[(size_t)m * ldm + n] > 0 ? v : 0;
-                if (c.flags & LSTC_EPI_ACCUM) v += 0.5;
-            }
-            maxerr = std::fmax(maxerr, std::fabs(v - out[(size_t)m * ldc + n]));
+    // the dropout mask of the launch: element i = m * N + n, regenerated by the library's own entry
+    std::vector<uint8_t> keep;
+    const bool drop = (c.flags & LSTC_EPI_DROPOUT) != 0;
+    if (drop) {
+        uint8_t* dk; CK(hipMalloc(&dk, (size_t)M * N));
+        int rk = lstc_dropout_mask(dk, (int64_t)M * N, c.p, seed, nullptr);
+        if (rk) { printf("lstc_dropout_mask rc=%d\n", rk); return 1; }
+        keep.resize((size_t)M * N);
+        CK(hipMemcpy(keep.data(), dk, keep.size(), hipMemcpyDeviceToHost));
+        hipFree(dk);
+    }
+    const bool b16 = c.dtype == LSTC_BF16 || c.dtype == LSTC_BF16P, x3 = c.dtype == LSTC_F32X3;
+    const double dscale = 1.0 / (1.0 - (double)c.p);
+    const float fscale = 1.f / (1.f - c.p);
+    double maxerr = 0, e32 = 0, efmt = 0, Bmax = 0;
+    size_t kept = 0;
+    for (int z = 0; z < batch; ++z) {
+        const float* A_ = hA.data() + (batch > 1 ? sa * z : 0);
+        const float* B_ = hB.data() + (batch > 1 ? sb * z : 0);
+        const float* O_ = out.data() + (batch > 1 ? sc * z : 0);
+        // logical operands as the kernel sees them, K contiguous both: a[m][k], b[n][k]
+        std::vector<float> a((size_t)M * K), b((size_t)N * K);
+        for (int m = 0; m < M; ++m) for (int k = 0; k < K; ++k) { float v = c.tA ? A_[(size_t)k * lda + m] : A_[(size_t)m * lda + k]; a[(size_t)m * K + k] = b16 ? bf16_round(v) : v; }
+        for (int n = 0; n < N; ++n) for (int k = 0; k < K; ++k) { float v = c.tB ? B_[(size_t)n * ldb + k] : B_[(size_t)k * ldb + n]; b[(size_t)n * K + k] = b16 ? bf16_round(v) : v; }
+        std::vector<float> ah, al, bh, bl;
+        float s_a = 1.f, s_b = 1.f;
+        if (x3) {
+            s_a = pack3_scale(a, M, K, K); s_b = pack3_scale(b, N, K, K);
+            ah.resize(a.size()); al.resize(a.size()); bh.resize(b.size()); bl.resize(b.size());
+            for (size_t i = 0; i < a.size(); ++i) split2(a[i], s_a, ah[i], al[i]);
+            for (size_t i = 0; i < b.size(); ++i) split2(b[i], s_b, bh[i], bl[i]);
         }
-    // padding columns of C must be untouched
+        for (int m = 0; m < M; ++m)
+            for (int n = 0; n < N; ++n) {
+                const float* ar = &a[(size_t)m * K];
+                const float* br = &b[(size_t)n * K];
+                double s = 0, sabs = 0, sf = 0; float s32 = 0.f;
+                for (int k = 0; k < K; ++k) {
+                    const double pr = (double)ar[k] * (double)br[k];
+                    s += pr; sabs += std::fabs(pr); s32 += ar[k] * br[k];
+                }
+                if (x3) {
+                    const float *ahr = &ah[(size_t)m * K], *alr = &al[(size_t)m * K], *bhr = &bh[(size_t)n * K], *blr = &bl[(size_t)n * K];
+                    for (int k = 0; k < K; ++k) sf += (double)ahr[k] * bhr[k] + (double)ahr[k] * blr[k] + (double)alr[k] * bhr[k];
+                    sf /= (double)s_a * (double)s_b;
+                }
+                // the epilogue three times: double reference, float restatement, the format's value in double; and the sum of |terms|
+                double v = s * (double)alpha, vf = sf * (double)alpha, t = sabs * (double)alpha; float w = s32 * alpha;
+                if (c.split <= 1) {
+                    if (c.flags & LSTC_EPI_BIAS) { v += hbias[n]; vf += hbias[n]; w += hbias[n]; t += std::fabs(hbias[n]); }
+                    if (c.flags & LSTC_EPI_RELU) { v = v > 0 ? v : 0; vf = vf > 0 ? vf : 0; w = w > 0 ? w : 0; }
+                    if (drop) {
+                        const bool kp = keep[(size_t)m * N + n] != 0; kept += kp;
+                        v = kp ? v * dscale : 0; vf = kp ? vf * dscale : 0; w = kp ? w * fscale : 0.f; t *= dscale;
+                    }
+                    if (c.flags & LSTC_EPI_RESIDUAL) { const float r = hres[(size_t)m * ldr + n]; v += r; vf += r; w += r; t += std::fabs(r); }
+                    if (c.flags & LSTC_EPI_RELU_MASK) { const bool on = hmask[(size_t)m * ldm + n] > 0; v = on ? v : 0; vf = on ? vf : 0; w = on ? w : 0.f; }
+                    if (c.flags & LSTC_EPI_ACCUM) { v += 0.5; vf += 0.5; w += 0.5f; t += 0.5; }
+                }
+                const float o = O_[(size_t)m * ldc + n];
+                maxerr = std::isfinite(o) ? std::fmax(maxerr, std::fabs(v - o)) : INFINITY;
+                e32 = std::fmax(e32, std::fabs(v - (double)w));
+                if (x3) efmt = std::fmax(efmt, std::fabs(v - vf));
+                Bmax = std::fmax(Bmax, t);
+            }
+    }
+    // padding columns of C (and the gaps between the problems of a batch) must be untouched
     bool pad_ok = true;
-    for (int m = 0; m < M; ++m)
-        for (int n = N; n < ldc; ++n) pad_ok &= out[(size_t)m * ldc + n] == (c.split > 1 ? 0.f : 0.5f);
-    // f32x3 is held to the f32 kernels' bound (operands in [-1, 1): |sum| <~ sqrt(K))
-    const bool ok = maxerr < 2e-4 * std::sqrt((double)K) * (c.dtype == LSTC_F32X3 ? 0.02 : 1.0) && pad_ok;
+    const float c0 = c.split > 1 ? 0.f : 0.5f;
+    for (int z = 0; z < batch; ++z) {
+        const float* O_ = out.data() + (batch > 1 ? sc * z : 0);
+        for (int m = 0; m < M; ++m)
+            for (int n = N; n < ldc; ++n) pad_ok &= O_[(size_t)m * ldc + n] == c0;
+        if (batch > 1) for (size_t i = nc1; i < sc; ++i) pad_ok &= O_[i] == c0;
+    }
+    if (drop && c.p > 0.f) pad_ok &= kept > 0 && kept < (size_t)M * batch * N;   // with p > 0 the mask really dropped and really kept (p = 0 keeps everything)
+    const double tol = 8.0 * std::fmax(std::fmax(e32, efmt), 4.0 * std::ldexp(1.0, -24) * Bmax);
+    const bool ok = maxerr <= tol && pad_ok;
     if (pA) hipFree(pA);
     if (pB) hipFree(pB);
-    printf("%s %s M=%d N=%d K=%d tA=%d tB=%d flags=%d var=%d split=%d maxerr=%.3g pad_ok=%d\n", ok ? "PASS" : "FAIL",
-           c.dtype == LSTC_F32X3 ? "f32x3" : c.dtype == LSTC_BF16P ? "bf16p" : c.dtype ? "bf16c" : "f32", M, N, K, c.tA, c.tB, c.flags, c.variant, c.split, maxerr, (int)pad_ok);
+    printf("%s %s M=%d N=%d K=%d tA=%d tB=%d flags=%d var=%d split=%d p=%.1f batch=%d maxerr=%.3g tol=%.3g ratio=%.3f pad_ok=%d\n", ok ? "PASS" : "FAIL",
+           c.dtype == LSTC_F32X3 ? "f32x3" : c.dtype == LSTC_BF16P ? "bf16p" : c.dtype ? "bf16c" : "f32", M, N, K, c.tA, c.tB, c.flags, c.variant, c.split,
+           c.p, batch, maxerr, tol, tol > 0 ? maxerr / tol : 0.0, (int)pad_ok);
     fflush(stdout);
     hipFree(dA); hipFree(dB); hipFree(dC); hipFree(dbias); hipFree(dres); hipFree(dmask);
     return ok ? 0 : 1;
@@ -333,6 +411,19 @@ int main(int argc, char** argv) {
             fails += check({8448, 2048, 64, 0, 1, LSTC_EPI_RESIDUAL, 1, 1, LSTC_BF16P, 1});
             fails += check({8448, 2048, 128, 0, 1, LSTC_EPI_RELU_MASK | LSTC_EPI_BIAS, 1, 1, LSTC_BF16P, 1});
         }
+        // dropout (p = 0.3, the mask fetched with lstc_dropout_mask): one case per dtype, ldc != N
+        const int DROP = LSTC_EPI_BIAS | LSTC_EPI_DROPOUT | LSTC_EPI_RESIDUAL;
+        fails += check({257, 132, 68, 0, 1, DROP, 4, 1, LSTC_F32, 1, 0.3f});
+        fails += check({257, 131, 67, 0, 1, DROP, 0, 1, LSTC_F32, 0, 0.3f});
+        fails += check({257, 131, 67, 0, 1, DROP, 0, 1, LSTC_BF16, 0, 0.3f});
+        fails += check({300, 520, 132, 0, 1, DROP, 0, 1, LSTC_F32X3, 1, 0.3f});
+        fails += check({300, 520, 132, 0, 1, DROP, 1, 1, LSTC_BF16P, 1, 0.3f});
+        // batch = 3 with strides that are not the dense ones (alpha / ACCUM epilogues only)
+        for (int tb : {1, 0}) {
+            fails += check({68, 36, 40, 0, tb, 0, 0, 1, LSTC_F32, 0, 0.f, 3});
+            fails += check({68, 36, 72, 0, tb, LSTC_EPI_ACCUM, 1, 1, LSTC_BF16, 0, 0.f, 3});
+        }
+        fails += check({68, 36, 40, 1, 0, LSTC_EPI_ACCUM, 4, 1, LSTC_F32, 0, 0.f, 3});
         printf("%s: %d failing cases\n", fails ? "FAILED" : "ALL PASS", fails);
     }
     if (check_only) return fails;
