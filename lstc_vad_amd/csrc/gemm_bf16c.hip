@@ -175,7 +175,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_bf16c_kernel(const GemmPar
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
-    const int l31 = lane & 31, h = lane >> 5;
 
     floatx16 acc[TM][TN];
 #pragma unroll
@@ -230,40 +229,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_bf16c_kernel(const GemmPar
         __syncthreads();
     }
 
-    // ---- epilogue (identical semantics to gemm_f32.hip)
-    const int flags = p.flags;
-    const bool atomic = gridDim.y > 1;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * WTN + j * 32 + l31;
-        if (col >= p.N) continue;
-        const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int rbase = m0 + wm * WTM + i * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row >= p.M) continue;
-                float v = acc[i][j][r] * p.alpha;
-                float* cp = p.C + (size_t)row * p.ldc + col;
-                if (atomic) {
-                    atomicAdd(cp, v);
-                    continue;
-                }
-                v += bv;
-                if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                if (flags & LSTC_EPI_DROPOUT) {
-                    const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                    v = drop_keep(idx, p.dk) ? v * p.dk.scale : 0.f;
-                }
-                if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                if (flags & LSTC_EPI_ACCUM) v += *cp;
-                *cp = v;
-            }
-        }
-    }
+    // ---- epilogue (lstc_common.h: the one-column-per-lane form is this kernel's only one)
+    epilogue_scalar<TM, TN>(make_epi_args(p.C, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu, p.flags, 0, p.alpha, p.dk),
+                            acc, m0 + wm * WTM, n0 + wn * WTN, lane, gridDim.y > 1);
 }
 
 template <int BM, int BN, int WGM, int WGN, bool A_KC, bool B_KC>
@@ -310,13 +278,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16_impl(const LstcGemmDesc
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return LSTC_E_SHAPE;
     const int a_min = d->transA ? d->M : d->K, b_min = d->transB ? d->K : d->N;
     if (d->lda < a_min || d->ldb < b_min || d->ldc < d->N) return LSTC_E_SHAPE;
-    if ((d->flags & LSTC_EPI_BIAS) && !d->bias) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RESIDUAL) && (!d->residual || d->ldr < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RELU_MASK) && (!d->relu_src || d->ld_relu < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_DROPOUT) && (uint64_t)d->M * (uint64_t)d->N > 0xffffffffull) return LSTC_E_RANGE;
+    if (const int rc = lstc_epi_check(d)) return rc;
     if (d->transA && d->transB) return LSTC_E_UNSUPPORTED;
     const int splits = d->split_k > 1 ? d->split_k : 1;
-    if (splits > 1 && d->flags != 0) return LSTC_E_UNSUPPORTED;
     GemmParams p;
     p.A = (const float*)d->A; p.B = (const float*)d->B; p.C = (float*)d->C;
     p.bias = d->bias; p.res = (const float*)d->residual; p.relu_src = (const float*)d->relu_src;

@@ -159,6 +159,30 @@ struct P1Params {
 
 constexpr int vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }   // s_waitcnt vmcnt(n) only
 
+// 4 x 4 transpose across (4 registers) x (the 4 lanes of a quad, c4 = lane & 3): quad_perm [2,3,0,1] first, then [1,0,3,2] (the
+// order these kernels' machine code was tuned with; quad_transpose of lstc_common.h runs the two steps the other way round)
+__device__ __forceinline__ void p1_quad_transpose(float& v0, float& v1, float& v2, float& v3, int c4) {
+    const bool b1 = (c4 & 2) != 0, b0 = (c4 & 1) != 0;
+    int s0 = __float_as_int(b1 ? v0 : v2), s1 = __float_as_int(b1 ? v1 : v3);
+    float r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
+    float r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0x4E, 0xF, 0xF, true));
+    if (b1) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
+    s0 = __float_as_int(b0 ? v0 : v1); s1 = __float_as_int(b0 ? v2 : v3);
+    r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true));            // quad_perm [1,0,3,2]
+    r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true));
+    if (b0) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
+}
+// v_permlane16_swap / v_permlane32_swap of two registers: the odd 16-lane rows of x <-> the even ones of y / lanes 32-63 of x <-> lanes 0-31 of y
+typedef unsigned p1_uint2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void p1_swap16(float& x, float& y) {
+    const p1_uint2v r_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+    x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);
+}
+__device__ __forceinline__ void p1_swap32(float& x, float& y) {
+    const p1_uint2v r_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+    x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);
+}
+
 // PERSISTENT: gridDim.x workgroups (one per CU) walk the work items (output tile x K split) round by round; in a round the
 // 32 workgroups of an XCD (blockIdx % 8) take 32 consecutive tiles (N fastest), so their A panels are shared in that XCD's
 // L2.  Between two items the LDS-DMA of the NEXT item's first two K steps is issued BEFORE the epilogue of the current one:
@@ -554,7 +578,7 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
         if (has_next) issue_head();
         __builtin_amdgcn_sched_barrier(0);
 
-        // ---- epilogue of (cmb, cnb, csplit) (semantics of gemm_f32.hip)
+        // ---- epilogue of (cmb, cnb, csplit) (the contract and its chain: lstc_common.h)
         bool done = false;
 #ifdef LSTC_TUNING
         if (p.debug & 1) {       // timing ablation: keep the accumulators live, store nothing
@@ -584,7 +608,6 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
         if constexpr (OPK) {
             if (!done) {
                 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-                typedef unsigned uint2v __attribute__((ext_vector_type(2)));
                 typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
                 const bool f_res = (flags & LSTC_EPI_RESIDUAL) != 0, f_mask = (flags & LSTC_EPI_RELU_MASK) != 0;
                 const int hdma = has_next ? (nkt > 1 ? 16 : 8) : 0;                              // LDS-DMA of the next item in flight
@@ -601,18 +624,13 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                     return ((size_t)(2 * cmb + wr) * kbp + cnb * 8 + wc * 2 + cp) * P1_TILE + rt * 512;
                 };
                 // one unit u = 8 rt' + ... : (cp = u >> 3, rt = u & 7): the two 16-column accumulators a4[rt][2 cp], a4[rt][2 cp + 1]
+                // (the chain below mirrors epi_chain of lstc_common.h, eight wide, on packed bf16 operands in registers with loads in flight)
                 auto unit = [&](int rt, int cp, const uint4v& opk, const floatx4v& o0, const floatx4v& o1) {
                     float e0 = a4[S16 ? rt : 0][S16 ? 2 * cp : 0][0], e1 = a4[S16 ? rt : 0][S16 ? 2 * cp : 0][1];
                     float e2 = a4[S16 ? rt : 0][S16 ? 2 * cp : 0][2], e3 = a4[S16 ? rt : 0][S16 ? 2 * cp : 0][3];
                     float o_0 = a4[S16 ? rt : 0][S16 ? 2 * cp + 1 : 0][0], o_1 = a4[S16 ? rt : 0][S16 ? 2 * cp + 1 : 0][1];
                     float o_2 = a4[S16 ? rt : 0][S16 ? 2 * cp + 1 : 0][2], o_3 = a4[S16 ? rt : 0][S16 ? 2 * cp + 1 : 0][3];
-#define P1_SWAP(x, y)                                                                                                    \
-                    do {                                                                                                 \
-                        const uint2v r_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false); \
-                        x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);                                           \
-                    } while (0)
-                    P1_SWAP(e0, o_0); P1_SWAP(e1, o_1); P1_SWAP(e2, o_2); P1_SWAP(e3, o_3);
-#undef P1_SWAP
+                    p1_swap16(e0, o_0); p1_swap16(e1, o_1); p1_swap16(e2, o_2); p1_swap16(e3, o_3);
                     float v[8] = {e0, e1, e2, e3, o_0, o_1, o_2, o_3};
                     const float bvv[8] = {pbias[cp][0][0], pbias[cp][0][1], pbias[cp][0][2], pbias[cp][0][3],
                                           pbias[cp][1][0], pbias[cp][1][1], pbias[cp][1][2], pbias[cp][1][3]};
@@ -776,17 +794,7 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                         }                                                                                               \
                     }                                                                                                   \
                 } while (0)
-                auto xpose2 = [&](float& v0, float& v1, float& v2, float& v3) {
-                    const bool b1 = (c4 & 2) != 0, b0 = (c4 & 1) != 0;
-                    int s0 = __float_as_int(b1 ? v0 : v2), s1 = __float_as_int(b1 ? v1 : v3);
-                    float r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0x4E, 0xF, 0xF, true));
-                    float r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0x4E, 0xF, 0xF, true));
-                    if (b1) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
-                    s0 = __float_as_int(b0 ? v0 : v1); s1 = __float_as_int(b0 ? v2 : v3);
-                    r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true));
-                    r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true));
-                    if (b0) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-                };
+                // (mirrors epi_chain4 of lstc_common.h on operands that are packed bf16 or in registers behind hand-counted waits)
 #define P1_FE_GROUP(v0, v1, v2, v3, rt, hf, cp, bv, av, mv, rv)                                                              \
                 do {                                                                                                    \
                     float4 v = make_float4((v0) * alpha + (bv)[0], (v1) * alpha + (bv)[1], (v2) * alpha + (bv)[2], (v3) * alpha + (bv)[3]); \
@@ -856,17 +864,10 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                         float y0 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][0], y1 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][1];
                         float y2 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][2], y3 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][3];
                         if (!P1_ABL_NOXPOSE) {
-                        xpose2(x0, x1, x2, x3);
-                        xpose2(y0, y1, y2, y3);
+                        p1_quad_transpose(x0, x1, x2, x3, c4);
+                        p1_quad_transpose(y0, y1, y2, y3, c4);
                         }
-                        typedef unsigned uint2v __attribute__((ext_vector_type(2)));
-#define P1_SWAP(x, y)                                                                                                    \
-                        do {                                                                                             \
-                            const uint2v r_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false); \
-                            x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);                                       \
-                        } while (0)
-                        if (!P1_ABL_NOXPOSE) { P1_SWAP(x0, y0); P1_SWAP(x1, y1); P1_SWAP(x2, y2); P1_SWAP(x3, y3); }
-#undef P1_SWAP
+                        if (!P1_ABL_NOXPOSE) { p1_swap16(x0, y0); p1_swap16(x1, y1); p1_swap16(x2, y2); p1_swap16(x3, y3); }
                         P1_FE_GROUP(x0, x1, x2, x3, rt, 0, cp2, fbias[cp2], ax[b & 1][2 * r2], axp[MPK ? (b & 1) : 0][MPK ? 2 * r2 : 0],
                                     axr[RPK ? (b & 1) : 0][RPK ? 2 * r2 : 0]);
                         P1_FE_GROUP(y0, y1, y2, y3, rt, 1, cp2, fbias[cp2], ax[b & 1][2 * r2 + 1], axp[MPK ? (b & 1) : 0][MPK ? 2 * r2 + 1 : 0],
@@ -889,44 +890,18 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
             // instead of 2 rows x 128 B with four times the instructions (cdna_hip_programming.md T21).
             const bool full = (cmb + 1) * 256 <= p.M && (cnb + 1) * 256 <= p.N;       // wave-uniform
             const int c4 = lane & 3, q8 = l31 >> 2;
-            auto xpose = [&](float& v0, float& v1, float& v2, float& v3) {
-                const bool b1 = (c4 & 2) != 0, b0 = (c4 & 1) != 0;
-                int s0 = __float_as_int(b1 ? v0 : v2), s1 = __float_as_int(b1 ? v1 : v3);
-                float r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
-                float r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0x4E, 0xF, 0xF, true));
-                if (b1) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
-                s0 = __float_as_int(b0 ? v0 : v1); s1 = __float_as_int(b0 ? v2 : v3);
-                r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true));            // quad_perm [1,0,3,2]
-                r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true));
-                if (b0) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-            };
             // one output group: 4 consecutive columns of one row held by this lane -> epilogue math -> ONE 16-B store
 #define P1_EPI_STORE(v0, v1, v2, v3, row, col, cok, bv)                                                                  \
             do {                                                                                                         \
                 if (!full && (!(cok) || (row) >= p.M)) break;                                                              \
-                float4 v = make_float4((v0) * alpha + (bv).x, (v1) * alpha + (bv).y, (v2) * alpha + (bv).z, (v3) * alpha + (bv).w); \
-                if (flags & LSTC_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); } \
-                if (flags & LSTC_EPI_DROPOUT) {                                                                            \
-                    const uint32_t idx = (uint32_t)(row) * (uint32_t)p.N + (uint32_t)(col);                                \
-                    v.x = drop_keep(idx, dkn) ? v.x * dkn.scale : 0.f;                                                   \
-                    v.y = drop_keep(idx + 1, dkn) ? v.y * dkn.scale : 0.f;                                               \
-                    v.z = drop_keep(idx + 2, dkn) ? v.z * dkn.scale : 0.f;                                               \
-                    v.w = drop_keep(idx + 3, dkn) ? v.w * dkn.scale : 0.f;                                               \
-                }                                                                                                        \
-                if (flags & LSTC_EPI_RESIDUAL) {                                                                           \
-                    const float4 r = *reinterpret_cast<const float4*>(p.res + (size_t)(row) * p.ldr + (col));              \
-                    v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;                                                        \
-                }                                                                                                        \
-                if (flags & LSTC_EPI_RELU_MASK) {                                                                          \
-                    const float4 m = *reinterpret_cast<const float4*>(p.relu_src + (size_t)(row) * p.ld_relu + (col));     \
-                    v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f; \
-                }                                                                                                        \
-                float* cp = Cz + (size_t)(row) * p.ldc + (col);                                                            \
-                if (flags & LSTC_EPI_ACCUM) { const float4 o = *reinterpret_cast<const float4*>(cp); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; } \
-                if (P1_ABL_NOSTORE) { const floatx4v sv = {v.x, v.y, v.z, v.w}; asm volatile("" :: "v"(sv), "v"(cp)); break; }       \
-                if (P1_ABL_L2STORE) cp = p.C + ((size_t)(row & 255) * p.ldc + (col));                                       \
-                if (P1_ABL_NOSTORE) { const floatx4v sv = {v.x, v.y, v.z, v.w}; asm volatile("" :: "v"(sv), "v"(cp)); break; }       \
-                if (P1_ABL_L2STORE) cp = p.C + ((size_t)((row) & 255) * p.ldc + (col));                                     \
+                float4 v = make_float4((v0) * alpha + (bv).x, (v1) * alpha + (bv).y, (v2) * alpha + (bv).z, (v3) * alpha + (bv).w);\
+                float* cp = Cz + (size_t)(row) * p.ldc + (col);                                                          \
+                v = epi_chain4(v, flags, (uint32_t)(row) * (uint32_t)p.N + (uint32_t)(col), dkn,      /* lstc_common.h */\
+                               [&] { return *reinterpret_cast<const float4*>(p.res + (size_t)(row) * p.ldr + (col)); },  \
+                               [&] { return *reinterpret_cast<const float4*>(p.relu_src + (size_t)(row) * p.ld_relu + (col)); },\
+                               [&] { return *reinterpret_cast<const float4*>(cp); });                                    \
+                if (P1_ABL_NOSTORE) { const floatx4v sv = {v.x, v.y, v.z, v.w}; asm volatile("" :: "v"(sv), "v"(cp)); break; }\
+                if (P1_ABL_L2STORE) cp = p.C + ((size_t)((row) & 255) * p.ldc + (col));                                  \
                 if (full) {      /* exactly one store instruction per group: 32 per wave, counted by the next item's waits */ \
                     const floatx4v sv = {v.x, v.y, v.z, v.w};                                                              \
                     /* s_nop 1: the store reads its 16 B of data registers after issue (cdna_hip_programming.md 5.7 item 1) */ \
@@ -953,16 +928,9 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                         float x2 = a4[S16 ? rt : 0][S16 ? 2 * cp2 : 0][2], x3 = a4[S16 ? rt : 0][S16 ? 2 * cp2 : 0][3];
                         float y0 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][0], y1 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][1];
                         float y2 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][2], y3 = a4[S16 ? rt : 0][S16 ? 2 * cp2 + 1 : 0][3];
-                        xpose(x0, x1, x2, x3);
-                        xpose(y0, y1, y2, y3);
-                        typedef unsigned uint2v __attribute__((ext_vector_type(2)));
-#define P1_SWAP(x, y)                                                                                                    \
-                        do {                                                                                             \
-                            const uint2v r_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false); \
-                            x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);                                       \
-                        } while (0)
-                        P1_SWAP(x0, y0); P1_SWAP(x1, y1); P1_SWAP(x2, y2); P1_SWAP(x3, y3);
-#undef P1_SWAP
+                        p1_quad_transpose(x0, x1, x2, x3, c4);
+                        p1_quad_transpose(y0, y1, y2, y3, c4);
+                        p1_swap32(x0, y0); p1_swap32(x1, y1); p1_swap32(x2, y2); p1_swap32(x3, y3);
                         const int row = cmb * 256 + wr * 128 + rt * 16 + 4 * (c16 & 1) + c4;
                         P1_EPI_STORE(x0, x1, x2, x3, row, col, cok, bv);
                         P1_EPI_STORE(y0, y1, y2, y3, row + 8, col, cok, bv);
@@ -981,7 +949,7 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
                         for (int g = 0; g < 4; ++g) {
                             float v0 = acc[S16 ? 0 : i][S16 ? 0 : j][4 * g], v1 = acc[S16 ? 0 : i][S16 ? 0 : j][4 * g + 1];
                             float v2 = acc[S16 ? 0 : i][S16 ? 0 : j][4 * g + 2], v3 = acc[S16 ? 0 : i][S16 ? 0 : j][4 * g + 3];
-                            xpose(v0, v1, v2, v3);
+                            p1_quad_transpose(v0, v1, v2, v3, c4);
                             const int row = cmb * 256 + wr * 128 + i * 32 + 4 * h + 8 * g + c4;
                             P1_EPI_STORE(v0, v1, v2, v3, row, col, cok, bv);
                         }
@@ -994,38 +962,33 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_kernel(const P1Params p) {
             else { pending = false; __builtin_amdgcn_s_waitcnt(vmcnt_imm(0)); }
         }
         if (!done) {
-            constexpr int NCG = S16 ? 4 : 2, NRT = S16 ? 8 : 4, NR = S16 ? 4 : 16;
+            if constexpr (S16) {       // 16x16 accumulators: column l15, rows 4 c16 + r of the tile - the chain of lstc_common.h in this layout's loop
 #pragma unroll
-            for (int j = 0; j < NCG; ++j) {
-                const int col = cnb * 256 + wc * 64 + (S16 ? j * 16 + l15 : j * 32 + l31);
-                if (col >= p.N) continue;
-                const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
+                for (int j = 0; j < 4; ++j) {
+                    const int col = cnb * 256 + wc * 64 + j * 16 + l15;
+                    if (col >= p.N) continue;
+                    const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
 #pragma unroll
-                for (int i = 0; i < NRT; ++i) {
-                    const int rbase = cmb * 256 + wr * 128 + (S16 ? i * 16 + 4 * c16 : i * 32 + 4 * h);
+                    for (int i = 0; i < 8; ++i) {
 #pragma unroll
-                    for (int r = 0; r < NR; ++r) {
-                        const int row = rbase + (r & 3) + 8 * (r >> 2);
-                        if (row >= p.M) continue;
-                        float v;
-                        if constexpr (S16) v = a4[i][j][r] * alpha; else v = acc[S16 ? 0 : i][S16 ? 0 : j][r] * alpha;
-                        float* cp = Cz + (size_t)row * p.ldc + col;
-                        if (atomic) {
-                            atomicAdd(cp, v);
-                            continue;
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = cmb * 256 + wr * 128 + i * 16 + 4 * c16 + r;
+                            if (row >= p.M) continue;
+                            float v = a4[i][j][r] * alpha;
+                            float* cp = Cz + (size_t)row * p.ldc + col;
+                            if (atomic) {
+                                atomicAdd(cp, v);
+                                continue;
+                            }
+                            v += bv;
+                            *cp = epi_chain(v, flags, (uint32_t)row * (uint32_t)p.N + (uint32_t)col, dkn, [&] { return p.res[(size_t)row * p.ldr + col]; },
+                                            [&] { return p.relu_src[(size_t)row * p.ld_relu + col]; }, [&] { return *cp; });
                         }
-                        v += bv;
-                        if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                        if (flags & LSTC_EPI_DROPOUT) {
-                            const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                            v = drop_keep(idx, dkn) ? v * dkn.scale : 0.f;
-                        }
-                        if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                        if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                        if (flags & LSTC_EPI_ACCUM) v += *cp;
-                        *cp = v;
                     }
                 }
+            } else {
+                epilogue_scalar<4, 2>(make_epi_args(Cz, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu, flags, 0, alpha, dkn), acc,
+                                      cmb * 256 + wr * 128, cnb * 256 + wc * 64, lane, atomic);
             }
             pending = false;
             __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
@@ -1208,7 +1171,6 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
     const int flags = p.flags;
     const float alpha = p.alpha;
     const int urow0 = mb * 256 + qr * 128 + w2r * 64, ucol0 = nb * 256 + qc * 128 + w2c * 64;
-    typedef unsigned uint2v __attribute__((ext_vector_type(2)));
     if constexpr (OPK) {
         typedef unsigned uint4v __attribute__((ext_vector_type(4)));
         typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
@@ -1235,13 +1197,8 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
             for (int rt = 0; rt < 4; ++rt) {
                 float e0 = qa[rt][2 * cp][0], e1 = qa[rt][2 * cp][1], e2 = qa[rt][2 * cp][2], e3 = qa[rt][2 * cp][3];
                 float o_0 = qa[rt][2 * cp + 1][0], o_1 = qa[rt][2 * cp + 1][1], o_2 = qa[rt][2 * cp + 1][2], o_3 = qa[rt][2 * cp + 1][3];
-#define P1_SWAP(x, y)                                                                                                    \
-                do {                                                                                                     \
-                    const uint2v r_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false); \
-                    x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);                                               \
-                } while (0)
-                P1_SWAP(e0, o_0); P1_SWAP(e1, o_1); P1_SWAP(e2, o_2); P1_SWAP(e3, o_3);
-#undef P1_SWAP
+                p1_swap16(e0, o_0); p1_swap16(e1, o_1); p1_swap16(e2, o_2); p1_swap16(e3, o_3);
+                // (the twin of the main kernel's `unit`: mirrors epi_chain of lstc_common.h, eight wide, on packed bf16 operands)
                 float v[8] = {e0, e1, e2, e3, o_0, o_1, o_2, o_3};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = v[e] * alpha + bvv[e];
@@ -1298,38 +1255,14 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
     } else {
         // f32 output: quad transposes + the half-wave exchange of the main kernel's wide epilogue - a lane stores 4 consecutive columns
         const int c4 = lane & 3;
-        auto xpose = [&](float& v0, float& v1, float& v2, float& v3) {
-            const bool b1 = (c4 & 2) != 0, b0 = (c4 & 1) != 0;
-            int s0 = __float_as_int(b1 ? v0 : v2), s1 = __float_as_int(b1 ? v1 : v3);
-            float r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0x4E, 0xF, 0xF, true));
-            float r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0x4E, 0xF, 0xF, true));
-            if (b1) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
-            s0 = __float_as_int(b0 ? v0 : v1); s1 = __float_as_int(b0 ? v2 : v3);
-            r0 = __int_as_float(__builtin_amdgcn_mov_dpp(s0, 0xB1, 0xF, 0xF, true));
-            r1 = __int_as_float(__builtin_amdgcn_mov_dpp(s1, 0xB1, 0xF, 0xF, true));
-            if (b0) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-        };
         auto store4 = [&](float v0, float v1, float v2, float v3, int row, int col, const float4& bv) {
             if (col >= p.N || row >= p.M) return;
             float4 v = make_float4(v0 * alpha + bv.x, v1 * alpha + bv.y, v2 * alpha + bv.z, v3 * alpha + bv.w);
-            if (flags & LSTC_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if (flags & LSTC_EPI_DROPOUT) {
-                const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                v.x = drop_keep(idx, dkn) ? v.x * dkn.scale : 0.f;
-                v.y = drop_keep(idx + 1, dkn) ? v.y * dkn.scale : 0.f;
-                v.z = drop_keep(idx + 2, dkn) ? v.z * dkn.scale : 0.f;
-                v.w = drop_keep(idx + 3, dkn) ? v.w * dkn.scale : 0.f;
-            }
-            if (flags & LSTC_EPI_RESIDUAL) {
-                const float4 r = *reinterpret_cast<const float4*>(p.res + (size_t)row * p.ldr + col);
-                v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-            }
-            if (flags & LSTC_EPI_RELU_MASK) {
-                const float4 m = *reinterpret_cast<const float4*>(p.relu_src + (size_t)row * p.ld_relu + col);
-                v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-            }
             float* cp = p.C + (size_t)row * p.ldc + col;
-            if (flags & LSTC_EPI_ACCUM) { const float4 o = *reinterpret_cast<const float4*>(cp); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+            v = epi_chain4(v, flags, (uint32_t)row * (uint32_t)p.N + (uint32_t)col, dkn,      // lstc_common.h
+                           [&] { return *reinterpret_cast<const float4*>(p.res + (size_t)row * p.ldr + col); },
+                           [&] { return *reinterpret_cast<const float4*>(p.relu_src + (size_t)row * p.ld_relu + col); },
+                           [&] { return *reinterpret_cast<const float4*>(cp); });
             *reinterpret_cast<float4*>(cp) = v;
         };
 #pragma unroll
@@ -1341,15 +1274,9 @@ __global__ void __launch_bounds__(NT8, 2) gemm_bf16p_q_kernel(const P1Params p, 
             for (int rt = 0; rt < 4; ++rt) {
                 float x0 = qa[rt][2 * cp2][0], x1 = qa[rt][2 * cp2][1], x2 = qa[rt][2 * cp2][2], x3 = qa[rt][2 * cp2][3];
                 float y0 = qa[rt][2 * cp2 + 1][0], y1 = qa[rt][2 * cp2 + 1][1], y2 = qa[rt][2 * cp2 + 1][2], y3 = qa[rt][2 * cp2 + 1][3];
-                xpose(x0, x1, x2, x3);
-                xpose(y0, y1, y2, y3);
-#define P1_SWAP(x, y)                                                                                                    \
-                do {                                                                                                     \
-                    const uint2v r_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false); \
-                    x = __uint_as_float(r_[0]); y = __uint_as_float(r_[1]);                                               \
-                } while (0)
-                P1_SWAP(x0, y0); P1_SWAP(x1, y1); P1_SWAP(x2, y2); P1_SWAP(x3, y3);
-#undef P1_SWAP
+                p1_quad_transpose(x0, x1, x2, x3, c4);
+                p1_quad_transpose(y0, y1, y2, y3, c4);
+                p1_swap32(x0, y0); p1_swap32(x1, y1); p1_swap32(x2, y2); p1_swap32(x3, y3);
                 const int row = urow0 + rt * 16 + 4 * (c16 & 1) + c4;
                 store4(x0, x1, x2, x3, row, col, bv);
                 store4(y0, y1, y2, y3, row + 8, col, bv);
@@ -1368,13 +1295,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
     if (!d->A || !d->B || !d->C) return LSTC_E_NULL;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || (!(d->flags & LSTC_EPI_OUT_PACK) && d->ldc < d->N)) return LSTC_E_SHAPE;
     if (d->batch > 1) return LSTC_E_UNSUPPORTED;
-    if ((d->flags & LSTC_EPI_BIAS) && !d->bias) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RESIDUAL) && (!d->residual || (!(d->flags & LSTC_EPI_RESIDUAL_PACK) && d->ldr < d->N))) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RELU_MASK) && (!d->relu_src || (!(d->flags & LSTC_EPI_RELU_MASK_PACK) && d->ld_relu < d->N))) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_DROPOUT) && (uint64_t)d->M * (uint64_t)d->N > 0xffffffffull) return LSTC_E_RANGE;
-    if (!aligned16(d->A) || !aligned16(d->B)) return LSTC_E_ALIGN;
+    if (const int rc = lstc_epi_check(d, (d->flags & LSTC_EPI_RESIDUAL_PACK) != 0, (d->flags & LSTC_EPI_RELU_MASK_PACK) != 0,
+                                      aligned16(d->A) && aligned16(d->B))) return rc;
     const int splits = d->split_k > 1 ? d->split_k : 1;
-    if (splits > 1 && d->flags != 0) return LSTC_E_UNSUPPORTED;
     // (transA, transB) = (0, 1): A, B are packs of [M, K], [N, K];  (1, 0): packs of the k-major sources [K, M], [K, N]
     const bool tr = d->transA != 0 && d->transB == 0;
     if (!tr && !(d->transA == 0 && d->transB != 0)) return LSTC_E_UNSUPPORTED;
@@ -1414,10 +1337,7 @@ __attribute__((visibility("hidden"))) int lstc_gemm_bf16p_impl(const LstcGemmDes
     p.debug = 0;
     if (variant_ != 0) return LSTC_E_UNSUPPORTED;
 #endif
-    p.vec_epi = (d->N % 4 == 0) && (d->ldc % 4 == 0) && aligned16(d->C) && (p.split_stride % 4 == 0) &&
-                (!(d->flags & LSTC_EPI_BIAS) || aligned16(d->bias)) &&
-                (!(d->flags & LSTC_EPI_RESIDUAL) || (aligned16(d->residual) && (p.res_kbp || d->ldr % 4 == 0))) &&
-                (!(d->flags & LSTC_EPI_RELU_MASK) || (aligned16(d->relu_src) && (p.mask_kbp || d->ld_relu % 4 == 0)));
+    p.vec_epi = lstc_epi_rows16(d, p.res_kbp != 0, p.mask_kbp != 0) && (p.split_stride % 4 == 0);      // any number of per-element operands
     if ((p.out_kbp || p.mask_kbp) && !p.vec_epi) return LSTC_E_ALIGN;
 #ifdef LSTC_TUNING
     if (p.debug & 2) p.vec_epi = 0;

@@ -48,7 +48,6 @@ struct GemmParams {
     int ktiles, ktiles_per_split;
     long long batch_stride_a, batch_stride_b, batch_stride_c;   // elements between consecutive problems of a batch (grid.z)
     unsigned int a_bytes, b_bytes;   // operand extents for the buffer descriptors of PIPE 5 (operands < 4 GiB)
-    int unused_ = 0;   // keeps the kernel-argument offsets of the two fields below, and with them every kernel's machine code, as they were
     int row_off;   // first row of this launch inside the caller's matrix (dropout counter of a row-split product)
     int epi_f4;    // 0: scalar epilogue; 1 / 2: float4 epilogue allowed, without / with ONE per-element operand (epilogue_f4)
 };
@@ -485,39 +484,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) gemm_f32_kernel(const GemmParam
             return;
         }
     }
-    const int flags = p.flags;
-    const bool atomic = gridDim.y > 1;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * WTN + j * 32 + l31;
-        if (col >= p.N) continue;
-        const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int rbase = m0 + wm * WTM + i * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row >= p.M) continue;
-                float v = acc[i][j][r] * p.alpha;
-                float* cp = p.C + (size_t)row * p.ldc + col;
-                if (atomic) {
-                    atomicAdd(cp, v);
-                    continue;
-                }
-                v += bv;
-                if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                if (flags & LSTC_EPI_DROPOUT) {
-                    const uint32_t idx = (uint32_t)(row + p.row_off) * (uint32_t)p.N + (uint32_t)col;
-                    v = drop_keep(idx, p.dk) ? v * p.dk.scale : 0.f;
-                }
-                if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                if (flags & LSTC_EPI_ACCUM) v += *cp;
-                *cp = v;
-            }
-        }
-    }
+    epilogue_scalar<TM, TN>(LSTC_EPI_ARGS(p), acc, m0 + wm * WTM, n0 + wn * WTN, lane, gridDim.y > 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -782,13 +749,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32_impl(const LstcGemmDesc*
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return LSTC_E_SHAPE;
     const int a_min = d->transA ? d->M : d->K, b_min = d->transB ? d->K : d->N;
     if (d->lda < a_min || d->ldb < b_min || d->ldc < d->N) return LSTC_E_SHAPE;
-    if ((d->flags & LSTC_EPI_BIAS) && !d->bias) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RESIDUAL) && (!d->residual || d->ldr < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RELU_MASK) && (!d->relu_src || d->ld_relu < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_DROPOUT) && (uint64_t)d->M * (uint64_t)d->N > 0xffffffffull) return LSTC_E_RANGE;
+    if (const int rc = lstc_epi_check(d)) return rc;
     if (d->transA && d->transB) return LSTC_E_UNSUPPORTED;
     const int splits = d->split_k > 1 ? d->split_k : 1;
-    if (splits > 1 && d->flags != 0) return LSTC_E_UNSUPPORTED;
     GemmParams p;
     p.A = (const float*)d->A; p.B = (const float*)d->B; p.C = (float*)d->C;
     p.bias = d->bias; p.res = (const float*)d->residual; p.relu_src = (const float*)d->relu_src;
@@ -804,7 +767,7 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32_impl(const LstcGemmDesc*
     // the documented tile variants only: garbage in this public field must not select an undefined tile
     // (LstcGemmDesc.variant, include/lstc_hip.h)
     if (!(d->variant == 0 || d->variant == 4 || d->variant == 8 || d->variant == 11 || d->variant == 12)) return LSTC_E_UNSUPPORTED;
-    const size_t a_ext = ((size_t)((d->transA ? d->K : d->M) - 1) * d->lda + (d->transA ? d->M : d->K)) * sizeof(float) + p.batch_stride_a * sizeof(float) * (size_t)(p.batch - 1) * 0;
+    const size_t a_ext = ((size_t)((d->transA ? d->K : d->M) - 1) * d->lda + (d->transA ? d->M : d->K)) * sizeof(float);
     const size_t b_ext = ((size_t)((d->transB ? d->N : d->K) - 1) * d->ldb + (d->transB ? d->K : d->N)) * sizeof(float);
     const bool fits32 = a_ext < 0xffffffffull && b_ext < 0xffffffffull;
     p.a_bytes = (unsigned int)(fits32 ? a_ext : 0);
@@ -817,16 +780,9 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32_impl(const LstcGemmDesc*
     const bool vb = aligned16(d->B) && (d->ldb % 4 == 0) && ((d->transB ? d->K : d->N) % 4 == 0) &&
                     (p.batch <= 1 || d->batch_stride_b % 4 == 0);
     p.row_off = 0;
-    // float4 epilogue (epilogue_f4): one row-contiguous float4 per lane and store, operands as float4 loads - needs 16-B aligned rows
-    // everywhere and at most ONE per-element operand (residual | ReLU-mask source | accumulate target)
-    {
-        const int naux = ((d->flags & LSTC_EPI_RESIDUAL) ? 1 : 0) + ((d->flags & LSTC_EPI_RELU_MASK) ? 1 : 0) + ((d->flags & LSTC_EPI_ACCUM) ? 1 : 0);
-        const bool al = d->N % 4 == 0 && d->N >= 4 && d->ldc % 4 == 0 && aligned16(d->C) && (!(d->flags & LSTC_EPI_BIAS) || aligned16(d->bias)) &&
-                        (!(d->flags & LSTC_EPI_RESIDUAL) || (d->ldr % 4 == 0 && aligned16(d->residual))) &&
-                        (!(d->flags & LSTC_EPI_RELU_MASK) || (d->ld_relu % 4 == 0 && aligned16(d->relu_src)));
-        // (batched launches - the split-K partials of the weight gradients - qualify when every problem's C stays 16-B aligned)
-        p.epi_f4 = (al && naux <= 1 && (p.batch <= 1 || d->batch_stride_c % 4 == 0) && eff_splits == 1) ? (naux ? 2 : 1) : 0;
-    }
+    // float4 epilogue (epilogue_f4, lstc_epi_f4_mode).  Batched launches - the split-K partials of the weight gradients - qualify when
+    // every problem's C stays 16-B aligned; a K split adds with atomics in the scalar form
+    p.epi_f4 = lstc_epi_f4_mode(d, (p.batch <= 1 || d->batch_stride_c % 4 == 0) && eff_splits == 1);
     auto launch = [&](GemmParams& q, int variant) {
         if (!d->transA && d->transB) return launch_layout<true, true>(q, va, vb, eff_splits, variant, st);
         if (!d->transA && !d->transB) return launch_layout<true, false>(q, va, vb, eff_splits, variant, st);

@@ -344,47 +344,16 @@ __global__ void __launch_bounds__(NT, 2) gemm_pk2s_kernel(const PkParams p) {
 #undef S2_DMA
 #undef S2_DMA_TILE
 
-    const int flags = p.flags;
     const bool atomic = gridDim.y > 1 && p.split_stride == 0;      // split_stride != 0: split z owns C + z * split_stride
-    float* const Cz = p.C + (size_t)blockIdx.y * p.split_stride;
-    const float alpha = p.alpha * p.inv_a[0] * p.inv_b[0];
+    const EpiArgs ea = make_epi_args(p.C + (size_t)blockIdx.y * p.split_stride, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu,
+                                     p.flags, 0, p.alpha * p.inv_a[0] * p.inv_b[0], dkn);
+    const int mw0 = mb * 128 + wm * 64, nw0 = nb * 128 + wn * 64;
     if (p.epi_f4 && !atomic) {                 // float4 form (host checked alignment and the operand count)
-        EpiArgs ea = make_epi_args(Cz, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu, flags, 0, alpha, dkn);
-        if (p.epi_f4 == 2) epilogue_f4<2, 2, true>(ea, acc, mb * 128 + wm * 64, nb * 128 + wn * 64, lane);
-        else epilogue_f4<2, 2, false>(ea, acc, mb * 128 + wm * 64, nb * 128 + wn * 64, lane);
+        if (p.epi_f4 == 2) epilogue_f4<2, 2, true>(ea, acc, mw0, nw0, lane);
+        else epilogue_f4<2, 2, false>(ea, acc, mw0, nw0, lane);
         return;
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = nb * 128 + wn * 64 + j * 32 + l31;
-        if (col >= p.N) continue;
-        const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rbase = mb * 128 + wm * 64 + i * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row >= p.M) continue;
-                float v = acc[i][j][r] * alpha;
-                float* cp = Cz + (size_t)row * p.ldc + col;
-                if (atomic) {
-                    atomicAdd(cp, v);
-                    continue;
-                }
-                v += bv;
-                if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                if (flags & LSTC_EPI_DROPOUT) {
-                    const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                    v = drop_keep(idx, dkn) ? v * dkn.scale : 0.f;
-                }
-                if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                if (flags & LSTC_EPI_ACCUM) v += *cp;
-                *cp = v;
-            }
-        }
-    }
+    epilogue_scalar<2, 2>(ea, acc, mw0, nw0, lane, atomic);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -534,47 +503,16 @@ __global__ void __launch_bounds__(NT, 1) gemm_pkw_kernel(const PkParams p) {
 #undef WD_DMA
 #undef WD_DMA_TILE
 
-    const int flags = p.flags;
     const bool atomic = gridDim.y > 1 && p.split_stride == 0;      // split_stride != 0: split z owns C + z * split_stride
-    float* const Cz = p.C + (size_t)blockIdx.y * p.split_stride;
-    const float alpha = p.alpha * p.inv_a[0] * p.inv_b[0];
+    const EpiArgs ea = make_epi_args(p.C + (size_t)blockIdx.y * p.split_stride, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu,
+                                     p.flags, 0, p.alpha * p.inv_a[0] * p.inv_b[0], dkn);
+    const int mw0 = mb * 256 + wm * 128, nw0 = nb * 128 + wn * 64;
     if (p.epi_f4 && !atomic) {                 // float4 form (host checked alignment and the operand count)
-        EpiArgs ea = make_epi_args(Cz, p.bias, p.res, p.relu_src, p.M, p.N, p.ldc, p.ldr, p.ld_relu, flags, 0, alpha, dkn);
-        if (p.epi_f4 == 2) epilogue_f4<4, 2, true>(ea, acc, mb * 256 + wm * 128, nb * 128 + wn * 64, lane);
-        else epilogue_f4<4, 2, false>(ea, acc, mb * 256 + wm * 128, nb * 128 + wn * 64, lane);
+        if (p.epi_f4 == 2) epilogue_f4<4, 2, true>(ea, acc, mw0, nw0, lane);
+        else epilogue_f4<4, 2, false>(ea, acc, mw0, nw0, lane);
         return;
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = nb * 128 + wn * 64 + j * 32 + l31;
-        if (col >= p.N) continue;
-        const float bv = (flags & LSTC_EPI_BIAS) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rbase = mb * 256 + wm * 128 + i * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
-                if (row >= p.M) continue;
-                float v = acc[i][j][r] * alpha;
-                float* cp = Cz + (size_t)row * p.ldc + col;
-                if (atomic) {
-                    atomicAdd(cp, v);
-                    continue;
-                }
-                v += bv;
-                if (flags & LSTC_EPI_RELU) v = fmaxf(v, 0.f);
-                if (flags & LSTC_EPI_DROPOUT) {
-                    const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
-                    v = drop_keep(idx, dkn) ? v * dkn.scale : 0.f;
-                }
-                if (flags & LSTC_EPI_RESIDUAL) v += p.res[(size_t)row * p.ldr + col];
-                if (flags & LSTC_EPI_RELU_MASK) v = p.relu_src[(size_t)row * p.ld_relu + col] > 0.f ? v : 0.f;
-                if (flags & LSTC_EPI_ACCUM) v += *cp;
-                *cp = v;
-            }
-        }
-    }
+    epilogue_scalar<4, 2>(ea, acc, mw0, nw0, lane, atomic);
 }
 
 }  // namespace
@@ -585,26 +523,15 @@ __attribute__((visibility("hidden"))) int lstc_gemm_f32x3_impl(const LstcGemmDes
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->ldc < d->N) return LSTC_E_SHAPE;
     if (d->batch > 1) return LSTC_E_UNSUPPORTED;
     if (!(d->variant == 0 || d->variant == 2 || d->variant == 3)) return LSTC_E_UNSUPPORTED;   // 2: 256x128 tiles, 3 = 0: 128x128
-    if ((d->flags & LSTC_EPI_BIAS) && !d->bias) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RESIDUAL) && (!d->residual || d->ldr < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_RELU_MASK) && (!d->relu_src || d->ld_relu < d->N)) return LSTC_E_NULL;
-    if ((d->flags & LSTC_EPI_DROPOUT) && (uint64_t)d->M * (uint64_t)d->N > 0xffffffffull) return LSTC_E_RANGE;
-    if (!aligned16(d->A) || !aligned16(d->B)) return LSTC_E_ALIGN;
+    if (const int rc = lstc_epi_check(d, false, false, aligned16(d->A) && aligned16(d->B))) return rc;
     const int splits = d->split_k > 1 ? d->split_k : 1;
-    if (splits > 1 && d->flags != 0) return LSTC_E_UNSUPPORTED;
     PkParams p;
     p.split_stride = splits > 1 ? d->batch_stride_c : 0;      // K splits into separate partial outputs (no atomics)
     p.A = (const pk_t*)d->A; p.B = (const pk_t*)d->B; p.C = (float*)d->C;
     p.bias = d->bias; p.res = (const float*)d->residual; p.relu_src = (const float*)d->relu_src;
     p.M = d->M; p.N = d->N; p.ldc = d->ldc; p.ldr = d->ldr; p.ld_relu = d->ld_relu; p.flags = d->flags; p.alpha = d->alpha;
     p.dk = make_drop_key(d->dropout_p, d->dropout_seed);
-    {
-        const int naux = ((d->flags & LSTC_EPI_RESIDUAL) ? 1 : 0) + ((d->flags & LSTC_EPI_RELU_MASK) ? 1 : 0) + ((d->flags & LSTC_EPI_ACCUM) ? 1 : 0);
-        const bool al = d->N % 4 == 0 && d->N >= 4 && d->ldc % 4 == 0 && aligned16(d->C) && (!(d->flags & LSTC_EPI_BIAS) || aligned16(d->bias)) &&
-                        (!(d->flags & LSTC_EPI_RESIDUAL) || (d->ldr % 4 == 0 && aligned16(d->residual))) &&
-                        (!(d->flags & LSTC_EPI_RELU_MASK) || (d->ld_relu % 4 == 0 && aligned16(d->relu_src))) && (p.split_stride % 4 == 0);
-        p.epi_f4 = (al && naux <= 1) ? (naux ? 2 : 1) : 0;
-    }
+    p.epi_f4 = lstc_epi_f4_mode(d, p.split_stride % 4 == 0);
     // (transA, transB) = (0, 1): A, B are packs of [M, K], [N, K];  (1, 0): packs of the k-major sources [K, M], [K, N]
     const bool tr = d->transA != 0 && d->transB == 0;
     if (!tr && !(d->transA == 0 && d->transB != 0)) return LSTC_E_UNSUPPORTED;

@@ -770,24 +770,11 @@ __global__ void __launch_bounds__(NT) splitk_finish_kernel(const float* __restri
             const float4 b = *reinterpret_cast<const float4*>(bias + col);
             v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
         }
-        if (flags & LSTC_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        if (flags & LSTC_EPI_DROPOUT) {
-            const uint32_t idx = (uint32_t)row * (uint32_t)N + (uint32_t)col;
-            v.x = drop_keep(idx, dk) ? v.x * dk.scale : 0.f;
-            v.y = drop_keep(idx + 1, dk) ? v.y * dk.scale : 0.f;
-            v.z = drop_keep(idx + 2, dk) ? v.z * dk.scale : 0.f;
-            v.w = drop_keep(idx + 3, dk) ? v.w * dk.scale : 0.f;
-        }
-        if (flags & LSTC_EPI_RESIDUAL) {
-            const float4 x = *reinterpret_cast<const float4*>(res + (int64_t)row * ldr + col);
-            v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
-        }
-        if (flags & LSTC_EPI_RELU_MASK) {
-            const float4 x = *reinterpret_cast<const float4*>(relu_src + (int64_t)row * ld_relu + col);
-            v.x = x.x > 0.f ? v.x : 0.f; v.y = x.y > 0.f ? v.y : 0.f; v.z = x.z > 0.f ? v.z : 0.f; v.w = x.w > 0.f ? v.w : 0.f;
-        }
+        // the chain behind the head: lstc_common.h (this kernel's head adds its bias under the flag, there is no alpha)
         float4* cp = reinterpret_cast<float4*>(C + (int64_t)grp * group_stride_c + (int64_t)row * ldc + col);
-        if (flags & LSTC_EPI_ACCUM) { const float4 x = *cp; v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w; }
+        v = epi_chain4(v, flags, (uint32_t)row * (uint32_t)N + (uint32_t)col, dk,
+                       [&] { return *reinterpret_cast<const float4*>(res + (int64_t)row * ldr + col); },
+                       [&] { return *reinterpret_cast<const float4*>(relu_src + (int64_t)row * ld_relu + col); }, [&] { return *cp; });
         *cp = v;
     }
 }

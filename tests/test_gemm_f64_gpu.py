@@ -256,6 +256,7 @@ def _launch(case, family, ck, seed=SEED, keep_products=False):
     pa = Placed(list(As), _ld(As[0].shape[1], False), 5 if case["a_off"] else 4, NAN, NAN)
     pb = Placed(list(Bs), _ld(Bs[0].shape[1], case["b_odd"]), 4, NAN, NAN)
     odd = bool(case["c_odd"])
+    c_off = 5 if case.get("c_off") else 4                      # c_off: C, residual and relu_src one float off 16-byte alignment
     n_slots = case["split"] if partials else 1
     if partials:
         ldc = N                                                # split z writes C + z * M * N: dense partial slabs
@@ -269,10 +270,10 @@ def _launch(case, family, ck, seed=SEED, keep_products=False):
             c_src = [torch.zeros(M, N) for _ in probs]         # split-K with atomics: the caller zeroes C
         else:
             c_src = [torch.full((M, N), GUARD) for _ in probs]
-        pc = Placed(c_src, ldc, 4, GUARD, GUARD)
+        pc = Placed(c_src, ldc, c_off, GUARD, GUARD)
     P0 = probs[0]
-    pr = Placed([P0["res"]], _ld(N, odd) + (0 if odd else 4), 4, GUARD, GUARD)
-    ps = Placed([P0["src"]], _ld(N, odd) + (0 if odd else 8), 4, GUARD, GUARD)
+    pr = Placed([P0["res"]], _ld(N, odd) + (0 if odd else 4), c_off, GUARD, GUARD)
+    ps = Placed([P0["src"]], _ld(N, odd) + (0 if odd else 8), c_off, GUARD, GUARD)
     bias = torch.cat([torch.full((4,), GUARD), P0["bias"], torch.full((4,), GUARD)]).to(DEV)
 
     d = L.GemmDesc()
@@ -499,6 +500,36 @@ def test_gemm_bf16p_more_tiles_than_cus(variant, name):
     for family in case["families"]:
         got, keep, over = _launch(case, family, ck)
         _check_case(case, family, ck, got, keep, over)
+    ck.done()
+
+
+# ============================================================================================ scalar against float4 epilogue
+# (dtype, M, N, K, layout, variant, id prefix): the smallest shapes that reach each pair of epilogues.  LSTC_BF16 has one epilogue only.
+AGREE = [(G.LSTC_F32, 257, 132, 68, "NT", 0, "agree_f32_pipe5"),                    # epilogue_f4 against epilogue_scalar of PIPE 5
+         (G.LSTC_F32X3, 300, 520, 100, "NT", 0, "agree_pk2s"),                      # gemm_pk 128 x 128 kernel
+         (G.LSTC_F32X3, 512, 200, 96, "NN", 2, "pkw_agree"),                        # 256 x 128 kernel (_assert_branch keys it on the "pkw" prefix: keep it)
+         (G.LSTC_BF16P, 300, 200, 100, "NT", G.NO_QTAIL, "agree_bf16p_wide"),       # wide epilogue on part-filled tiles
+         (G.LSTC_BF16P, 512, 512, 64, "NT", G.NO_QTAIL, "agree_bf16p_fastepi")]     # pipelined epilogue on whole 256 x 256 tiles
+AGREE_SETS = [(n, f, a) for (n, f), a in zip(G.EPI_SETS, G.ALPHAS) if bool(f & G.RESIDUAL) + bool(f & G.RELU_MASK) + bool(f & G.ACCUM) <= 1]
+
+
+@pytest.mark.parametrize("dtype,M,N,K,layout,variant,tag", AGREE, ids=[a[-1] for a in AGREE])
+def test_scalar_and_float4_epilogues_agree_bitwise(dtype, M, N, K, layout, variant, tag):
+    """The same product and flags twice through lstc_gemm: everything 16-byte aligned (float4 / wide / pipelined epilogue), then with
+    C, residual and relu_src one float off at the same leading dimensions (the one-column-per-lane epilogue).  Both launches run the
+    same K loop and both epilogues are the one chain of csrc/lstc_common.h in float32 without contraction: C must be bit-identical,
+    the guards around it untouched.  Every EPI_SETS row with at most one per-element operand, with its alpha, dropout at DROP_P."""
+    assert len(AGREE_SETS) == 8
+    ck = Checks(G.DTYPE_NAMES[dtype], tag)
+    for name, fl, alpha in AGREE_SETS:
+        got = []
+        for c_off in (0, 1):
+            case = G.make_case("%s_%s-%s-%dx%dx%d" % (tag, name, layout, M, N, K), dtype, M, N, K, layout, variant, fl, alpha, c_off=c_off)
+            if dtype == G.LSTC_BF16P:
+                case["qtail"] = False
+            g, _, _ = _launch(case, "randn", ck)                  # (asserts the guards and pad columns of C itself)
+            got.append(g[0])
+        ck.equal("%s C (aligned) == C (one float off)" % name, got[0], got[1])
     ck.done()
 
 
