@@ -592,6 +592,15 @@ int lstc_cast_bf16_f32(const void* x, float* y, int64_t n, void* stream);
 int lstc_gather_rows(const float* src, int64_t src_rows, const int64_t* idx, float* dst, int64_t n_rows,
                      int64_t row_floats, void* stream);
 
+/* dst[j][m, :] = src[j][map[m], :] for m < rows and j < n (1 <= n <= 3) matrices of `cols` floats per row, in ONE launch: the
+ * ordinary [M, H d_k] Q, K and V of layer 0 out of the projections of the unique rows of a batch whose windows overlap
+ * (DESIGN 3.2).  `src`, `dst`, `ld_src`, `ld_dst` are HOST arrays of n entries (device pointers; row strides in floats >= cols).
+ * `map` is a device array of `rows` int32 row numbers into the sources; the kernel takes it as given and clamps nothing, so
+ * every entry must name a row the sources hold.  Bases 16-byte aligned, cols and every row stride multiples of 4
+ * (LSTC_E_ALIGN / LSTC_E_SHAPE), rows <= 2^31; n outside 1..3 LSTC_E_SHAPE; all refusals before the launch. */
+int lstc_expand_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
+                     const int32_t* map, int64_t rows, int32_t cols, void* stream);
+
 /* ------------------------------------------------------------------------------ misc */
 int lstc_version(void);
 const char* lstc_strerror(int code);

@@ -1108,6 +1108,29 @@ __global__ void __launch_bounds__(NT) gather_rows_kernel(const float4* __restric
         out[i] = in[i];
 }
 
+// dst_j[m, :] = src_j[map[m], :] for j < n matrices of `cols4` float4 per row (row strides in float4): Q, K and V of the token rows
+// [M, .] out of the projections of the UNIQUE rows (layer 0 of a batch whose windows overlap), one launch for the three.  One wave
+// per row, the row index wave-uniform; HBM-bound (the unique rows are read once from HBM, their repeats from L2).  The map is taken
+// as given: its entries must lie inside the source matrices.
+struct ExpandArgs {
+    const float4* src[3];
+    float4* dst[3];
+    int64_t ld_src[3], ld_dst[3];
+};
+__global__ void __launch_bounds__(NT) expand_rows_kernel(ExpandArgs a, int n, const int32_t* __restrict__ map, int64_t rows,
+                                                         int cols4) {
+    const int lane = threadIdx.x & 63;
+    const int64_t m = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (m >= rows) return;
+    const int64_t s = map[m];
+    for (int j = 0; j < n; ++j) {
+        const float4* __restrict__ in = a.src[j] + s * a.ld_src[j];
+        float4* __restrict__ out = a.dst[j] + m * a.ld_dst[j];
+#pragma unroll 8
+        for (int c = lane; c < cols4; c += 64) out[c] = in[c];
+    }
+}
+
 inline int grid_for(int64_t work_items, int per_block, int cap = 2048) {
     int64_t g = (work_items + per_block - 1) / per_block;
     if (g < 1) g = 1;
@@ -1590,6 +1613,25 @@ int lstc_gather_rows(const float* src, int64_t src_rows, const int64_t* idx, flo
     if (chunks > 64) chunks = 64;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)n_rows, (unsigned)chunks), NT, 0, (hipStream_t)stream,
                        (const float4*)src, src_rows, idx, (float4*)dst, row_vec);
+    return lstc_launch_status();
+}
+
+int lstc_expand_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
+                     const int32_t* map, int64_t rows, int32_t cols, void* stream) {
+    if (!src || !ld_src || !dst || !ld_dst || !map) return LSTC_E_NULL;
+    if (n < 1 || n > 3 || rows <= 0 || rows > 0x80000000LL || cols <= 0 || (cols & 3)) return LSTC_E_SHAPE;
+    ExpandArgs a = {};
+    for (int j = 0; j < n; ++j) {
+        if (!src[j] || !dst[j]) return LSTC_E_NULL;
+        if (ld_src[j] < cols || ld_dst[j] < cols) return LSTC_E_SHAPE;
+        if (!aligned16(src[j]) || !aligned16(dst[j]) || (ld_src[j] & 3) || (ld_dst[j] & 3)) return LSTC_E_ALIGN;
+        a.src[j] = (const float4*)src[j];
+        a.dst[j] = (float4*)dst[j];
+        a.ld_src[j] = ld_src[j] / 4;
+        a.ld_dst[j] = ld_dst[j] / 4;
+    }
+    const int64_t wg = (rows + NT / 64 - 1) / (NT / 64);
+    hipLaunchKernelGGL(expand_rows_kernel, dim3((unsigned)wg), NT, 0, (hipStream_t)stream, a, (int)n, map, rows, (int)(cols / 4));
     return lstc_launch_status();
 }
 

@@ -99,7 +99,7 @@ class TrainStep:
                     not self.encoder.input_layerNorm and norm_feats.bank.dim() == 3 and norm_feats.bank.shape[1] == a.n_patch):
                 Lc = a.part_len if self.mode == "LTN" else 1
                 n_seq = 2 * norm_feats.bs * norm_feats.rows // Lc
-                cls = self.encoder.forward_cls((norm_feats.bank, norm_feats.idx_flat, n_seq, Lc))
+                cls = self.encoder.forward_cls((norm_feats.bank, norm_feats.idx_flat, n_seq, Lc, norm_feats))
                 outputs = self.head(cls)
                 loss, scalars = training_loss(self.args, self.mode, outputs, abnorm_labs, group=self.group,
                                               distributed=self.loss_rank, exchange=self.loss_exchange)

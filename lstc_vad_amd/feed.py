@@ -8,6 +8,7 @@ with ``non_blocking=True`` on a side HIP stream; the compute stream only waits o
 torch is used purely for memory/stream plumbing."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -70,10 +71,31 @@ class LazyRows:
     the fused gather + CLS-concat kernel (lstc_cls_concat_gather_fwd: the gathered batch is never written); everything else calls
     ``materialize()`` (lstc_gather_rows) and sees the ordinary ``[bs, rows, P, d]`` tensor."""
 
-    def __init__(self, bank, idx_flat, kind, bs, rows):
+    def __init__(self, bank, idx_flat, kind, bs, rows, uniq=None, inverse=None, n_unique=0):
         self.bank, self.idx_flat, self.kind, self.bs, self.rows = bank, idx_flat, kind, bs, rows
         self.shape = (bs, rows) + tuple(bank.shape[1:])
         self.device = bank.device
+        # the batch's clips without their repeats (overlapping windows of short videos): ``uniq[:n_unique]`` the sorted distinct
+        # clip indices, ``inverse[i]`` the place of clip ``idx_flat[i]`` among them (both int64, beside the indices); the host knows
+        # ``n_unique`` before anything is launched.  Layer 0 projects the distinct rows only (functional.DedupRows).
+        self.uniq, self.inverse, self.n_unique = uniq, inverse, int(n_unique)
+        self._row_maps = {}
+
+    def row_map(self, Lc, n_cls):
+        """int32 [N * (1 + Lc * P)]: for every token of the N = 2 * bs * rows / Lc sequences ``[CLS, Lc clips x P patches]`` its row in
+        ``Xu = [n_cls CLS rows; bank[uniq]]`` viewed as [n_cls + n_unique * P, d].  Token (n, s > 0) -> n_cls + u * P + (s - 1) % P with
+        u the place of its clip among the distinct ones; token (n, 0) -> row 0 when one CLS row serves every sequence (n_cls = 1,
+        a learned token), else row n (n_cls = N: the mean of the sequence's own tokens)."""
+        hit = self._row_maps.get((Lc, n_cls))
+        if hit is None:
+            P = int(self.bank.shape[1])
+            N = self.inverse.numel() // Lc
+            if n_cls not in (1, N):
+                raise ValueError(f"row_map: {n_cls} CLS rows for {N} sequences (1 or {N})")
+            tok = self.inverse.view(N, Lc, 1) * P + torch.arange(P, device=self.inverse.device) + n_cls
+            cls = torch.arange(N, device=self.inverse.device).view(N, 1) if n_cls == N else tok.new_zeros((N, 1))
+            hit = self._row_maps[(Lc, n_cls)] = torch.cat([cls, tok.view(N, Lc * P)], 1).reshape(-1).to(torch.int32)
+        return hit
 
     def idx(self):
         n = self.bs * self.rows
@@ -87,6 +109,12 @@ class LazyRows:
         """Is ``other`` the abnormal half of the batch this is the normal half of (one flat index vector, normal first)?"""
         return (isinstance(other, LazyRows) and other.idx_flat is self.idx_flat and self.kind == 0 and other.kind == 1 and
                 (other.bs, other.rows) == (self.bs, self.rows))
+
+
+def unique_clips(idx):
+    """Sorted distinct entries of a clip-index array and, for every entry of ``idx.reshape(-1)``, its place among them (int64)."""
+    uniq, inverse = np.unique(np.asarray(idx).reshape(-1), return_inverse=True)
+    return uniq.astype(np.int64), inverse.reshape(-1).astype(np.int64)
 
 
 class ResidentBank:
@@ -106,7 +134,6 @@ class ResidentBank:
         self._done = [None] * depth
 
     def _stage(self, arrays):
-        import numpy as np
         s = self._slot
         self._slot = (s + 1) % self.depth
         if self._done[s] is not None:
@@ -131,11 +158,19 @@ class ResidentBank:
         # a stale or negative clip index would be a silent out-of-bounds read of HBM - reject it here, on a few hundred integers
         if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= int(self.bank.shape[0])):
             raise IndexError(f"clip index out of range for a bank of {int(self.bank.shape[0])} clips: [{int(idx.min())}, {int(idx.max())}]")
-        dev = self._stage([idx.reshape(-1)] + list(extras))
         if lazy:
             if idx.ndim != 3 or idx.shape[0] != 2:
                 raise ValueError("gather(lazy=True) takes the [2, bs, rows] index array of a normal / abnormal pair batch")
-            return ((LazyRows(self.bank, dev[0], 0, idx.shape[1], idx.shape[2]), LazyRows(self.bank, dev[0], 1, idx.shape[1], idx.shape[2])),
-                    *dev[1:])
+            # indices | distinct clips (padded to the same length: the slab keeps its shape from step to step) | inverse: ONE copy
+            n = idx.size
+            uniq, inverse = unique_clips(idx)
+            staged = np.zeros(3 * n, np.int64)
+            staged[:n], staged[n:n + uniq.size], staged[2 * n:] = idx.reshape(-1), uniq, inverse
+            dev = self._stage([staged] + list(extras))
+            flat, more = dev[0][:n], (dev[0][n:2 * n], dev[0][2 * n:], uniq.size)
+            pair = (LazyRows(self.bank, flat, 0, idx.shape[1], idx.shape[2], *more), LazyRows(self.bank, flat, 1, idx.shape[1], idx.shape[2], *more))
+            pair[1]._row_maps = pair[0]._row_maps
+            return (pair, *dev[1:])
+        dev = self._stage([idx.reshape(-1)] + list(extras))
         out = self.F.gather_rows(self.bank, dev[0]).reshape(tuple(idx.shape) + tuple(self.bank.shape[1:]))
         return (out, *dev[1:])

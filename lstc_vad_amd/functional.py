@@ -246,6 +246,7 @@ def drop_producer_packs():
     producing f32 tensor and its pack: 1.2 GB at the headline shape) never outlives one encoder call - evaluation and
     pseudo-label loops never reach the optimizer's bump_weight_epoch()."""
     _producer_packs.clear()
+    _dedup_rows.clear()
 
 
 def _producer_pack(t: torch.Tensor, kind):
@@ -816,6 +817,82 @@ def gather_rows(bank: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
+def expand_rows(srcs, dsts, row_map: torch.Tensor):
+    """dsts[j][m, :] = srcs[j][row_map[m], :] for up to three float32 matrices of equal width in ONE launch (``lstc_expand_rows``).
+    Row strides are free, columns contiguous; ``row_map`` int32 on the device, one entry per destination row, every entry a row of
+    the sources (the kernel does not clamp)."""
+    n = len(srcs)
+    if n != len(dsts) or row_map.dtype != torch.int32 or not row_map.is_contiguous():
+        raise TypeError("expand_rows: as many sources as destinations and a contiguous int32 row map")
+    rows, cols = dsts[0].shape
+    for a, b in zip(srcs, dsts):
+        if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 2 or tuple(b.shape) != (rows, cols) or a.shape[1] != cols or \
+                a.stride(1) != 1 or b.stride(1) != 1:
+            raise TypeError("expand_rows: float32 matrices of one width with contiguous columns")
+    if row_map.numel() != rows:
+        raise RuntimeError(f"expand_rows: {row_map.numel()} map entries for {rows} rows")
+    ptrs = lambda ts: (C.c_void_p * n)(*[dev_ptr(t) for t in ts])
+    lds = lambda ts: (C.c_int64 * n)(*[t.stride(0) for t in ts])
+    check(_lib.load().lstc_expand_rows(ptrs(srcs), lds(srcs), ptrs(dsts), lds(dsts), n, dev_ptr(row_map), rows, cols, stream_ptr()),
+          "lstc_expand_rows")
+    return dsts
+
+
+# ---- layer-0 projections on the distinct rows of a batch (exact-f32 mode).  The window sampler's parts overlap whenever a video has
+# fewer clips than part_num * part_len, so the same (clip, patch) bank row sits in several sequences; layer 0 has no LayerNorm in front
+# of Q / K / V, which are therefore per-row functions of raw bank rows - equal rows in, equal rows out, bit for bit (every tile form of
+# the GEMM keeps each element's k order, DESIGN 3.1).  The fused gather + CLS concat leaves a ``DedupRows`` beside its result; the
+# attention block that receives that tensor projects Xu = [CLS rows; bank[distinct clips]] and lstc_expand_rows writes the ordinary
+# [M, H d_k] Q, K, V.  Everything behind that - attention, what the backward saves, the backward itself - is unchanged.
+# LSTC_DEDUP_ROWS=0 turns it off (read per call: the reference arm of the tests and of the A/B).
+# The path is taken when the share of rows it saves is at least DEDUP_MIN_SHARE = cost of the added passes / GEMM time of the full
+# projections, measured at the headline shape (M = 100352, d = 2048; profiles/dedup_rows_kernel_stats_{parent,pr}.md): expand 0.75 ms
+# + gathers 0.22 ms + the row map's index arithmetic 0.05 ms + the 64-row tail tiles of three GEMMs whose row count is no longer a
+# multiple of 128, 0.24 ms = 1.26 ms, over 3 x 5.65 ms = 16.95 ms -> 0.074.
+DEDUP_MIN_SHARE = 0.075
+
+
+class DedupRows:
+    __slots__ = ("bank", "uniq", "n_unique", "row_map", "n_cls", "S")
+
+    def __init__(self, bank, uniq, n_unique, row_map, n_cls, S):
+        self.bank, self.uniq, self.n_unique, self.row_map, self.n_cls, self.S = bank, uniq, n_unique, row_map, n_cls, S
+
+    def rows(self):
+        return self.n_cls + self.n_unique * int(self.bank.shape[1])
+
+    def unique_input(self, x2):
+        """Xu [n_cls + U * P, d]: the CLS rows as the concat wrote them into ``x2`` [N * S, d], then the distinct clips' rows."""
+        P, dm = int(self.bank.shape[1]), int(self.bank.shape[2])
+        xu = torch.empty((self.rows(), dm), device=x2.device, dtype=torch.float32)
+        cls_at = torch.arange(0, self.n_cls * self.S, self.S, device=x2.device, dtype=torch.int64)
+        gather_rows(x2, cls_at, out=xu[:self.n_cls])
+        gather_rows(self.bank, self.uniq[:self.n_unique], out=xu[self.n_cls:].view(self.n_unique, P, dm))
+        return xu
+
+
+_dedup_rows = {}            # _pack_key(layer-0 input) -> (tensor, version, DedupRows): one entry, consumed by the block that reads it
+
+
+def _dedup_spec(lazy, idx, N, Lc, S, learned_cls, has_pos, pack_only):
+    """The ``DedupRows`` of a fused-gather batch when layer 0 may and should project distinct rows only, else None."""
+    if (lazy is None or getattr(lazy, "inverse", None) is None or _compute_dtype != F32 or pack_only or has_pos or
+            os.environ.get("LSTC_DEDUP_ROWS", "1") == "0" or lazy.idx_flat is not idx or lazy.inverse.numel() != N * Lc or
+            torch.cuda.is_current_stream_capturing()):
+        return None
+    n_cls = 1 if learned_cls else N
+    if 1.0 - (n_cls + lazy.n_unique * int(lazy.bank.shape[1])) / float(N * S) < DEDUP_MIN_SHARE:
+        return None
+    return DedupRows(lazy.bank, lazy.uniq, lazy.n_unique, lazy.row_map(Lc, n_cls), n_cls, S)
+
+
+def _take_dedup_rows(x):
+    hit = _dedup_rows.pop(_pack_key(x), None) if _dedup_rows else None
+    if hit is None or hit[1] != x._version or hit[0]._version != hit[1] or _compute_dtype != F32:
+        return None
+    return hit[2]
+
+
 def dropout_mask(shape, p: float, seed: int, device) -> torch.Tensor:
     m = torch.empty(shape, device=device, dtype=torch.uint8)
     check(_lib.load().lstc_dropout_mask(dev_ptr(m), m.numel(), float(p), int(seed), stream_ptr()), "lstc_dropout_mask")
@@ -1366,6 +1443,7 @@ class MHAFunction(torch.autograd.Function):
         training = cfg["training"]
         p_attn = cfg["attn_dropout"] if training else 0.0
         p_fc = cfg["fc_dropout"] if training else 0.0
+        dedup = _take_dedup_rows(x)    # exact-f32 mode, x straight from the fused gather + CLS concat: its distinct rows
         x2 = x.contiguous().view(N * S, dm)
         xp = maybe_pack(x2)            # f32x3: one pack of X feeds Q, K, V now and the three weight gradients later
         xa = xp if xp is not None else x2
@@ -1378,6 +1456,23 @@ class MHAFunction(torch.autograd.Function):
             # core reads it (forward and backward) and writes O / dQ | dK | dV as packs: no f32 activation between the two GEMMs
             qkv_p = gemm(xa, wqkv, trans_b=True, out_pack=True)
             q = k = v = None
+        elif dedup is not None:      # layer 0 of a batch with repeated clips: project the distinct rows, then spread them over the tokens
+            xu = dedup.unique_input(x2)
+            if wqkv is not None:
+                qkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
+                expand_rows([gemm(xu, wqkv, trans_b=True)], [qkv], dedup.row_map)
+                q, k, v = qkv[:, : H * dk], qkv[:, H * dk: 2 * H * dk], qkv[:, 2 * H * dk:]
+            else:
+                q, k = (torch.empty((N * S, H * dk), device=x2.device, dtype=torch.float32) for _ in range(2))
+                v = torch.empty((N * S, H * dv), device=x2.device, dtype=torch.float32)
+                us = [gemm(xu, w, trans_b=True) for w in (wq, wk, wv)]
+                if dk == dv:
+                    expand_rows(us, [q, k, v], dedup.row_map)
+                else:
+                    expand_rows(us[:2], [q, k], dedup.row_map)
+                    expand_rows(us[2:], [v], dedup.row_map)
+                del us
+            del xu
         elif wqkv is not None:       # w_qs / w_ks / w_vs live in one buffer (MultiHeadAttention.fuse_qkv_): one GEMM, X read once
             qkv = gemm(xa, wqkv, trans_b=True)
             q, k, v = qkv[:, : H * dk], qkv[:, H * dk: 2 * H * dk], qkv[:, 2 * H * dk:]
@@ -2060,7 +2155,8 @@ class ClsConcatFunction(torch.autograd.Function):
         # x_hi: optional second half of the batch (abnormal sequences); the cat is fused into the kernel
         # pack_only: the bf16 activation stream - the result exists only as layer 0's packed operand (returned as its bf16 view)
         # gather = (clip_idx int64 [N * Lc] on the device, N, Lc): x is a feature BANK [clips, P, d] and sequence n the clips
-        #   clip_idx[n*Lc : (n+1)*Lc] - batch formation, cat and CLS concat in one pass (lstc_cls_concat_gather_fwd)
+        #   clip_idx[n*Lc : (n+1)*Lc] - batch formation, cat and CLS concat in one pass (lstc_cls_concat_gather_fwd); an optional fourth
+        #   entry is the feed.LazyRows behind clip_idx, which knows the batch's distinct clips (layer 0 on distinct rows, ``DedupRows``)
         if gather is not None:
             return ClsConcatFunction._forward_gather(ctx, x, cls_token, pos, pack_only, gather)
         N_lo, Sm1, dm = x.shape
@@ -2122,7 +2218,8 @@ class ClsConcatFunction(torch.autograd.Function):
 
 
 def _cls_concat_gather(ctx, bank, cls_token, pos, pack_only, gather):
-    idx, N, Lc = gather
+    idx, N, Lc = gather[:3]
+    lazy = gather[3] if len(gather) > 3 else None        # the feed.LazyRows behind ``idx``: knows the batch's distinct clips
     clips, P, dm = bank.shape
     S = Lc * P + 1
     if bank.dtype != torch.float32 or not bank.is_contiguous() or idx.dtype != torch.int64 or idx.numel() != N * Lc or bank.requires_grad:
@@ -2144,6 +2241,10 @@ def _cls_concat_gather(ctx, bank, cls_token, pos, pack_only, gather):
         return buf.view(torch.bfloat16)
     if want_pack:
         _register_pack(y.view(N * S, dm), Packed(buf, N * S, dm, _lib.BF16P))
+    spec = _dedup_spec(lazy, idx, N, Lc, S, cls_token is not None, pos is not None, pack_only)
+    _dedup_rows.clear()
+    if spec is not None:
+        _dedup_rows[_pack_key(y)] = (y, y._version, spec)
     return y
 
 

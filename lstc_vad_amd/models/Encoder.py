@@ -62,7 +62,7 @@ class Encoder(nn.Module):
     def _gather_spec(x):
         """``x`` = (bank [clips, P, d], clip_idx int64 [N * Lc] on the device, N, Lc): sequences still to be gathered out of an
         HBM-resident feature bank (engine.TrainStep on a feed.LazyRows batch) -> (N, S - 1, d)."""
-        bank, idx, N, Lc = x
+        bank, idx, N, Lc = x[:4]
         return N, Lc * bank.shape[1], bank.shape[2]
 
     def _act_chain(self, enc_output, enc_output_hi, layers) -> bool:
@@ -87,11 +87,12 @@ class Encoder(nn.Module):
     def _embed(self, enc_output, enc_output_hi=None, pack_only=False):
         if isinstance(enc_output, tuple):
             # batch formation fused into the CLS concat (lstc_cls_concat_gather_fwd): the gathered batch is never written
-            bank, idx, N, Lc = enc_output
+            # an optional fifth entry, the feed.LazyRows behind ``idx``, travels on to the concat (layer 0 on distinct rows)
+            bank, idx, N, Lc = enc_output[:4]
             if self.input_layerNorm:
                 raise RuntimeError("Encoder: a gather spec cannot feed the input LayerNorm (materialise the batch first)")
             out = ClsConcatFunction.apply(bank, self.cls_token if self.CLS_learned else None,
-                                          self.position_enc if self.position_encoding else None, None, pack_only, (idx, N, Lc))
+                                          self.position_enc if self.position_encoding else None, None, pack_only, (idx, N, Lc) + tuple(enc_output[4:5]))
             if pack_only:
                 return PackedAct(out, (N, Lc * bank.shape[1] + 1, bank.shape[2]))
             if self.position_encoding and self.training and self.position_dropout.p > 0:
