@@ -354,6 +354,15 @@ int lstc_cls_wsum(const float* W, const float* X, float* Y, int64_t N, int32_t S
 int lstc_cls_outer(const float* W1, const float* U1, const float* W2, const float* U2, float* dX, int64_t N, int32_t S,
                    int32_t H, int32_t d, void* stream);
 
+/* lstc_cls_dot for a padded batch: sequence n has klen[n] keys (device int32 [N]; the CLS token counts, so klen = real tokens + 1;
+ * values are clamped to [1, S]).  Mode 1 runs the softmax over the keys j < klen[n]; in every mode out (and in mode 1 probs) is
+ * exactly 0 for j >= klen[n], and the rows X[n, j >= klen[n]] are never read - they may hold anything, NaN included.  With zero
+ * weights there lstc_cls_wsum / lstc_cls_outer need no length of their own as long as those rows are finite.  klen[n] == S for
+ * every n gives lstc_cls_dot's result bit for bit.  Same requirements and return codes as lstc_cls_dot, S >= 2 (LSTC_E_SHAPE),
+ * klen == NULL is LSTC_E_NULL. */
+int lstc_cls_dot_len(const float* U, const float* X, const int32_t* klen, float* out, float* probs, int64_t N, int32_t S, int32_t H,
+                     int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream);
+
 /* The three passes above over a PACKED X (round 5: the bf16 activation stream hands the last full layer's output to the CLS-only
  * layer as an lstc_pack1 operand of the [N*S, d] matrix and takes the gradient back as one; same reference lines).  Arithmetic is
  * f32 on the widened bf16 values; lstc_cls_outer_pack rounds dX once (RNE) after adding `add0` [N, d] (may be NULL) to row 0 of
@@ -438,6 +447,19 @@ int lstc_cls_concat_gather_fwd(const float* bank, int64_t bank_clips, const int6
 /* Gradient w.r.t. the Encoder input, needed only when something upstream is trainable (input_layerNorm,
  * models/Encoder.py:48-49): dx[n,t,:] = dy[n,t+1,:] + (mean_cls ? dy[n,0,:]/(S-1) : 0). */
 int lstc_cls_concat_bwd(const float* dy, float* dx, int64_t N, int32_t S, int32_t d, int32_t mean_cls, void* stream);
+
+/* The CLS concat of a PADDED batch: sequence n has lens[n] real tokens x[n, :lens[n]] (device int32 [N], the CLS token not
+ * counted; values are clamped to [1, S-1]), the rest of its row of x is padding that is never read (it may hold NaN).
+ *   forward:  y[n,0] = mean(x[n, :L_n]) (or `cls_token`), y[n,1+t] = x[n,t] for t < L_n, `pos` [S, d] added on rows 0..L_n, and the
+ *             rows past L_n written as exact zeros: row n is what the un-lengthed call gives for x[n:n+1, :L_n], then zeros.
+ *   backward: dx[n,t] = dy[n,t+1] + (mean_cls ? dy[n,0] / L_n : 0) for t < L_n, exact zeros beyond (dx may be NULL);
+ *             dtok [S, d] (may be NULL) = sum over the sequences with t <= L_n of dy[n,t,:] - row 0 is the gradient of a learned
+ *             CLS token, rows 0..S-1 that of the position table; the sequences are added in order (deterministic).
+ * 16-B accesses when d % 4 == 0 and every operand is 16-B aligned, 4-B ones otherwise: the results are the same bits. */
+int lstc_cls_concat_len_fwd(const float* x, const int32_t* lens, const float* cls_token, const float* pos, float* y, int64_t N,
+                            int32_t S, int32_t d, void* stream);
+int lstc_cls_concat_len_bwd(const float* dy, const int32_t* lens, float* dx, float* dtok, int64_t N, int32_t S, int32_t d,
+                            int32_t mean_cls, void* stream);
 
 /* out[c] = sum_r x[r, c] for x [rows, ld] (first `cols` columns); deterministic two-pass reduction.
  * `partial` is caller workspace of n_partial*cols floats.  Bias / LayerNorm / pos-enc gradients. */

@@ -21,10 +21,10 @@ EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 
 EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
-    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_wsum",
+    "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_dot_len", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
-    "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
+    "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_cls_concat_len_fwd", "lstc_cls_concat_len_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
     "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_sqnorm_accum", "lstc_scale",
     "lstc_sqnorm_multi_scratch", "lstc_sqnorm_multi", "lstc_clip_scale_multi",
     "lstc_gather_rows", "lstc_expand_rows", "lstc_cast_f32_bf16", "lstc_cast_bf16_f32", "lstc_pack3", "lstc_pack3_bytes", "lstc_pack1", "lstc_pack1_multi", "lstc_pack1_bytes", "lstc_colsum_pack1", "lstc_gemm_splits",
@@ -129,6 +129,7 @@ def load():
         "lstc_sdpa_fwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_sdpa_bwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_cls_dot": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
+        "lstc_cls_dot_len": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
         "lstc_cls_wsum": [vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_outer": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_dot_pack": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
@@ -147,6 +148,8 @@ def load():
         "lstc_cls_concat_fwd_pack": [vp, vp, i64, vp, vp, vp, i64, i32, i32, vp, vp],
         "lstc_cls_concat_gather_fwd": [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, vp, vp],
         "lstc_cls_concat_bwd": [vp, vp, i64, i32, i32, i32, vp],
+        "lstc_cls_concat_len_fwd": [vp, vp, vp, vp, vp, i64, i32, i32, vp],
+        "lstc_cls_concat_len_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_colsum": [vp, i64, i32, i32, vp, i32, vp, i32, vp],
         "lstc_colsum_batched": [vp, i32, i64, i32, i32, i64, vp, i32, vp, vp],
         "lstc_dropout_apply": [vp, vp, i64, f32, u64, vp],

@@ -1297,13 +1297,16 @@ namespace {
 constexpr int ASSOC_MAXS = 128;
 
 // The per-(sequence, head) rows of dot products `sc` [H][S] (LDS) -> out / probs; modes of cls_dot_kernel.  One wave per head.
+// LEN (lstc_cls_dot_len): only the keys j < kl exist - `sc` holds nothing beyond them, out and probs are exact zeros there.
+template <bool LEN = false>
 __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* __restrict__ probs, int n, int S, int H, int mode,
-                                    const DropKey& dkey, int has_drop, int wave, int lane) {
+                                    const DropKey& dkey, int has_drop, int wave, int lane, int kl = 0) {
+    const int Sv = LEN ? kl : S;          // keys that exist
     for (int h = wave; h < H; h += NT / 64) {
         float* row = sc + h * S;
         float* orow = out + ((size_t)n * H + h) * S;
         if (mode == 0) {
-            for (int j = lane; j < S; j += 64) orow[j] = row[j];
+            for (int j = lane; j < S; j += 64) orow[j] = j < Sv ? row[j] : 0.f;
             continue;
         }
         float* prow = probs + ((size_t)n * H + h) * S;
@@ -1313,14 +1316,14 @@ __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* _
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = lane + 64 * jj;
-                v[jj] = j < S ? row[j] : -INFINITY;
+                v[jj] = j < Sv ? row[j] : -INFINITY;
                 m = fmaxf(m, v[jj]);
             }
             m = wave_max(m);
             float s = 0.f;
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                v[jj] = (lane + 64 * jj < S) ? expf(v[jj] - m) : 0.f;
+                v[jj] = (lane + 64 * jj < Sv) ? expf(v[jj] - m) : 0.f;
                 s += v[jj];
             }
             s = wave_sum(s);
@@ -1340,7 +1343,7 @@ __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* _
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = lane + 64 * jj;
                 pv[jj] = dp[jj] = 0.f;
-                if (j < S) {
+                if (j < Sv) {
                     pv[jj] = prow[j];
                     const float keep = has_drop ? (drop_keep(flat0 + (uint32_t)j, dkey) ? dkey.scale : 0.f) : 1.f;
                     dp[jj] = row[j] * keep;
@@ -1351,7 +1354,7 @@ __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* _
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = lane + 64 * jj;
-                if (j < S) orow[j] = pv[jj] * (dp[jj] - rs);
+                if (j < S) orow[j] = j < Sv ? pv[jj] * (dp[jj] - rs) : 0.f;
             }
         }
     }
@@ -1359,10 +1362,11 @@ __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* _
 
 // mode 0: raw dot products; 1: softmax over j, probs -> `probs`, dropout(probs) -> `out`;
 // mode 2: `out` = P * (dP - sum_j dP P), dP = dot * keep  (softmax + dropout backward; `probs` is an input)
-template <int HT>
+// LEN: sequence n has klen[n] keys (clamped to [1, S]); the rows X[n, j >= klen[n]] are never read.
+template <int HT, bool LEN = false>
 __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U, const float* __restrict__ X,
                                                       float* __restrict__ out, float* __restrict__ probs, int S, int H, int d,
-                                                      int mode, DropKey dkey, int has_drop) {
+                                                      int mode, DropKey dkey, int has_drop, const int32_t* __restrict__ klen) {
     dkey = drop_key_now(dkey);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ul = sm;                   // [H][d]
@@ -1371,14 +1375,15 @@ __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U
     const float* Un = U + (size_t)n * H * d;
     const float* Xn = X + (size_t)n * S * d;
     const int d4 = d >> 2;
+    const int Sv = LEN ? min(max((int)klen[n], 1), S) : S;          // rows of X that exist
     for (int i = threadIdx.x; i < H * d4; i += NT) reinterpret_cast<float4*>(Ul)[i] = reinterpret_cast<const float4*>(Un)[i];
     __syncthreads();
     // a wave takes two rows at a time and requests all of their float4 pieces (up to 16 KB in flight per wave) before the first
     // product: the kernel is a stream over X, and the head vectors read from LDS serve both rows
     constexpr int XC = 8, NW = NT / 64;
-    for (int j = wave; j < S; j += 2 * NW) {
+    for (int j = wave; j < Sv; j += 2 * NW) {
         const int j1 = j + NW;
-        const bool two = j1 < S;
+        const bool two = j1 < Sv;
         const float4* x0p = reinterpret_cast<const float4*>(Xn + (size_t)j * d);
         const float4* x1p = reinterpret_cast<const float4*>(Xn + (size_t)(two ? j1 : j) * d);
         float part0[HT], part1[HT];
@@ -1417,7 +1422,7 @@ __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U
             }
     }
     __syncthreads();
-    cls_dot_tail(sc, out, probs, n, S, H, mode, dkey, has_drop, wave, lane);
+    cls_dot_tail<LEN>(sc, out, probs, n, S, H, mode, dkey, has_drop, wave, lane, Sv);
 }
 
 template <int HT>
@@ -1774,10 +1779,32 @@ int lstc_cls_dot(const float* U, const float* X, float* out, float* probs, int64
     const int has_drop = dropout_p > 0.f;
     const dim3 grid((unsigned)N);
     hipStream_t st = (hipStream_t)stream;
-    if (H <= 2) launch_big_lds<cls_dot_kernel<2>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
-    else if (H <= 4) launch_big_lds<cls_dot_kernel<4>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
-    else if (H <= 8) launch_big_lds<cls_dot_kernel<8>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
-    else launch_big_lds<cls_dot_kernel<16>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop);
+    if (H <= 2) launch_big_lds<cls_dot_kernel<2>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
+    else if (H <= 4) launch_big_lds<cls_dot_kernel<4>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
+    else if (H <= 8) launch_big_lds<cls_dot_kernel<8>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
+    else launch_big_lds<cls_dot_kernel<16>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
+    return lstc_launch_status();
+}
+
+int lstc_cls_dot_len(const float* U, const float* X, const int32_t* klen, float* out, float* probs, int64_t N, int32_t S, int32_t H,
+                     int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream) {
+    int rc = assoc_check(U, X, out, N, S, H, d);
+    if (rc) return rc;
+    if (!klen) return LSTC_E_NULL;
+    if (S < 2) return LSTC_E_SHAPE;
+    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
+    if (mode != 0 && !probs) return LSTC_E_NULL;
+    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
+    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
+    if (lds > 96 * 1024) return LSTC_E_RANGE;
+    const DropKey dk = make_drop_key(dropout_p, seed);
+    const int has_drop = dropout_p > 0.f;
+    const dim3 grid((unsigned)N);
+    hipStream_t st = (hipStream_t)stream;
+    if (H <= 2) launch_big_lds<cls_dot_kernel<2, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
+    else if (H <= 4) launch_big_lds<cls_dot_kernel<4, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
+    else if (H <= 8) launch_big_lds<cls_dot_kernel<8, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
+    else launch_big_lds<cls_dot_kernel<16, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
     return lstc_launch_status();
 }
 

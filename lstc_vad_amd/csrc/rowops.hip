@@ -667,6 +667,72 @@ __global__ void __launch_bounds__(NT) cls_concat_bwd_kernel(const float* __restr
     for (int t = 0; t < S - 1; ++t) xr[(int64_t)t * d] = dr[(int64_t)(t + 1) * d] + g0;
 }
 
+// ------------------------------------------------------------------------------ CLS concat of padded batches (per-sequence lengths)
+// Sequence n has lens[n] real tokens (clamped to [1, S-1]); the rest of its row of x is padding that is never read.  One kernel text
+// for the 4-B (V = float) and the 16-B (V = float4: d % 4 == 0, aligned operands) access pattern; `dv` counts V's per row.  A column's
+// arithmetic is a sequential walk over the tokens in both, so the two paths give the same bits.
+__device__ inline int concat_len(const int32_t* __restrict__ lens, int64_t n, int S) { return min(max((int)lens[n], 1), S - 1); }
+__device__ inline float vzero(float) { return 0.f; }
+__device__ inline float4 vzero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ inline float vadd(float a, float b) { return a + b; }
+__device__ inline float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ inline float vdiv(float a, float r) { return a / r; }
+__device__ inline float4 vdiv(const float4& a, float r) { return make_float4(a.x / r, a.y / r, a.z / r, a.w / r); }
+
+// grid (N, ceil(dv/NT)).  y[n,0] = cls or mean(x[n,:L]); y[n,1+t] = x[n,t] for t < L; pos on rows 0..L; rows > L exact zeros.
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_len_fwd_kernel(const V* __restrict__ x, const int32_t* __restrict__ lens,
+                                                                 const V* __restrict__ cls, const V* __restrict__ pos,
+                                                                 V* __restrict__ y, int S, int dv) {
+    const int64_t n = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    const int L = concat_len(lens, n, S);
+    const V* xr = x + n * (int64_t)(S - 1) * dv + c;
+    V* yr = y + n * (int64_t)S * dv + c;
+    V s = vzero(V{});
+#pragma unroll 8
+    for (int t = 0; t < L; ++t) {
+        const V v = xr[(int64_t)t * dv];
+        s = vadd(s, v);
+        yr[(int64_t)(t + 1) * dv] = pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v;
+    }
+    for (int t = L; t < S - 1; ++t) yr[(int64_t)(t + 1) * dv] = vzero(V{});
+    V cv = cls ? cls[c] : vdiv(s, (float)L);
+    if (pos) cv = vadd(cv, pos[c]);
+    yr[0] = cv;
+}
+
+// dx[n,t] = dy[n,t+1] + (mean_cls ? dy[n,0] / L : 0) for t < L, exact zeros beyond.
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_len_bwd_kernel(const V* __restrict__ dy, const int32_t* __restrict__ lens,
+                                                                 V* __restrict__ dx, int S, int dv, int mean_cls) {
+    const int64_t n = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    const int L = concat_len(lens, n, S);
+    const V* dr = dy + n * (int64_t)S * dv + c;
+    V* xr = dx + n * (int64_t)(S - 1) * dv + c;
+    const V g0 = mean_cls ? vdiv(dr[0], (float)L) : vzero(V{});
+#pragma unroll 8
+    for (int t = 0; t < L; ++t) xr[(int64_t)t * dv] = vadd(dr[(int64_t)(t + 1) * dv], g0);
+    for (int t = L; t < S - 1; ++t) xr[(int64_t)t * dv] = vzero(V{});
+}
+
+// dtok[t, :] = sum over the sequences with t <= L_n of dy[n, t, :] (the gradient of a learned CLS token: row 0, and of the position
+// table: rows 0..S-1).  grid (S, ceil(dv/NT)); the sequences are walked in order, so the sum is deterministic.
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_len_dtok_kernel(const V* __restrict__ dy, const int32_t* __restrict__ lens,
+                                                                  V* __restrict__ dtok, int64_t N, int S, int dv) {
+    const int t = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    V s = vzero(V{});
+    for (int64_t n = 0; n < N; ++n)
+        if (t <= concat_len(lens, n, S)) s = vadd(s, dy[(n * S + t) * (int64_t)dv + c]);
+    dtok[(int64_t)t * dv + c] = s;
+}
+
 // ---------------------------------------------------------------------------------- colsum
 // pass 1: grid (ceil(cols/NT), n_partial): workgroup y sums rows y, y+n_partial, ... of NT columns.
 // (blockIdx.z = plane of a batched call, lstc_colsum_batched: planes are `xstride` / n_partial * cols floats apart)
@@ -1355,6 +1421,41 @@ int lstc_cls_concat_bwd(const float* dy, float* dx, int64_t N, int32_t S, int32_
     if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
     hipLaunchKernelGGL(cls_concat_bwd_kernel, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, (hipStream_t)stream, dy, dx,
                        S, d, mean_cls);
+    return lstc_launch_status();
+}
+
+int lstc_cls_concat_len_fwd(const float* x, const int32_t* lens, const float* cls_token, const float* pos, float* y, int64_t N,
+                            int32_t S, int32_t d, void* stream) {
+    if (!x || !lens || !y) return LSTC_E_NULL;
+    if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (d % 4 == 0 && aligned16(x) && aligned16(y) && (!cls_token || aligned16(cls_token)) && (!pos || aligned16(pos)))
+        hipLaunchKernelGGL(cls_concat_len_fwd_kernel<float4>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, st, (const float4*)x, lens,
+                           (const float4*)cls_token, (const float4*)pos, (float4*)y, S, d / 4);
+    else
+        hipLaunchKernelGGL(cls_concat_len_fwd_kernel<float>, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, st, x, lens, cls_token, pos, y,
+                           S, d);
+    return lstc_launch_status();
+}
+
+int lstc_cls_concat_len_bwd(const float* dy, const int32_t* lens, float* dx, float* dtok, int64_t N, int32_t S, int32_t d,
+                            int32_t mean_cls, void* stream) {
+    if (!dy || !lens || (!dx && !dtok)) return LSTC_E_NULL;
+    if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const bool v4 = d % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(dtok);
+    const int dv = v4 ? d / 4 : d;
+    const unsigned gy = (unsigned)((dv + NT - 1) / NT);
+    if (dx) {
+        if (v4) hipLaunchKernelGGL(cls_concat_len_bwd_kernel<float4>, dim3((unsigned)N, gy), NT, 0, st, (const float4*)dy, lens, (float4*)dx,
+                                   S, dv, mean_cls);
+        else hipLaunchKernelGGL(cls_concat_len_bwd_kernel<float>, dim3((unsigned)N, gy), NT, 0, st, dy, lens, dx, S, dv, mean_cls);
+    }
+    if (dtok) {
+        if (v4) hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float4>, dim3((unsigned)S, gy), NT, 0, st, (const float4*)dy, lens,
+                                   (float4*)dtok, N, S, dv);
+        else hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float>, dim3((unsigned)S, gy), NT, 0, st, dy, lens, dtok, N, S, dv);
+    }
     return lstc_launch_status();
 }
 

@@ -1707,6 +1707,20 @@ def cls_dot(u, x3, mode, probs=None, p_drop=0.0, seed=0):
     return out, probs
 
 
+def cls_dot_len(u, x3, klen, mode, probs=None, p_drop=0.0, seed=0):
+    """``cls_dot`` on a padded batch (lstc_cls_dot_len): ``klen`` int32 [N] on the device, keys per sequence with the CLS token."""
+    N, S, dm = x3.shape
+    H = u.shape[1]
+    if klen.dtype != torch.int32 or klen.numel() != N or not klen.is_contiguous():
+        raise ValueError("cls_dot_len: klen must be a contiguous int32 tensor of N entries")
+    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+    if mode == 1:
+        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+    check(_lib.load().lstc_cls_dot_len(dev_ptr(u), dev_ptr(x3), dev_ptr(klen), dev_ptr(out), dev_ptr(probs), N, S, H, dm, mode,
+                                       float(p_drop), int(seed), stream_ptr()), "lstc_cls_dot_len")
+    return out, probs
+
+
 def cls_wsum(w, x3):
     N, S, dm = x3.shape
     H = w.shape[1]
@@ -1770,7 +1784,10 @@ class MHAClsAssocFunction(torch.autograd.Function):
         xb[n,h] = sum_j Pd[n,h,j] x[n,j]            o[n,h]       = Wv_h xb[n,h]           (no V = X Wv^T GEMM)
     Exactly models/MultiHeadAttention.py:93-126 for query row 0 — same values up to float re-association — but the two
     [N*S, d] x [d, H*dk] projections and their four backward GEMMs (5 of the 43 TFLOP of an LTN step) become per-head
-    [N, dk] x [dk, d] products (one batched launch each) plus three passes over X."""
+    [N, dk] x [dk, d] products (one batched launch each) plus three passes over X.
+    ``cfg["key_lengths"]`` (int32 [N] on the device: keys per sequence, the CLS token counted) makes the batch a padded one: the
+    softmax runs over each sequence's own keys (lstc_cls_dot_len, which never reads the rows beyond them); the weighted sum and
+    the outer product see zero weights there, so the input gradient of a padded row is zero."""
 
     @staticmethod
     @_small_m_fwd
@@ -1803,7 +1820,13 @@ class MHAClsAssocFunction(torch.autograd.Function):
             _note(cfg["site"] + "attn_dropout#cls", p_attn, seed_a, (N, H, S, S))
         if p_fc > 0:
             _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
-        if xp is None:
+        klen = cfg.get("key_lengths")
+        if klen is not None:
+            if xp is not None:
+                raise RuntimeError("MHAClsAssocFunction: key lengths need the f32 activations")
+            pd, probs = cls_dot_len(u, x, klen, 1, None, p_attn, seed_a)
+            xb = cls_wsum(pd, x)
+        elif xp is None:
             pd, probs = cls_dot(u, x, 1, None, p_attn, seed_a)                            # dropped probs, probs
             xb = cls_wsum(pd, x)                                                          # [N, H, d]
         else:
@@ -1844,7 +1867,10 @@ class MHAClsAssocFunction(torch.autograd.Function):
         dwv = grad_sink(wv)
         dwv = torch.empty_like(wv) if dwv is None else dwv
         gemm_batched(doc, xb, dwv, dv, dm, N, H * dv, H * dm, dm, True, False, H, dv, dm, dv * dm)
-        if xp is None:
+        if c.get("key_lengths") is not None:
+            ds, _ = cls_dot_len(dxb, x, c["key_lengths"], 2, probs, c["p_attn"], c["seed_a"])
+            du = cls_wsum(ds, x)
+        elif xp is None:
             ds, _ = cls_dot(dxb, x, 2, probs, c["p_attn"], c["seed_a"])                   # d(logit) [N,H,S]
             du = cls_wsum(ds, x)                                                          # [N, H, d]
         else:
@@ -2215,6 +2241,75 @@ class ClsConcatFunction(torch.autograd.Function):
                 dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
                 dpos[0, :S] = tok.view(S, dm)
         return dx, dcls, dpos, None, None, None
+
+
+class ClsConcatLenFunction(torch.autograd.Function):
+    """``ClsConcatFunction`` for a padded batch: ``lens`` (int32 [N] on the device) real tokens per sequence.  The CLS token is the
+    mean over a sequence's own tokens, the rows past them come out as exact zeros and the padding of ``x`` is never read
+    (lstc_cls_concat_len_fwd / _bwd); its input gradient is zero."""
+
+    @staticmethod
+    def forward(ctx, x, cls_token, pos, lens):
+        N, Sm1, dm = x.shape
+        S = Sm1 + 1
+        if lens.dtype != torch.int32 or lens.numel() != N or not lens.is_contiguous():
+            raise ValueError("ClsConcatLenFunction: lens must be a contiguous int32 tensor of N entries")
+        x = x.contiguous()
+        y = torch.empty((N, S, dm), device=x.device, dtype=torch.float32)
+        pos_s = pos[0, :S].contiguous() if pos is not None else None
+        cls_v = cls_token.reshape(-1) if cls_token is not None else None
+        check(_lib.load().lstc_cls_concat_len_fwd(dev_ptr(x), dev_ptr(lens), dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y), N, S, dm,
+                                                  stream_ptr()), "lstc_cls_concat_len_fwd")
+        ctx.lens = lens
+        ctx.meta = (N, S, dm, cls_token is not None, pos.shape if pos is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, S, dm, learned, pos_shape = ctx.meta
+        dy = dy.contiguous()
+        dx = dcls = dpos = tok = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((N, S - 1, dm), device=dy.device, dtype=torch.float32)
+        if learned or pos_shape is not None:
+            tok = torch.empty((S, dm), device=dy.device, dtype=torch.float32)
+        if dx is not None or tok is not None:
+            check(_lib.load().lstc_cls_concat_len_bwd(dev_ptr(dy), dev_ptr(ctx.lens), dev_ptr(dx), dev_ptr(tok), N, S, dm,
+                                                      int(not learned), stream_ptr()), "lstc_cls_concat_len_bwd")
+        if learned:
+            dcls = tok[0].clone().view(1, 1, dm)
+        if pos_shape is not None:
+            dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
+            dpos[0, :S] = tok
+        return dx, dcls, dpos, None
+
+
+def lengths_arg(lengths, N, S, device):
+    """Normalise the ``lengths`` of a padded batch of N sequences with S - 1 token slots: a Python sequence or a CPU tensor is
+    range-checked here (ValueError; 1 <= L <= S - 1) and copied to ``device``; a device tensor is taken as it is, without a host
+    sync and clamped to [1, S - 1] (as the kernels clamp it again).  Returns (int32 [N] on ``device``, the lengths as a list or None for a device
+    tensor).  Pure torch; the checks run before anything touches the device."""
+    host = None
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.numel() != N:
+            raise ValueError(f"lengths: expected {N} entries (one per sequence), got shape {tuple(lengths.shape)}")
+        if lengths.is_floating_point() or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths: expected integers, got {lengths.dtype}")
+        if not lengths.is_cuda:
+            host = [int(v) for v in lengths.tolist()]
+    else:
+        host = list(lengths)
+        if len(host) != N:
+            raise ValueError(f"lengths: expected {N} entries (one per sequence), got {len(host)}")
+        if any(isinstance(v, bool) or int(v) != v for v in host):
+            raise ValueError("lengths: expected integers")
+        host = [int(v) for v in host]
+    if host is None:
+        return lengths.to(device=device, dtype=torch.int32).clamp(1, S - 1).contiguous(), None
+    bad = [(n, v) for n, v in enumerate(host) if not 1 <= v <= S - 1]
+    if bad:
+        raise ValueError(f"lengths: every sequence needs 1 <= length <= {S - 1} (its token slots); got length {bad[0][1]} for sequence {bad[0][0]}")
+    return torch.tensor(host, dtype=torch.int32).to(device), host
 
 
 def _cls_concat_gather(ctx, bank, cls_token, pos, pack_only, gather):

@@ -2,8 +2,10 @@
 import torch
 from torch import nn
 
-from ..functional import ClsConcatFunction, DropoutFunction, LayerNormFunction, PackedAct, act_chain_ok, drop_producer_packs
+from ..functional import (ClsConcatFunction, ClsConcatLenFunction, DropoutFunction, LayerNormFunction, PackedAct, act_chain_ok,
+                          drop_producer_packs, lengths_arg)
 from .EncoderLayer import EncoderLayer
+from .MultiHeadAttention import key_padding_mask
 
 
 class Encoder(nn.Module):
@@ -112,11 +114,62 @@ class Encoder(nn.Module):
             enc_output = DropoutFunction.apply(enc_output, self.position_dropout.p, "position_dropout")
         return enc_output
 
-    def forward_cls(self, enc_output, enc_output_hi=None, src_mask=None):
+    def _lengths(self, enc_output, enc_output_hi, lengths):
+        """A padded batch: refuse what does not take lengths, check them -> (lens int32 [N] on the input's device, kept-keys mask
+        [N, 1, 1, S]).  Every refusal is raised before any launch (and before the input's device matters)."""
+        if isinstance(enc_output, PackedAct):
+            raise NotImplementedError("Encoder: lengths need f32 activations (no PackedAct input)")
+        if isinstance(enc_output, tuple):
+            raise ValueError("Encoder: a gather spec cannot carry lengths (materialise the padded batch first)")
+        if enc_output_hi is not None:
+            raise ValueError("Encoder: lengths describe one padded batch: concatenate enc_output and enc_output_hi first")
+        if enc_output.dim() != 3:
+            raise ValueError(f"Encoder: lengths need a padded batch [N, S - 1, d_model], got {tuple(enc_output.shape)}")
+        N, S = enc_output.shape[0], enc_output.shape[1] + 1
+        lens, host = lengths_arg(lengths, N, S, enc_output.device)
+        attn0 = self.layer_stack[0].slf_attn
+        if attn0.relative_pe_2D:
+            # the 2-D bias needs exactly window_size**2 patch tokens per sequence: only a batch without padding qualifies
+            if host is None or any(v != attn0.window_size ** 2 for v in host):
+                raise ValueError("Encoder: relative_pe_2D needs window_size**2 patch tokens in every sequence - lengths must be given "
+                                 f"on the host and all equal {attn0.window_size ** 2}")
+        if not enc_output.is_cuda:
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        return lens, key_padding_mask(lens + 1, S)
+
+    def _embed_len(self, enc_output, lens, kept):
+        """``_embed`` of a padded batch: the input LayerNorm sees the padding as zeros (its rows come out as beta and the concat drops
+        them), the CLS concat reads the real tokens only and leaves exact zeros behind them."""
+        if self.input_layerNorm:
+            enc_output = torch.where(kept[:, 0, 0, 1:, None], enc_output, enc_output.new_zeros(()))
+            enc_output = LayerNormFunction.apply(enc_output, self.layer_norm.weight, self.layer_norm.bias)
+        enc_output = ClsConcatLenFunction.apply(enc_output, self.cls_token if self.CLS_learned else None,
+                                                self.position_enc if self.position_encoding else None, lens)
+        if self.position_encoding and self.training and self.position_dropout.p > 0:
+            enc_output = DropoutFunction.apply(enc_output, self.position_dropout.p, "position_dropout")
+        return enc_output
+
+    def _forward_cls_len(self, enc_output, src_mask, lens, kept):
+        enc_output = self._embed_len(enc_output, lens, kept)
+        mask = kept if src_mask is None else key_padding_mask(lens + 1, enc_output.shape[1], src_mask)
+        n = len(self.layer_stack)
+        for i, layer in enumerate(self.layer_stack[:-1]):
+            layer.pos_ffn._emit_pack = i + 1 < n - 1
+            layer.slf_attn._act16_out = layer.pos_ffn._act16_out = False
+            enc_output = layer(enc_output, slf_attn_mask=mask)[0]
+        out = self.layer_stack[-1].forward_cls(enc_output, slf_attn_mask=src_mask, key_lengths=lens + 1)
+        drop_producer_packs()
+        return out
+
+    def forward_cls(self, enc_output, enc_output_hi=None, src_mask=None, lengths=None):
         """``forward(x, src_mask)[:, 0, :]`` without computing the rows nobody reads: the train / eval loops consume only the
         CLS token of the last layer (Train/temporal_transformer_shanghaitech.py:123,
         Train/spatio_transformer_shanghaitech.py:97), so the last layer evaluates its query, output projection and
-        FFN for that token alone (K/V still use every token).  Saves ~25 % of the step's FLOPs at 3 layers."""
+        FFN for that token alone (K/V still use every token).  Saves ~25 % of the step's FLOPs at 3 layers.
+        ``lengths``: a padded batch, as in ``forward``; row n is what ``forward_cls(x[n:n+1, :lengths[n]])`` returns."""
+        if lengths is not None:
+            lens, kept = self._lengths(enc_output, enc_output_hi, lengths)
+            return self._forward_cls_len(enc_output, src_mask, lens, kept)
         # enc_output_hi: optional second half of the batch (the abnormal sequences) so the caller need not cat
         # src_mask: the full layers get the mask, the CLS-only last layer its query row 0; the bf16 activation stream stays off
         n = len(self.layer_stack)
@@ -134,10 +187,27 @@ class Encoder(nn.Module):
         drop_producer_packs()
         return out
 
-    def forward(self, enc_output, src_mask=None, return_attn=False, return_attn_v=False):
+    def forward(self, enc_output, src_mask=None, return_attn=False, return_attn_v=False, lengths=None):
+        """``lengths`` (a Python sequence, a CPU tensor or a device tensor of N integers) makes ``enc_output`` [N, S - 1, d_model] a
+        PADDED batch: sequence n has ``lengths[n]`` real patch tokens ``x[n, :lengths[n]]`` (1 <= lengths[n] <= S - 1, the CLS token
+        not counted) and the rest of its row is padding that is never read (it may hold NaN).  Rows 0..lengths[n] of the result
+        are what ``forward(x[n:n+1, :lengths[n]])`` returns, in ``eval()`` and in training with every dropout rate 0; the rows past
+        them are finite and otherwise unspecified, the returned probabilities of padded keys are 0 and the input gradient of the
+        padding is 0.  With dropout on, element (n, h, i, j) of an attention mask keeps its counter over the padded S (and the
+        other sites theirs over the padded rows): a valid draw, but not the draw the sequence would have got alone.
+        Lengths on the host are range-checked (ValueError) before any launch; a device tensor costs no host sync and is clamped
+        to [1, S - 1] by the kernels.  ``src_mask`` is and-ed with the key padding.  Refused: a gather spec, a PackedAct input,
+        ``relative_pe_2D`` unless every length is window_size**2.  The bf16 activation stream is off, as with a mask."""
         attn_list, v_list = [], []
-        act = not return_attn_v and src_mask is None and self._act_chain(enc_output, None, list(self.layer_stack))
-        enc_output = self._embed(enc_output, None, pack_only=act)
+        if lengths is not None:
+            lens, kept = self._lengths(enc_output, None, lengths)
+            enc_output = self._embed_len(enc_output, lens, kept)
+            if src_mask is not None:
+                kept = key_padding_mask(lens + 1, enc_output.shape[1], src_mask)
+            src_mask, act = kept, False
+        else:
+            act = not return_attn_v and src_mask is None and self._act_chain(enc_output, None, list(self.layer_stack))
+            enc_output = self._embed(enc_output, None, pack_only=act)
         for i, layer in enumerate(self.layer_stack):
             layer.pos_ffn._emit_pack = i + 1 < len(self.layer_stack)      # the last layer's output goes to the caller
             layer.slf_attn._act16_out, layer.pos_ffn._act16_out = act, act and i + 1 < len(self.layer_stack)

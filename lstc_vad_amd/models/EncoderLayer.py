@@ -25,8 +25,12 @@ class EncoderLayer(nn.Module):
         enc_output = self.pos_ffn(res[0]) if self.FFN_need else res[0]
         return (enc_output,) + tuple(res[1:])
 
-    def forward_cls(self, enc_input, slf_attn_mask=None):
+    def forward_cls(self, enc_input, slf_attn_mask=None, key_lengths=None):
         """Last-layer shortcut: returns only the CLS row [N, d]; attention output projection and FFN run on N rows
-        instead of N*S (the rest of the layer's output is never read by the train loops)."""
-        out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask)
+        instead of N*S (the rest of the layer's output is never read by the train loops).  ``key_lengths``: a padded batch
+        (MultiHeadAttention.forward_cls)."""
+        if key_lengths is None:
+            out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask)
+        else:
+            out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask, key_lengths=key_lengths)
         return self.pos_ffn(out) if self.FFN_need else out

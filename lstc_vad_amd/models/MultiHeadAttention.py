@@ -24,6 +24,17 @@ def relative_position_index_3d(window_depth: int, window_size: int) -> torch.Ten
     return ((dd + window_depth - 1) * span * span + (dh + window_size - 1) * span + (dw + window_size - 1)).long()
 
 
+def key_padding_mask(key_lengths, S, mask=None):
+    """bool [N, 1, 1, S]: key j of sequence n is kept while j < key_lengths[n] (clamped to [1, S]); and-ed with ``mask`` (anything
+    that broadcasts against [N, H, S, S], zero = masked) when one is given.  Plain torch on the tensor's own device, no host sync."""
+    kl = key_lengths.to(torch.int64).clamp(1, S)
+    m = (torch.arange(S, device=kl.device)[None, :] < kl[:, None]).view(-1, 1, 1, S)
+    if mask is None:
+        return m
+    mask = (mask != 0).to(kl.device)
+    return m & mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+
+
 def relative_position_index_2d(window_size: int) -> torch.Tensor:
     """2-D variant (:79-89): entry = (dh+ws-1)(2ws-1) + (dw+ws-1)."""
     t = torch.arange(window_size * window_size)
@@ -119,13 +130,27 @@ class MultiHeadAttention(nn.Module):
         from ..functional import cls_pack_ok
         return self._cls_assoc_ok(S) and cls_pack_ok(N, S, self.n_head, self.d_model)
 
-    def forward_cls(self, x, mask=None):
+    def forward_cls(self, x, mask=None, key_lengths=None):
         """CLS-query attention for the last encoder layer: x [N, S, d] -> [N, d] (== ``forward(x, x, x, mask)[0][:, 0]``).
-        ``mask`` as in ``forward``; only its query row 0 is read."""
+        ``mask`` as in ``forward``; only its query row 0 is read.
+        ``key_lengths``: int32 [N] on the device, the keys of each sequence of a padded batch (the CLS token counted, 1..S; the
+        kernels clamp): keys beyond them do not exist.  Alone, and where the re-associated form applies (``_cls_assoc_ok``), it
+        runs that form with lstc_cls_dot_len - no K / V projection of the padded batch; with a ``mask`` as well, or S > 128, the
+        K/V-projecting form takes the key-padding mask of the lengths, and-ed with ``mask``."""
         cfg = dict(n_head=self.n_head, d_k=self.d_k, d_v=self.d_v, layer_norm=self.layerNorm_flag,
                    attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
                    site=self._site)
-        if mask is not None:
+        if key_lengths is not None:
+            if isinstance(x, PackedAct):
+                raise NotImplementedError("key lengths need the f32 activations (Encoder keeps the bf16 stream off when lengths are given)")
+            if mask is None and self._cls_assoc_ok(x.shape[1]):
+                cfg.update(key_lengths=key_lengths)
+                fn = MHAClsAssocFunction
+            else:
+                cfg.update(mask=attn_mask_arg(key_padding_mask(key_lengths, x.shape[1], mask), x.shape[0], self.n_head, x.shape[1],
+                                              device=x.device))
+                fn = MHAClsFunction
+        elif mask is not None:
             # the re-associated form does its softmax inside lstc_cls_dot and stays unmasked: the K/V-projecting form takes the mask
             if isinstance(x, PackedAct):
                 raise NotImplementedError("an attention mask needs the f32 activations (Encoder keeps the bf16 stream off when one is given)")

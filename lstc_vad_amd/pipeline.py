@@ -65,8 +65,8 @@ class _ScoreBoard:
     rank``) also hands over the work (sequences to pool, or a closure that scores the clips).  ``results()`` scores what is
     owned, sums the zero-padded flat vector over the ranks and runs every video's ``finish`` on every rank."""
 
-    def __init__(self, enc, head, device, rank, world, group, pool_sequences, exchange=None):
-        self.enc, self.head, self.device = enc, head, device
+    def __init__(self, enc, head, device, rank, world, group, pool_sequences, exchange=None, ragged=False):
+        self.enc, self.head, self.device, self.ragged = enc, head, device, ragged
         self.rank, self.world, self.group, self.exchange = rank, world, group, exchange
         self.pool_sequences = pool_sequences
         self.items, self.total = [], 0             # (offset, count, finish) in list order
@@ -104,7 +104,8 @@ class _ScoreBoard:
     def flush(self):
         if not self.pool:
             return
-        sc = scoring.ltn_sequence_scores(self.enc, self.head, [q for _, seqs in self.pool for q in seqs])
+        sc = scoring.ltn_sequence_scores(self.enc, self.head, [q for _, seqs in self.pool for q in seqs],
+                                         **({"ragged": True} if self.ragged else {}))
         o = 0
         for off, seqs in self.pool:
             self.parts.append((off, sc[o:o + len(seqs)]))
@@ -135,13 +136,14 @@ def _threshold(scores_np, threshold):
 @torch.no_grad()
 def generate_pseudo_labels(enc, head, mode, dataset, dataset_path, training_txt, threshold, part_len=1, n_patch=16,
                            d_model=None, segment_len=16, classifier_head=False, out_path=None, pool_sequences=2048,
-                           rank=None, world=None, group=None, exchange=None):
+                           rank=None, world=None, group=None, exchange=None, ragged=False):
     """mode 'STN' | 'LTN'; dataset 'SHT' | 'UCF' | 'UBnormal'.  Returns the dict (and writes it when ``out_path`` - on rank 0
-    only under several ranks; every rank returns the complete dict)."""
+    only under several ranks; every rank returns the complete dict).  ``ragged``: the pooled LTN parts of all lengths (the short
+    tail parts of ``tail='short'``) share padded batches (scoring.ltn_sequence_scores)."""
     device = next(enc.parameters()).device
     d_model = d_model or enc.layer_norm.normalized_shape[0]
     rank, world = _ranks(rank, world, group)
-    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange)
+    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged)
     keys = []
 
     with FeatureArchive(dataset_path) as arc:
@@ -182,13 +184,14 @@ def _auc_of(rows, return_frames):
 
 @torch.no_grad()
 def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, part_len, n_patch, segment_len=16,
-                 return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None):
+                 return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, ragged=False):
     """``masks``: directory of ``<video>.npy`` frame masks (SHT / UBnormal, ``--test_mask_dir``) or the ground-truth
     archive (UCF, ``--test_mask_path``).  LTN only scores parts; STN scores clips (in-loop evaluation of the spatio
-    scripts, Train/spatio_transformer_shanghaitech.py:118-150: every clip's score x segment_len)."""
+    scripts, Train/spatio_transformer_shanghaitech.py:118-150: every clip's score x segment_len).  ``ragged``: pooled LTN
+    parts of all lengths share padded batches (scoring.ltn_sequence_scores)."""
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
-    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange)
+    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged)
 
     def stn_finish(anno):
         def fin(v):

@@ -31,11 +31,36 @@ def part_ranges(n: int, part_len: int):
     return [(i * part_len, n if i == n_parts - 1 else (i + 1) * part_len) for i in range(n_parts)]
 
 
-def ltn_sequence_scores(enc, head, seqs, max_batch=4096):
+def ragged_batches(seqs, max_batch=4096):
+    """The batches of ``ltn_sequence_scores(ragged=True)``: consecutive chunks of up to ``max_batch`` sequences of ANY lengths, each
+    padded to the longest sequence of the whole call -> [(ids, x [n, T_max, d], lengths)] with ``ids`` the positions in ``seqs``
+    (input order), ``x[k, :lengths[k]] = seqs[ids[k]]`` and zeros behind (the content of the padding is free: the encoder never
+    reads it).  Pure torch; runs on CPU tensors."""
+    t_max = max(s.shape[0] for s in seqs)
+    d = seqs[0].shape[1]
+    batches = []
+    for c in range(0, len(seqs), max_batch):
+        ids = list(range(c, min(c + max_batch, len(seqs))))
+        x = seqs[0].new_zeros((len(ids), t_max, d))
+        lengths = [int(seqs[i].shape[0]) for i in ids]
+        for k, i in enumerate(ids):
+            x[k, :lengths[k]] = seqs[i]
+        batches.append((ids, x, lengths))
+    return batches
+
+
+def ltn_sequence_scores(enc, head, seqs, max_batch=4096, ragged=False):
     """seqs: list of [len_i * P, d] tensors (any mix of videos) -> tensor [len(seqs)] of P(abnormal).  Same-length
     sequences share a batch of up to ``max_batch`` rows, so a whole test set is scored in a handful of launch sequences
-    that fill the GPU like a training step does."""
+    that fill the GPU like a training step does.
+    ``ragged``: sequences of ALL lengths share batches instead - padded to the longest of the call and scored through
+    ``Encoder.forward_cls(x, lengths=...)``, one launch chain per ``max_batch`` sequences rather than one per distinct length;
+    every score is what the sequence gets alone (up to float re-association), in input order."""
     out = torch.empty(len(seqs), device=seqs[0].device, dtype=torch.float32)
+    if ragged:
+        for ids, x, lengths in ragged_batches(seqs, max_batch):
+            out[ids[0]:ids[-1] + 1] = head(enc.forward_cls(x, lengths=lengths)).view(-1, 2)[:, 1]
+        return out
     by_len = {}
     for i, s in enumerate(seqs):
         by_len.setdefault(s.shape[0], []).append(i)
@@ -71,10 +96,10 @@ def ltn_part_sequences(feats, part_len, tail="rewindow"):
     return seqs, ranges
 
 
-def ltn_part_scores(enc, head, feats, part_len, tail="rewindow"):
-    """feats [n_clips, P, d] -> (scores [n_parts], [(beg, end)])."""
+def ltn_part_scores(enc, head, feats, part_len, tail="rewindow", ragged=False):
+    """feats [n_clips, P, d] -> (scores [n_parts], [(beg, end)]).  ``ragged``: as in ``ltn_sequence_scores``."""
     seqs, ranges = ltn_part_sequences(feats, part_len, tail)
-    return ltn_sequence_scores(enc, head, seqs), ranges
+    return ltn_sequence_scores(enc, head, seqs, ragged=ragged), ranges
 
 
 def ucf_bins(feats, n_frames, segment_len=16, max_clips=32):
@@ -116,9 +141,10 @@ def ltn_ucf_bin_sequences(feats, n_frames, part_len, segment_len=16, normalize=T
     return seqs, ranges, r
 
 
-def ltn_ucf_bin_scores(enc, head, feats, n_frames, part_len, segment_len=16, normalize=True, rewindow=True, max_clips=32):
+def ltn_ucf_bin_scores(enc, head, feats, n_frames, part_len, segment_len=16, normalize=True, rewindow=True, max_clips=32,
+                       ragged=False):
     seqs, ranges, r = ltn_ucf_bin_sequences(feats, n_frames, part_len, segment_len, normalize, rewindow, max_clips)
-    return ltn_sequence_scores(enc, head, seqs), ranges, r
+    return ltn_sequence_scores(enc, head, seqs, ragged=ragged), ranges, r
 
 
 def frame_scores_sht(scores, ranges, anno, segment_len=16):
