@@ -294,6 +294,35 @@ int lstc_attn_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* str
 int lstc_attn_cls_fwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);   /* query row 0: sq is ignored */
 int lstc_attn_cls_bwd_masked(const LstcAttnDesc* d, const LstcAttnMask* m, void* stream);
 
+/* Attention over sequence offsets: an UNPADDED batch (same reference lines as lstc_attn_fwd, models/MultiHeadAttention.py:97-122,
+ * applied to every sequence on its own length).  The tokens of all sequences lie back to back: Q, K, V, O (and dO, dQ, dK, dV) are
+ * [M, ld] token-major as the projection GEMMs leave them, sequence n = rows row0[n] .. row0[n+1] - 1 (S_n tokens, CLS first).  The
+ * probabilities are ragged: sequence n owns H * S_n * S_n floats [H, S_n, S_n] from probs + prob0[n].  A call covers the n_ids
+ * sequences seq_ids[0 .. n_ids) (seq_ids NULL: sequences 0 .. n_ids - 1) in ONE launch whose LDS tile is sized by d->S, the
+ * longest sequence of the call: callers bucket the sequences by ceil(S_n / 32) and call once per bucket.
+ *   Structure and arithmetic are those of the first-generation kernels (csrc/attention.hip, attn_fwd_kernel / attn_bwd_kernel with
+ *   VAR): exact-f32 products in every dtype, any d_k, d_v and alignment, no mask.  The relative bias of token pair (i, j), i, j >= 1,
+ *   is table[index[(i-1)*index_ld + (j-1)], h]: a shorter sequence reads the top-left corner of the index alone.
+ *   Dropout: the counter of element (n, h, i, j) is its offset prob0[n] + (h*S_n + i)*S_n + j in the ragged buffer, so
+ *   lstc_dropout_mask() over that buffer with the same seed regenerates the mask.
+ *   Backward: one workgroup per (chunk of the call's sequences, head); dtable is written as d->dtable_chunks partial tables
+ *   [chunks, table_rows, H] (the caller sums them in a fixed order): dtable non-NULL needs dtable_chunks > 0, else
+ *   LSTC_E_UNSUPPORTED.  There are no float atomics.
+ * One writer per output element; its value depends neither on the bucketing nor on the other sequences of the batch.
+ * Device offsets are trusted, except that S_n is clamped to [1, 32 * ceil(d->S / 32)] for the LDS tile.  d->N is not read.
+ * Checked before any launch: d, s, row0, prob0, Q, K, V, probs, O (forward), dO / dQ / dK / dV (backward) NULL: LSTC_E_NULL;
+ * any packed operand or output of the descriptor: LSTC_E_UNSUPPORTED; d->S > 128 or n_probs > 2^32 - 1 (the dropout counter is
+ * 32 bits): LSTC_E_RANGE; n_ids <= 0, n_probs < 0 or a chunk count that does not match dtable_chunks: LSTC_E_SHAPE. */
+typedef struct LstcSeqs {
+    const int32_t* row0;            /* device int32 [N + 1]: first row of every sequence, row0[N] = M */
+    const int64_t* prob0;           /* device int64 [N + 1]: first float of every sequence's probabilities, prob0[N] = n_probs */
+    const int32_t* seq_ids;         /* device int32 [n_ids]: the sequences of this call; NULL = 0 .. n_ids - 1 */
+    int32_t n_ids;
+    int64_t n_probs;                /* floats in the ragged probabilities buffer */
+} LstcSeqs;
+int lstc_attn_var_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
+int lstc_attn_var_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
+
 /* Rectangular attention (reference models/MultiHeadAttention.py:17-23, class ScaledDotProductAttention): the queries and the
  * keys have lengths of their own and there is no relative bias (csrc/attention_x.hip).
  *   A = (Q scale) K^T [N, H, Sq, Sk] ; A = mask byte == 0 ? -1e9f : A (m non-NULL) ; P = softmax(A, -1) ; Pd = dropout(P) ;
@@ -362,6 +391,20 @@ int lstc_cls_outer(const float* W1, const float* U1, const float* W2, const floa
  * klen == NULL is LSTC_E_NULL. */
 int lstc_cls_dot_len(const float* U, const float* X, const int32_t* klen, float* out, float* probs, int64_t N, int32_t S, int32_t H,
                      int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream);
+
+/* The three passes over an UNPADDED X (same reference lines: models/MultiHeadAttention.py:97-122 restricted to row 0): X and dX are
+ * [M, d], sequence n = rows row0[n] .. row0[n+1] - 1 (device int32 [N + 1]; S_n is clamped to [1, S_max]).  U, Y stay [N, H, d] and
+ * W*, out, probs [N, H, S_max], small N-row arrays: out (and probs) are exactly 0 for j >= S_n, mode 1 runs the softmax over the
+ * sequence's own S_n keys, and only the first S_n entries of a W row are read.  lstc_cls_outer_var adds `add0` [N, d] (may be NULL)
+ * to row 0 of every sequence - the CLS row's own terms - so every row of dX has one writer.  At equal lengths the results are those of
+ * lstc_cls_dot / _wsum / _outer on the [N, S, d] view, bit for bit.  Requirements and return codes as lstc_cls_dot with S = S_max;
+ * row0 == NULL is LSTC_E_NULL. */
+int lstc_cls_dot_var(const float* U, const float* X, const int32_t* row0, float* out, float* probs, int64_t N, int32_t S_max, int32_t H,
+                     int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream);
+int lstc_cls_wsum_var(const float* W, const float* X, const int32_t* row0, float* Y, int64_t N, int32_t S_max, int32_t H, int32_t d,
+                      void* stream);
+int lstc_cls_outer_var(const float* W1, const float* U1, const float* W2, const float* U2, const float* add0, const int32_t* row0,
+                       float* dX, int64_t N, int32_t S_max, int32_t H, int32_t d, void* stream);
 
 /* The three passes above over a PACKED X (round 5: the bf16 activation stream hands the last full layer's output to the CLS-only
  * layer as an lstc_pack1 operand of the [N*S, d] matrix and takes the gradient back as one; same reference lines).  Arithmetic is
@@ -459,6 +502,21 @@ int lstc_cls_concat_bwd(const float* dy, float* dx, int64_t N, int32_t S, int32_
 int lstc_cls_concat_len_fwd(const float* x, const int32_t* lens, const float* cls_token, const float* pos, float* y, int64_t N,
                             int32_t S, int32_t d, void* stream);
 int lstc_cls_concat_len_bwd(const float* dy, const int32_t* lens, float* dx, float* dtok, int64_t N, int32_t S, int32_t d,
+                            int32_t mean_cls, void* stream);
+
+/* The CLS concat (models/Encoder.py:51-58) unpadded in and unpadded out: x [M - N, d] holds the patch tokens of N sequences back to
+ * back, y [M, d] the same with each sequence's CLS row in front.  row0 (device int32 [N + 1]) gives the rows of y: sequence n =
+ * rows row0[n] .. row0[n+1] - 1 with L_n = S_n - 1 patch tokens, which are rows row0[n] - n .. of x.
+ *   forward:  y[row0[n]] = mean of the sequence's own L_n rows (a sequential walk per column) or `cls_token`, the rows behind it the
+ *             tokens; `pos` [>= S_max, d] (may be NULL) is added on rows 0..L_n of every sequence.
+ *   backward: dx_n[t] = dy[row0[n]+1+t] + (mean_cls ? dy[row0[n]] / L_n : 0) (dx may be NULL); dtok [S_max, d] (may be NULL) = sum over
+ *             the sequences that have token t of dy[row0[n]+t] - row 0 the gradient of a learned CLS token, rows 0..S_max-1 that of
+ *             the position table; the sequences are added in order (deterministic).
+ * 16-B accesses when d % 4 == 0 and every operand is 16-B aligned, 4-B ones otherwise: the results are the same bits, and a
+ * sequence's bits do not depend on its neighbours.  The offsets are trusted. */
+int lstc_cls_concat_var_fwd(const float* x, const int32_t* row0, const float* cls_token, const float* pos, float* y, int64_t N,
+                            int32_t d, void* stream);
+int lstc_cls_concat_var_bwd(const float* dy, const int32_t* row0, float* dx, float* dtok, int64_t N, int32_t S_max, int32_t d,
                             int32_t mean_cls, void* stream);
 
 /* out[c] = sum_r x[r, c] for x [rows, ld] (first `cols` columns); deterministic two-pass reduction.

@@ -176,22 +176,38 @@ __device__ __forceinline__ void lds_times_rows(const float* __restrict__ Alds, c
     }
 }
 
+__device__ __forceinline__ int seq_count(const SeqParams& sq) { return sq.n_ids; }
+__device__ __forceinline__ int seq_count(const NoSeqs&) { return 0; }
+
 // First-generation kernels (S <= 128), forward and backward.
 // MASKED: where the mask byte of (n, h, i, j) is 0 the scaled logit is replaced by ATTN_MASK_FILL before the bias is added; in the
 // backward the saved P carries the mask already, so dV and the row sums do not change.  The unmasked instantiation compiles to
 // what the kernel was before masks existed (tools/isa_diff.py).
-template <int T, bool MASKED>
-__global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+// VAR (lstc_attn_var_fwd / _bwd): the sequence, its length and its operand rows come from the offset tables of `sq` instead of
+// n * S - sequence n = rows row0[n] .. row0[n + 1] - 1 of Q / K / V / O, its probabilities [H, S_n, S_n] from prob0[n], which is
+// also the dropout counter of its first element.  S_n is clamped to [1, 32 T], the LDS tile of the instantiation.
+template <int T, bool MASKED, bool VAR = false>
+__global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk, const SeqArg<VAR> sq) {
     const DropKey dkn = drop_key_now(p.dkey);
     constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
     constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int n = ATTN_CHUNK, h = ATTN_HEAD, S = p.S;
+    int n = ATTN_CHUNK, S = p.S;
+    const int h = ATTN_HEAD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    float* Ob = p.O + (size_t)n * S * p.ldo + (size_t)h * p.dv;
+    size_t r0;                       // the sequence's first row
+    if constexpr (VAR) {
+        if (sq.ids) n = sq.ids[n];
+        const int b = sq.row0[n];
+        S = min(max(sq.row0[n + 1] - b, 1), SP);
+        r0 = (size_t)b;
+    } else {
+        r0 = (size_t)n * S;
+    }
+    const float* Qb = p.Q + r0 * p.ldq + (size_t)h * p.dk;
+    const float* Kb = p.K + r0 * p.ldk + (size_t)h * p.dk;
+    const float* Vb = p.V + r0 * p.ldv + (size_t)h * p.dv;
+    float* Ob = p.O + r0 * p.ldo + (size_t)h * p.dv;
 
 #pragma unroll 1
     for (int t = wave; t < T * T; t += NT / 64) {
@@ -202,8 +218,16 @@ __global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const Attn
     }
     __syncthreads();
 
-    float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
-    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    float* pr_base;
+    uint32_t flat0;
+    if constexpr (VAR) {
+        const int64_t e0 = sq.prob0[n] + (int64_t)h * S * S;
+        pr_base = p.probs + e0;
+        flat0 = (uint32_t)e0;
+    } else {
+        pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
+        flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    }
     const uint8_t* mk_nh = nullptr;
     if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
     // sq == 0 (a key-padding mask): every query row reads the same S bytes - once per (sequence, head), ahead of the row loop,
@@ -261,12 +285,13 @@ __global__ void __launch_bounds__(NT, T <= 2 ? 4 : 2) attn_fwd_kernel(const Attn
         }
     }
     __syncthreads();
-    lds_times_rows<T, false, BF>(sm, Vb, p.ldv, S, p.dv, 1.f, Ob, p.ldo, reinterpret_cast<__bf16*>(p.Op), (uint32_t)n * (uint32_t)S,
-                             (uint32_t)((h * p.dv) >> 5), (uint32_t)p.kbo);
+    if constexpr (VAR) lds_times_rows<T, false, BF>(sm, Vb, p.ldv, S, p.dv, 1.f, Ob, p.ldo);      // row output only
+    else lds_times_rows<T, false, BF>(sm, Vb, p.ldv, S, p.dv, 1.f, Ob, p.ldo, reinterpret_cast<__bf16*>(p.Op), (uint32_t)n * (uint32_t)S,
+                                      (uint32_t)((h * p.dv) >> 5), (uint32_t)p.kbo);
 }
 
-template <int T, bool MASKED>
-__global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+template <int T, bool MASKED, bool VAR = false>
+__global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const AttnParams p, const MaskArg<MASKED> mk, const SeqArg<VAR> sq) {
     const DropKey dkn = drop_key_now(p.dkey);
     constexpr bool BF = false;       // first generation: exact-f32 products only (bf16 products made these latency-bound loops slower)
     constexpr int SP = 32 * T, LD = SP + 1, NJ = (SP + 63) / 64;
@@ -274,7 +299,7 @@ __global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const Attn
     float* Dm = sm;                 // dP~ then dA
     float* Pm = sm + SP * LD;       // dropped probabilities
     float* tacc = sm + 2 * SP * LD; // [NT/64][table_rows] bias-table gradient of this head, one copy per wave
-    const int h = ATTN_HEAD, S = p.S;
+    const int h = ATTN_HEAD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool has_bias = p.index_ld > 0 && p.dtable != nullptr;
     if (has_bias)
@@ -283,13 +308,23 @@ __global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const Attn
     // positions differ), and a wave walks its rows in order, so plain read-modify-write is race-free and the sum order fixed
     float* const tw = tacc + wave * p.table_rows;
     const int n_begin = ATTN_CHUNK * p.n_per_wg;
-    const int n_end = min(p.N, n_begin + p.n_per_wg);
+    const int n_end = min(VAR ? seq_count(sq) : p.N, n_begin + p.n_per_wg);
 #pragma unroll 1
-    for (int n = n_begin; n < n_end; ++n) {
-        const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-        const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-        const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-        const float* dOb = p.dO + (size_t)n * S * p.ldo + (size_t)h * p.dv;
+    for (int it = n_begin; it < n_end; ++it) {
+        int n = it, S = p.S;
+        size_t r0;                   // the sequence's first row
+        if constexpr (VAR) {
+            if (sq.ids) n = sq.ids[it];
+            const int b = sq.row0[n];
+            S = min(max(sq.row0[n + 1] - b, 1), SP);
+            r0 = (size_t)b;
+        } else {
+            r0 = (size_t)n * S;
+        }
+        const float* Qb = p.Q + r0 * p.ldq + (size_t)h * p.dk;
+        const float* Kb = p.K + r0 * p.ldk + (size_t)h * p.dk;
+        const float* Vb = p.V + r0 * p.ldv + (size_t)h * p.dv;
+        const float* dOb = p.dO + r0 * p.ldo + (size_t)h * p.dv;
         __syncthreads();   // previous sequence's LDS readers are done
 #pragma unroll 1
         for (int t = wave; t < T * T; t += NT / 64) {
@@ -299,8 +334,16 @@ __global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const Attn
             store_tile_lds<LD>(Dm, ti, tj, acc);
         }
         __syncthreads();
-        const float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
-        const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+        const float* pr_base;
+        uint32_t flat0;
+        if constexpr (VAR) {
+            const int64_t e0 = sq.prob0[n] + (int64_t)h * S * S;
+            pr_base = p.probs + e0;
+            flat0 = (uint32_t)e0;
+        } else {
+            pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
+            flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+        }
         const uint8_t* mk_nh = nullptr;
         if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
         bool mk_rows_alike = false;                     // as in the forward: a key-padding mask is read once per (sequence, head)
@@ -349,9 +392,9 @@ __global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const Attn
             }
         }
         __syncthreads();
-        lds_times_rows<T, true, BF>(Pm, dOb, p.ldo, S, p.dv, 1.f, p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv, p.ldv);
-        lds_times_rows<T, false, BF>(Dm, Kb, p.ldk, S, p.dk, p.scale, p.dQ + (size_t)n * S * p.ldq + (size_t)h * p.dk, p.ldq);
-        lds_times_rows<T, true, BF>(Dm, Qb, p.ldq, S, p.dk, p.scale, p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk, p.ldk);
+        lds_times_rows<T, true, BF>(Pm, dOb, p.ldo, S, p.dv, 1.f, p.dV + r0 * p.ldv + (size_t)h * p.dv, p.ldv);
+        lds_times_rows<T, false, BF>(Dm, Kb, p.ldk, S, p.dk, p.scale, p.dQ + r0 * p.ldq + (size_t)h * p.dk, p.ldq);
+        lds_times_rows<T, true, BF>(Dm, Qb, p.ldq, S, p.dk, p.scale, p.dK + r0 * p.ldk + (size_t)h * p.dk, p.ldk);
     }
     if (has_bias) {
         __syncthreads();
@@ -359,7 +402,7 @@ __global__ void __launch_bounds__(NT, T <= 3 ? 2 : 1) attn_bwd_kernel(const Attn
             float v = tacc[i];
 #pragma unroll
             for (int w = 1; w < NT / 64; ++w) v += tacc[w * p.table_rows + i];
-            if (p.table_partials) p.dtable[((size_t)ATTN_CHUNK * p.table_rows + i) * p.H + h] = v;
+            if (VAR || p.table_partials) p.dtable[((size_t)ATTN_CHUNK * p.table_rows + i) * p.H + h] = v;      // VAR: partial tables only
             else atomicAdd(&p.dtable[(size_t)i * p.H + h], v);
         }
     }
@@ -939,10 +982,10 @@ int attn_fwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
     auto gen1 = [&](auto masked, const auto& mask_arg) {
         constexpr bool M = decltype(masked)::value;
         switch (T) {
-            case 1: launch_big_lds<attn_fwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg); break;
-            case 2: launch_big_lds<attn_fwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg); break;
-            case 3: launch_big_lds<attn_fwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg); break;
-            default: launch_big_lds<attn_fwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 1: launch_big_lds<attn_fwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 2: launch_big_lds<attn_fwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 3: launch_big_lds<attn_fwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            default: launch_big_lds<attn_fwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
         }
     };
     if (mk) gen1(std::true_type{}, *mk); else gen1(std::false_type{}, NoMask{});
@@ -1030,19 +1073,85 @@ int attn_bwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
     auto gen1 = [&](auto masked, const auto& mask_arg) {
         constexpr bool M = decltype(masked)::value;
         switch (T) {
-            case 1: launch_big_lds<attn_bwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg); break;
-            case 2: launch_big_lds<attn_bwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg); break;
-            case 3: launch_big_lds<attn_bwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg); break;
-            default: launch_big_lds<attn_bwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg); break;
+            case 1: launch_big_lds<attn_bwd_kernel<1, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 2: launch_big_lds<attn_bwd_kernel<2, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 3: launch_big_lds<attn_bwd_kernel<3, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
+            default: launch_big_lds<attn_bwd_kernel<4, M>>(grid, NT, lds, st, p, mask_arg, NoSeqs{}); break;
         }
     };
     if (mk) gen1(std::true_type{}, *mk); else gen1(std::false_type{}, NoMask{});
     return lstc_launch_status();
 }
 
+// Attention over sequence offsets (lstc_attn_var_fwd / _bwd): the checks shared by both, all ahead of any launch.  The descriptor
+// is filled as for one sequence of d->S tokens (its N does not enter: the probabilities are addressed through prob0).
+int fill_var(const LstcAttnDesc* d, const LstcSeqs* s, AttnParams& p, SeqParams& sq, bool bwd) {
+    if (!d || !s || !s->row0 || !s->prob0) return LSTC_E_NULL;
+    if (d->O_pack || d->dQ_pack || d->dK_pack || d->dV_pack || d->in_pack_cols > 0 || d->dO_pack_cols > 0) return LSTC_E_UNSUPPORTED;
+    if (d->S > 128) return LSTC_E_RANGE;
+    if (s->n_ids <= 0 || s->n_probs < 0) return LSTC_E_SHAPE;
+    if ((uint64_t)s->n_probs > 0xffffffffull) return LSTC_E_RANGE;      // 32-bit dropout counters = offsets in the ragged buffer
+    LstcAttnDesc one = *d;
+    one.N = 1;
+    const int rc = fill_params(&one, p, bwd);
+    if (rc) return rc;
+    if (!bwd && !d->O) return LSTC_E_NULL;
+    sq.row0 = s->row0; sq.prob0 = s->prob0; sq.ids = s->seq_ids; sq.n_ids = s->n_ids;
+    return 0;
+}
+
+int attn_var_fwd(const LstcAttnDesc* d, const LstcSeqs* s, hipStream_t st) {
+    AttnParams p;
+    SeqParams sq;
+    const int rc = fill_var(d, s, p, sq, false);
+    if (rc) return rc;
+    const int T = (p.S + 31) / 32;
+    const size_t lds = (size_t)(32 * T) * (32 * T + 1) * sizeof(float);
+    dim3 grid = ATTN_GRID(sq.n_ids, p.H);
+    switch (T) {
+        case 1: launch_big_lds<attn_fwd_kernel<1, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        case 2: launch_big_lds<attn_fwd_kernel<2, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        case 3: launch_big_lds<attn_fwd_kernel<3, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        default: launch_big_lds<attn_fwd_kernel<4, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+    }
+    return lstc_launch_status();
+}
+
+int attn_var_bwd(const LstcAttnDesc* d, const LstcSeqs* s, hipStream_t st) {
+    AttnParams p;
+    SeqParams sq;
+    const int rc = fill_var(d, s, p, sq, true);
+    if (rc) return rc;
+    const int T = (p.S + 31) / 32;
+    const bool bias = d->index_ld > 0 && d->dtable;
+    if (bias && d->table_rows <= 0) return LSTC_E_SHAPE;
+    if (bias && d->dtable_chunks <= 0) return LSTC_E_UNSUPPORTED;      // partial tables only: no float atomics on this path
+    p.table_rows = bias ? d->table_rows : 0;
+    const size_t lds = ((size_t)2 * (32 * T) * (32 * T + 1) + (size_t)(NT / 64) * p.table_rows) * sizeof(float);
+    if (lds > 160 * 1024) return LSTC_E_RANGE;
+    int npw = (int)(((int64_t)sq.n_ids * p.H + 4095) / 4096);
+    npw = npw < 1 ? 1 : (npw > 8 ? 8 : npw);
+    if (bias) npw = (sq.n_ids + d->dtable_chunks - 1) / d->dtable_chunks;
+    p.n_per_wg = npw;
+    p.table_partials = 1;
+    const int chunks = (sq.n_ids + npw - 1) / npw;
+    if (bias && chunks != d->dtable_chunks) return LSTC_E_SHAPE;
+    dim3 grid = ATTN_GRID(chunks, p.H);
+    switch (T) {
+        case 1: launch_big_lds<attn_bwd_kernel<1, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        case 2: launch_big_lds<attn_bwd_kernel<2, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        case 3: launch_big_lds<attn_bwd_kernel<3, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+        default: launch_big_lds<attn_bwd_kernel<4, false, true>>(grid, NT, lds, st, p, NoMask{}, sq); break;
+    }
+    return lstc_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+
+int lstc_attn_var_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) { return attn_var_fwd(d, s, (hipStream_t)stream); }
+int lstc_attn_var_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) { return attn_var_bwd(d, s, (hipStream_t)stream); }
 
 int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) { return attn_fwd(d, nullptr, (hipStream_t)stream); }
 int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) { return attn_bwd(d, nullptr, (hipStream_t)stream); }
@@ -1363,7 +1472,9 @@ __device__ inline void cls_dot_tail(float* sc, float* __restrict__ out, float* _
 // mode 0: raw dot products; 1: softmax over j, probs -> `probs`, dropout(probs) -> `out`;
 // mode 2: `out` = P * (dP - sum_j dP P), dP = dot * keep  (softmax + dropout backward; `probs` is an input)
 // LEN: sequence n has klen[n] keys (clamped to [1, S]); the rows X[n, j >= klen[n]] are never read.
-template <int HT, bool LEN = false>
+// VAR (lstc_cls_dot_var): X is unpadded [M, d] and `klen` the row table row0 [N + 1]: sequence n = rows row0[n] .. row0[n + 1] - 1,
+// out / probs stay [N, H, S] with S the longest sequence and exact zeros behind a sequence's own keys (the LEN tail).
+template <int HT, bool LEN = false, bool VAR = false>
 __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U, const float* __restrict__ X,
                                                       float* __restrict__ out, float* __restrict__ probs, int S, int H, int d,
                                                       int mode, DropKey dkey, int has_drop, const int32_t* __restrict__ klen) {
@@ -1373,9 +1484,9 @@ __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U
     float* sc = sm + (size_t)H * d;   // [H][S]
     const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* Un = U + (size_t)n * H * d;
-    const float* Xn = X + (size_t)n * S * d;
+    const float* Xn = VAR ? X + (size_t)klen[n] * d : X + (size_t)n * S * d;
     const int d4 = d >> 2;
-    const int Sv = LEN ? min(max((int)klen[n], 1), S) : S;          // rows of X that exist
+    const int Sv = VAR ? min(max((int)(klen[n + 1] - klen[n]), 1), S) : LEN ? min(max((int)klen[n], 1), S) : S;          // rows of X that exist
     for (int i = threadIdx.x; i < H * d4; i += NT) reinterpret_cast<float4*>(Ul)[i] = reinterpret_cast<const float4*>(Un)[i];
     __syncthreads();
     // a wave takes two rows at a time and requests all of their float4 pieces (up to 16 KB in flight per wave) before the first
@@ -1422,15 +1533,18 @@ __global__ void __launch_bounds__(NT) cls_dot_kernel(const float* __restrict__ U
             }
     }
     __syncthreads();
-    cls_dot_tail<LEN>(sc, out, probs, n, S, H, mode, dkey, has_drop, wave, lane, Sv);
+    cls_dot_tail<LEN || VAR>(sc, out, probs, n, S, H, mode, dkey, has_drop, wave, lane, Sv);
 }
 
-template <int HT>
+// VAR (lstc_cls_wsum_var / lstc_cls_outer_var): X / dX unpadded [M, d], sequence n = rows row0[n] .. row0[n + 1] - 1 (clamped to
+// [1, S] rows); W stays [N, H, S] and only its first S_n entries per head are read.
+template <int HT, bool VAR = false>
 __global__ void __launch_bounds__(NT) cls_wsum_kernel(const float* __restrict__ W, const float* __restrict__ X,
-                                                       float* __restrict__ Y, int S, int H, int d) {
+                                                       float* __restrict__ Y, int S, int H, int d, const int32_t* __restrict__ row0) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // W[n]: [H][S]
     const int n = blockIdx.x;
-    const float* Xn = X + (size_t)n * S * d;
+    const float* Xn = VAR ? X + (size_t)row0[n] * d : X + (size_t)n * S * d;
+    const int Sv = VAR ? min(max((int)(row0[n + 1] - row0[n]), 1), S) : S;
     for (int i = threadIdx.x; i < H * S; i += NT) sm[i] = W[(size_t)n * H * S + i];
     __syncthreads();
     const int d4 = d >> 2;
@@ -1438,7 +1552,7 @@ __global__ void __launch_bounds__(NT) cls_wsum_kernel(const float* __restrict__ 
         float4 acc[HT];
 #pragma unroll
         for (int h = 0; h < HT; ++h) acc[h] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int j = 0; j < S; ++j) {
+        for (int j = 0; j < Sv; ++j) {
             const float4 x = reinterpret_cast<const float4*>(Xn + (size_t)j * d)[c];
 #pragma unroll
             for (int h = 0; h < HT; ++h)
@@ -1453,10 +1567,12 @@ __global__ void __launch_bounds__(NT) cls_wsum_kernel(const float* __restrict__ 
     }
 }
 
-template <int HT>
+// VAR: `add0` [N, d] (may be null) joins row 0 of each sequence - the CLS row's own gradient terms - so every row of dX keeps one writer.
+template <int HT, bool VAR = false>
 __global__ void __launch_bounds__(NT) cls_outer_kernel(const float* __restrict__ W1, const float* __restrict__ U1,
                                                         const float* __restrict__ W2, const float* __restrict__ U2,
-                                                        float* __restrict__ dX, int S, int H, int d) {
+                                                        float* __restrict__ dX, int S, int H, int d, const int32_t* __restrict__ row0,
+                                                        const float* __restrict__ add0) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // W1[n], W2[n]: 2 x [H][S]
     const int n = blockIdx.x;
     for (int i = threadIdx.x; i < H * S; i += NT) {
@@ -1465,7 +1581,8 @@ __global__ void __launch_bounds__(NT) cls_outer_kernel(const float* __restrict__
     }
     __syncthreads();
     const int d4 = d >> 2;
-    float* Dn = dX + (size_t)n * S * d;
+    float* Dn = VAR ? dX + (size_t)row0[n] * d : dX + (size_t)n * S * d;
+    const int Sv = VAR ? min(max((int)(row0[n + 1] - row0[n]), 1), S) : S;
     for (int c = threadIdx.x; c < d4; c += NT) {
         float4 u1[HT], u2[HT];
 #pragma unroll
@@ -1476,7 +1593,7 @@ __global__ void __launch_bounds__(NT) cls_outer_kernel(const float* __restrict__
                 u2[h] = reinterpret_cast<const float4*>(U2 + ((size_t)n * H + h) * d)[c];
             }
         }
-        for (int j = 0; j < S; ++j) {
+        for (int j = 0; j < Sv; ++j) {
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int h = 0; h < HT; ++h)
@@ -1485,6 +1602,12 @@ __global__ void __launch_bounds__(NT) cls_outer_kernel(const float* __restrict__
                     o.x += a * u1[h].x + b * u2[h].x; o.y += a * u1[h].y + b * u2[h].y;
                     o.z += a * u1[h].z + b * u2[h].z; o.w += a * u1[h].w + b * u2[h].w;
                 }
+            if constexpr (VAR) {
+                if (j == 0 && add0) {
+                    const float4 e = reinterpret_cast<const float4*>(add0 + (size_t)n * d)[c];
+                    o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
+                }
+            }
             reinterpret_cast<float4*>(Dn + (size_t)j * d)[c] = o;
         }
     }
@@ -1754,12 +1877,12 @@ int assoc_check(const void* a, const void* b, const void* c, int64_t N, int S, i
     return 0;
 }
 
-#define LSTC_H_DISPATCH(KERN, H, ...)                                            \
-    do {                                                                         \
-        if ((H) <= 2) hipLaunchKernelGGL(KERN<2>, __VA_ARGS__);                  \
-        else if ((H) <= 4) hipLaunchKernelGGL(KERN<4>, __VA_ARGS__);             \
-        else if ((H) <= 8) hipLaunchKernelGGL(KERN<8>, __VA_ARGS__);             \
-        else hipLaunchKernelGGL(KERN<16>, __VA_ARGS__);                          \
+#define LSTC_H_DISPATCH(KERN, VAR, H, ...)                                              \
+    do {                                                                                \
+        if ((H) <= 2) hipLaunchKernelGGL((KERN<2, VAR>), __VA_ARGS__);                  \
+        else if ((H) <= 4) hipLaunchKernelGGL((KERN<4, VAR>), __VA_ARGS__);             \
+        else if ((H) <= 8) hipLaunchKernelGGL((KERN<8, VAR>), __VA_ARGS__);             \
+        else hipLaunchKernelGGL((KERN<16, VAR>), __VA_ARGS__);                          \
     } while (0)
 
 }  // namespace
@@ -1808,12 +1931,56 @@ int lstc_cls_dot_len(const float* U, const float* X, const int32_t* klen, float*
     return lstc_launch_status();
 }
 
+int lstc_cls_dot_var(const float* U, const float* X, const int32_t* row0, float* out, float* probs, int64_t N, int32_t S_max, int32_t H,
+                     int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream) {
+    const int32_t S = S_max;
+    int rc = assoc_check(U, X, out, N, S, H, d);
+    if (rc) return rc;
+    if (!row0) return LSTC_E_NULL;
+    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
+    if (mode != 0 && !probs) return LSTC_E_NULL;
+    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
+    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
+    if (lds > 96 * 1024) return LSTC_E_RANGE;
+    const DropKey dk = make_drop_key(dropout_p, seed);
+    const int has_drop = dropout_p > 0.f;
+    const dim3 grid((unsigned)N);
+    hipStream_t st = (hipStream_t)stream;
+    if (H <= 2) launch_big_lds<cls_dot_kernel<2, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
+    else if (H <= 4) launch_big_lds<cls_dot_kernel<4, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
+    else if (H <= 8) launch_big_lds<cls_dot_kernel<8, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
+    else launch_big_lds<cls_dot_kernel<16, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
+    return lstc_launch_status();
+}
+
+int lstc_cls_wsum_var(const float* W, const float* X, const int32_t* row0, float* Y, int64_t N, int32_t S_max, int32_t H, int32_t d,
+                      void* stream) {
+    int rc = assoc_check(X, Y, X, N, S_max, H, d);
+    if (rc) return rc;
+    if (!W || !row0) return LSTC_E_NULL;
+    const size_t lds = (size_t)H * S_max * sizeof(float);
+    LSTC_H_DISPATCH(cls_wsum_kernel, true, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S_max, H, d, row0);
+    return lstc_launch_status();
+}
+
+int lstc_cls_outer_var(const float* W1, const float* U1, const float* W2, const float* U2, const float* add0, const int32_t* row0,
+                       float* dX, int64_t N, int32_t S_max, int32_t H, int32_t d, void* stream) {
+    int rc = assoc_check(U1, U2, dX, N, S_max, H, d);
+    if (rc) return rc;
+    if (!W1 || !W2 || !row0) return LSTC_E_NULL;
+    if (add0 && !aligned16(add0)) return LSTC_E_ALIGN;
+    const size_t lds = (size_t)2 * H * S_max * sizeof(float);
+    LSTC_H_DISPATCH(cls_outer_kernel, true, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S_max, H, d, row0,
+                    add0);
+    return lstc_launch_status();
+}
+
 int lstc_cls_wsum(const float* W, const float* X, float* Y, int64_t N, int32_t S, int32_t H, int32_t d, void* stream) {
     int rc = assoc_check(X, Y, X, N, S, H, d);
     if (rc) return rc;
     if (!W) return LSTC_E_NULL;
     const size_t lds = (size_t)H * S * sizeof(float);
-    LSTC_H_DISPATCH(cls_wsum_kernel, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S, H, d);
+    LSTC_H_DISPATCH(cls_wsum_kernel, false, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S, H, d, (const int32_t*)nullptr);
     return lstc_launch_status();
 }
 
@@ -1823,7 +1990,8 @@ int lstc_cls_outer(const float* W1, const float* U1, const float* W2, const floa
     if (rc) return rc;
     if (!W1 || !W2) return LSTC_E_NULL;
     const size_t lds = (size_t)2 * H * S * sizeof(float);
-    LSTC_H_DISPATCH(cls_outer_kernel, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S, H, d);
+    LSTC_H_DISPATCH(cls_outer_kernel, false, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S, H, d,
+                    (const int32_t*)nullptr, (const float*)nullptr);
     return lstc_launch_status();
 }
 

@@ -52,6 +52,20 @@ using MaskArg = std::conditional_t<MASKED, MaskParams, NoMask>;
 // -1e9f + bias rounds back to -1e9f for |bias| < 32, so a fully masked row comes out uniform and nothing is ever -inf or NaN
 constexpr float ATTN_MASK_FILL = -1e9f;
 
+// Sequence offsets of the *_var entry points (LstcSeqs): the tokens of all sequences lie back to back in [M, ld] matrices, sequence
+// n = rows row0[n] .. row0[n + 1] - 1, its probabilities H * S_n * S_n floats from prob0[n]; a launch covers the n_ids sequences
+// ids[0 .. n_ids) (ids null: 0 .. n_ids - 1).  The third argument of the first-generation kernel bodies is a SeqArg<VAR>, empty for
+// the fixed-S kernels, whose code then holds no trace of it (`if constexpr (VAR)`).
+struct SeqParams {
+    const int32_t* row0;
+    const int64_t* prob0;
+    const int32_t* ids;
+    int n_ids;
+};
+struct NoSeqs {};
+template <bool VAR>
+using SeqArg = std::conditional_t<VAR, SeqParams, NoSeqs>;
+
 typedef __bf16 attn_h8 __attribute__((ext_vector_type(8)));
 typedef float attn_f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 attn_h2 __attribute__((ext_vector_type(2)));

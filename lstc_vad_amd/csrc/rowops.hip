@@ -733,6 +733,68 @@ __global__ void __launch_bounds__(NT) cls_concat_len_dtok_kernel(const V* __rest
     dtok[(int64_t)t * dv + c] = s;
 }
 
+// ------------------------------------------------------------------------------ CLS concat, unpadded in and unpadded out
+// Sequence n owns rows row0[n] .. row0[n + 1] - 1 of y [M, d] (CLS first) and, having one token fewer, rows row0[n] - n .. of x
+// [M - N, d].  The same two access patterns and the same sequential per-column walk as the length kernels above: a sequence's bits
+// depend neither on the path nor on its neighbours.
+// grid (N, ceil(dv/NT)).  y[row0[n]] = cls or mean(x_n); y[row0[n] + 1 + t] = x_n[t]; pos on rows 0..L_n of the sequence.
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_var_fwd_kernel(const V* __restrict__ x, const int32_t* __restrict__ row0,
+                                                                 const V* __restrict__ cls, const V* __restrict__ pos,
+                                                                 V* __restrict__ y, int dv) {
+    const int64_t n = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    const int64_t b = row0[n];
+    const int L = (int)(row0[n + 1] - b) - 1;
+    const V* xr = x + (b - n) * dv + c;
+    V* yr = y + b * dv + c;
+    V s = vzero(V{});
+#pragma unroll 8
+    for (int t = 0; t < L; ++t) {
+        const V v = xr[(int64_t)t * dv];
+        s = vadd(s, v);
+        yr[(int64_t)(t + 1) * dv] = pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v;
+    }
+    V cv = cls ? cls[c] : vdiv(s, (float)max(L, 1));
+    if (pos) cv = vadd(cv, pos[c]);
+    yr[0] = cv;
+}
+
+// dx_n[t] = dy[row0[n] + 1 + t] + (mean_cls ? dy[row0[n]] / L_n : 0)
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_var_bwd_kernel(const V* __restrict__ dy, const int32_t* __restrict__ row0,
+                                                                 V* __restrict__ dx, int dv, int mean_cls) {
+    const int64_t n = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    const int64_t b = row0[n];
+    const int L = (int)(row0[n + 1] - b) - 1;
+    const V* dr = dy + b * dv + c;
+    V* xr = dx + (b - n) * dv + c;
+    const V g0 = mean_cls ? vdiv(dr[0], (float)max(L, 1)) : vzero(V{});
+#pragma unroll 8
+    for (int t = 0; t < L; ++t) xr[(int64_t)t * dv] = vadd(dr[(int64_t)(t + 1) * dv], g0);
+}
+
+// dtok[t, :] = sum over the sequences that have token t (t < S_n) of dy[row0[n] + t, :], the sequences walked in order.
+// grid (S_max, ceil(dv/NT)).
+template <typename V>
+__global__ void __launch_bounds__(NT) cls_concat_var_dtok_kernel(const V* __restrict__ dy, const int32_t* __restrict__ row0,
+                                                                  V* __restrict__ dtok, int64_t N, int dv) {
+    const int t = blockIdx.x;
+    const int c = blockIdx.y * NT + threadIdx.x;
+    if (c >= dv) return;
+    V s = vzero(V{});
+    int64_t b = row0[0];
+    for (int64_t n = 0; n < N; ++n) {
+        const int64_t e = row0[n + 1];
+        if (b + t < e) s = vadd(s, dy[(b + t) * dv + c]);
+        b = e;
+    }
+    dtok[(int64_t)t * dv + c] = s;
+}
+
 // ---------------------------------------------------------------------------------- colsum
 // pass 1: grid (ceil(cols/NT), n_partial): workgroup y sums rows y, y+n_partial, ... of NT columns.
 // (blockIdx.z = plane of a batched call, lstc_colsum_batched: planes are `xstride` / n_partial * cols floats apart)
@@ -1455,6 +1517,40 @@ int lstc_cls_concat_len_bwd(const float* dy, const int32_t* lens, float* dx, flo
         if (v4) hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float4>, dim3((unsigned)S, gy), NT, 0, st, (const float4*)dy, lens,
                                    (float4*)dtok, N, S, dv);
         else hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float>, dim3((unsigned)S, gy), NT, 0, st, dy, lens, dtok, N, S, dv);
+    }
+    return lstc_launch_status();
+}
+
+int lstc_cls_concat_var_fwd(const float* x, const int32_t* row0, const float* cls_token, const float* pos, float* y, int64_t N,
+                            int32_t d, void* stream) {
+    if (!x || !row0 || !y) return LSTC_E_NULL;
+    if (N <= 0 || d <= 0) return LSTC_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (d % 4 == 0 && aligned16(x) && aligned16(y) && (!cls_token || aligned16(cls_token)) && (!pos || aligned16(pos)))
+        hipLaunchKernelGGL(cls_concat_var_fwd_kernel<float4>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, st, (const float4*)x, row0,
+                           (const float4*)cls_token, (const float4*)pos, (float4*)y, d / 4);
+    else
+        hipLaunchKernelGGL(cls_concat_var_fwd_kernel<float>, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, st, x, row0, cls_token, pos, y, d);
+    return lstc_launch_status();
+}
+
+int lstc_cls_concat_var_bwd(const float* dy, const int32_t* row0, float* dx, float* dtok, int64_t N, int32_t S_max, int32_t d,
+                            int32_t mean_cls, void* stream) {
+    if (!dy || !row0 || (!dx && !dtok)) return LSTC_E_NULL;
+    if (N <= 0 || d <= 0 || (dtok && S_max < 1)) return LSTC_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const bool v4 = d % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(dtok);
+    const int dv = v4 ? d / 4 : d;
+    const unsigned gy = (unsigned)((dv + NT - 1) / NT);
+    if (dx) {
+        if (v4) hipLaunchKernelGGL(cls_concat_var_bwd_kernel<float4>, dim3((unsigned)N, gy), NT, 0, st, (const float4*)dy, row0, (float4*)dx,
+                                   dv, mean_cls);
+        else hipLaunchKernelGGL(cls_concat_var_bwd_kernel<float>, dim3((unsigned)N, gy), NT, 0, st, dy, row0, dx, dv, mean_cls);
+    }
+    if (dtok) {
+        if (v4) hipLaunchKernelGGL(cls_concat_var_dtok_kernel<float4>, dim3((unsigned)S_max, gy), NT, 0, st, (const float4*)dy, row0,
+                                   (float4*)dtok, N, dv);
+        else hipLaunchKernelGGL(cls_concat_var_dtok_kernel<float>, dim3((unsigned)S_max, gy), NT, 0, st, dy, row0, dtok, N, dv);
     }
     return lstc_launch_status();
 }

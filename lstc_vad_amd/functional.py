@@ -817,6 +817,22 @@ def gather_rows(bank: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
+class GatherRowsFunction(torch.autograd.Function):
+    """``gather_rows(x, idx)`` of a [rows, d] matrix with a gradient: dx has dy's rows at ``idx`` (distinct indices) and zeros
+    elsewhere.  The CLS rows of an unpadded batch where the CLS-only layer runs in full (MultiHeadAttention.forward_cls)."""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        ctx.idx, ctx.shape = idx, tuple(x.shape)
+        return gather_rows(x.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = torch.zeros(ctx.shape, device=dy.device, dtype=torch.float32)
+        dx.index_copy_(0, ctx.idx, dy.contiguous())        # a copy of N rows (plumbing): one writer per row
+        return dx, None
+
+
 def expand_rows(srcs, dsts, row_map: torch.Tensor):
     """dsts[j][m, :] = srcs[j][row_map[m], :] for up to three float32 matrices of equal width in ONE launch (``lstc_expand_rows``).
     Row strides are free, columns contiguous; ``row_map`` int32 on the device, one entry per destination row, every entry a row of
@@ -1211,6 +1227,156 @@ def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, ou
     return dq, dk_, dv_, dtable
 
 
+UNPADDED_MAX_TOKENS = 128      # S_n = L_n + 1 of the unpadded route: the LDS tile of the first-generation attention kernels
+# 1: one attention launch per tile count T = ceil(S_n / 32) present in the batch, each over a device list of its sequences, instead of
+# ONE launch instantiated for the longest sequence.  Same bits either way.  Measured on the scoring workload of tools/unpadded_time.py
+# (forward only, T <= 2): 136.64 ms bucketed against 136.85 ms single, inside the spread - so the single launch is the default
+_ATTN_VAR_BUCKETS = os.environ.get("LSTC_ATTN_VAR_BUCKETS", "0") == "1"
+
+
+class SeqLayout:
+    """The layout of an unpadded batch (include/lstc_hip.h, LstcSeqs), built on the host by ``unpadded_layout``: N sequences of
+    ``lengths[n]`` patch tokens, ``S[n] = lengths[n] + 1`` tokens with the CLS token.  ``in0`` [N + 1]: first row of each sequence
+    in the input [sum L, d]; ``row0`` [N + 1]: in the activations [M, d], ``M = sum S``; ``prob0(H)`` [N + 1]: first float of its
+    [H, S_n, S_n] probabilities; ``buckets``: {T: ids} with T = ceil(S_n / 32), ids ascending (the launches of the bucketed form,
+    ``_ATTN_VAR_BUCKETS``).  ``on(device, H)`` uploads the tables once per (device, H) in two copies; everything else is plain
+    Python and runs without a device."""
+
+    def __init__(self, lengths):
+        self.lengths = list(lengths)
+        self.N = len(self.lengths)
+        self.S = [v + 1 for v in self.lengths]
+        self.in0, self.row0 = [0], [0]
+        for v in self.lengths:
+            self.in0.append(self.in0[-1] + v)
+            self.row0.append(self.row0[-1] + v + 1)
+        self.M, self.S_max = self.row0[-1], max(self.S)
+        self.buckets = {}
+        for n, sn in enumerate(self.S):
+            self.buckets.setdefault((sn + 31) // 32, []).append(n)
+        self.equal = all(sn == self.S[0] for sn in self.S)
+        self._dev = {}
+
+    def prob0(self, H):
+        out = [0]
+        for sn in self.S:
+            out.append(out[-1] + H * sn * sn)
+        return out
+
+    def n_probs(self, H):
+        return H * sum(sn * sn for sn in self.S)
+
+    def on(self, device, H):
+        """-> dict(row0 int32 [N + 1], row0_64 int64 [N] (the CLS rows, for lstc_gather_rows), prob0 int64 [N + 1], launches
+        [(S of the launch, ids int32 or None, n_ids)]) on ``device``."""
+        key = (str(device), int(H), _ATTN_VAR_BUCKETS)
+        if key not in self._dev:
+            single = not _ATTN_VAR_BUCKETS or len(self.buckets) == 1
+            groups = [] if single else [(T, ids) for T, ids in sorted(self.buckets.items())]
+            flat = list(self.row0)
+            for _, ids in groups:
+                flat += ids
+            i32 = torch.tensor(flat, dtype=torch.int32).to(device)
+            i64 = torch.tensor(self.prob0(H) + self.row0[:-1], dtype=torch.int64).to(device)
+            launches, off = [], self.N + 1
+            for _, ids in groups:
+                launches.append((max(self.S[n] for n in ids), i32[off: off + len(ids)], len(ids)))
+                off += len(ids)
+            if single:
+                launches = [(self.S_max, None, self.N)]
+            self._dev[key] = dict(row0=i32[: self.N + 1], prob0=i64[: self.N + 1], row0_64=i64[self.N + 1:], launches=launches)
+        return self._dev[key]
+
+
+def unpadded_layout(lengths, max_tokens=UNPADDED_MAX_TOKENS):
+    """Host lengths (a Python sequence or a CPU tensor of N integers: patch tokens per sequence, the CLS token not counted) ->
+    ``SeqLayout``.  Range-checked with ValueError before anything touches a device: integers, at least one sequence, 1 <= L_n and
+    L_n + 1 <= ``max_tokens`` (128 tokens, the attention kernels' LDS tile).  A device tensor is refused: the size of the output
+    depends on the sum of the lengths, so there is no device-lengths form.  Pure Python."""
+    if torch.is_tensor(lengths):
+        if lengths.is_cuda:
+            raise ValueError("unpadded lengths must live on the host (the output size depends on their sum): pass a list or a CPU tensor")
+        if lengths.dim() != 1:
+            raise ValueError(f"lengths: expected a 1-D tensor, got shape {tuple(lengths.shape)}")
+        if lengths.is_floating_point() or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths: expected integers, got {lengths.dtype}")
+        host = [int(v) for v in lengths.tolist()]
+    else:
+        host = list(lengths)
+        if any(isinstance(v, bool) or int(v) != v for v in host):
+            raise ValueError("lengths: expected integers")
+        host = [int(v) for v in host]
+    if not host:
+        raise ValueError("lengths: expected at least one sequence")
+    bad = [(n, v) for n, v in enumerate(host) if not 1 <= v <= max_tokens - 1]
+    if bad:
+        raise ValueError(f"lengths: every sequence needs 1 <= length <= {max_tokens - 1} patch tokens (at most {max_tokens} tokens "
+                         f"with the CLS token on the unpadded route); got length {bad[0][1]} for sequence {bad[0][0]}")
+    return SeqLayout(host)
+
+
+def _attn_var_desc(q, k, v, H, dk, dv, table, index, p_drop, seed):
+    d = AttnDesc()
+    d.N, d.H, d.dk, d.dv = 1, H, dk, dv
+    d.ldq, d.ldk, d.ldv = q.stride(0), k.stride(0), v.stride(0)
+    d.dtype = F32                   # exact-f32 products in every compute mode
+    if table is not None:
+        d.index_ld, d.table_rows = index.shape[1], table.shape[0]
+        d.table, d.index = dev_ptr(table), dev_ptr(index)
+    d.scale = 1.0 / (dk ** 0.5)
+    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
+    d.Q, d.K, d.V = dev_ptr(q), dev_ptr(k), dev_ptr(v)
+    return d
+
+
+def attn_var_fwd(q, k, v, lay: SeqLayout, H, dk, dv, table, index, p_drop, seed, out=None, probs=None):
+    """The attention core over an unpadded batch (lstc_attn_var_fwd): q, k, v [M, ld] row operands, ``lay`` the batch's layout.
+    One launch instantiated for the longest sequence (``_ATTN_VAR_BUCKETS``: one per tile count present in the batch).
+    Returns (o [M, H*dv], probs: the flat ragged buffer, sequence n's [H, S_n, S_n] block from ``lay.prob0(H)[n]``)."""
+    dev = q.device
+    t = lay.on(dev, H)
+    npr = lay.n_probs(H)
+    o = torch.empty((lay.M, H * dv), device=dev, dtype=torch.float32) if out is None else out
+    probs = torch.empty((npr,), device=dev, dtype=torch.float32) if probs is None else probs
+    d = _attn_var_desc(q, k, v, H, dk, dv, table, index, p_drop, seed)
+    d.ldo, d.O, d.probs = o.stride(0), dev_ptr(o), dev_ptr(probs)
+    for S, ids, n_ids in t["launches"]:
+        d.S = S
+        sq = _lib.Seqs(dev_ptr(t["row0"]), dev_ptr(t["prob0"]), dev_ptr(ids), n_ids, npr)
+        check(_lib.load().lstc_attn_var_fwd(C.byref(d), C.byref(sq), stream_ptr()), "lstc_attn_var_fwd")
+    return o, probs
+
+
+def attn_var_bwd(do, q, k, v, probs, lay: SeqLayout, H, dk, dv, table, index, p_drop, seed, out=None):
+    """Backward of ``attn_var_fwd`` (lstc_attn_var_bwd) -> dq, dk, dv (row strides of q, k, v), dtable.  The bias-table gradient
+    is written as partial tables, one per chunk of each launch's sequences, and summed in a fixed order: no float atomics."""
+    dev = q.device
+    t = lay.on(dev, H)
+    dq, dk_, dv_ = out if out is not None else (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
+    if not (dq.stride(0) == q.stride(0) and dk_.stride(0) == k.stride(0) and dv_.stride(0) == v.stride(0)):
+        raise RuntimeError("attn_var_bwd: dQ / dK / dV must have the row strides of Q / K / V")
+    d = _attn_var_desc(q, k, v, H, dk, dv, table, index, p_drop, seed)
+    d.ldo, d.dO, d.probs = do.stride(0), dev_ptr(do), dev_ptr(probs)
+    d.dQ, d.dK, d.dV = dev_ptr(dq), dev_ptr(dk_), dev_ptr(dv_)
+    chunks, parts = [], None
+    if table is not None:
+        for _, _, n_ids in t["launches"]:
+            npw = min(8, max(1, (n_ids * H + 4095) // 4096))
+            c = (n_ids + npw - 1) // npw
+            chunks.append((n_ids + ((n_ids + c - 1) // c) - 1) // ((n_ids + c - 1) // c))
+        parts = torch.empty((sum(chunks), table.shape[0] * H), device=dev, dtype=torch.float32)
+    first = 0
+    for i, (S, ids, n_ids) in enumerate(t["launches"]):
+        d.S = S
+        if parts is not None:
+            d.dtable, d.dtable_chunks = dev_ptr(parts[first:]), chunks[i]
+            first += chunks[i]
+        sq = _lib.Seqs(dev_ptr(t["row0"]), dev_ptr(t["prob0"]), dev_ptr(ids), n_ids, lay.n_probs(H))
+        check(_lib.load().lstc_attn_var_bwd(C.byref(d), C.byref(sq), stream_ptr()), "lstc_attn_var_bwd")
+    dtable = colsum(parts).view(table.shape[0], H) if parts is not None else None
+    return dq, dk_, dv_, dtable
+
+
 def _sdpa_operand(t):
     """A [b, H, l, d] operand of the rectangular attention as the kernels address it: any strides over (sequence, head, token),
     feature stride 1 - a copy only where that last one fails."""
@@ -1439,18 +1605,23 @@ class MHAFunction(torch.autograd.Function):
         if ctx.is_act:
             return MHAFunction._forward_act(ctx, x, wq, wk, wv, wfc, ln_w, ln_b, table, index, cfg)
         N, S, dm = x.shape
+        # unpadded batch (SeqLayout): x is [1, M, d] - every row-wise step sees one sequence of M rows, only the attention core
+        # knows what a sequence is
+        seqs = cfg.get("seqs")
+        if seqs is not None and ((N, S) != (1, seqs.M) or cfg.get("mask") is not None):
+            raise RuntimeError(f"MHAFunction: an unpadded batch is [1, M, d] = [1, {seqs.M}, d] without a mask, got {tuple(x.shape)}")
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
         training = cfg["training"]
         p_attn = cfg["attn_dropout"] if training else 0.0
         p_fc = cfg["fc_dropout"] if training else 0.0
-        dedup = _take_dedup_rows(x)    # exact-f32 mode, x straight from the fused gather + CLS concat: its distinct rows
+        dedup = _take_dedup_rows(x) if seqs is None else None    # exact-f32 mode, x straight from the fused gather + CLS concat: its distinct rows
         x2 = x.contiguous().view(N * S, dm)
         xp = maybe_pack(x2)            # f32x3: one pack of X feeds Q, K, V now and the three weight gradients later
         xa = xp if xp is not None else x2
         wqkv = _fused_qkv_weight(wq, wk, wv)
         qkv_p = None
         mask = cfg.get("mask")          # normalised attention mask (attn_mask_arg), not differentiable: row operands, masked kernels
-        if (mask is None and xp is not None and wqkv is not None and wqkv.shape[0] == H * (2 * dk + dv) and attn_packed_inputs(N, S, H, dk, dv) and
+        if (mask is None and seqs is None and xp is not None and wqkv is not None and wqkv.shape[0] == H * (2 * dk + dv) and attn_packed_inputs(N, S, H, dk, dv) and
                 packed_out_shape(N * S, wqkv.shape[0]) and packed_out_shape(N * S, H * dv) and wfc.shape[0] >= max(_x3_min[0], 1)):
             # bf16 mode: Q | K | V exist only as ONE packed bf16 operand - the projection writes it (LSTC_EPI_OUT_PACK), the attention
             # core reads it (forward and backward) and writes O / dQ | dK | dV as packs: no f32 activation between the two GEMMs
@@ -1482,11 +1653,14 @@ class MHAFunction(torch.autograd.Function):
             v = gemm(xa, wv, trans_b=True)
         seed_a = next_seed() if p_attn > 0 else 0
         seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:
-            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, S, S))
+        if p_attn > 0:      # unpadded: the counters run over the ragged probabilities buffer
+            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, S, S) if seqs is None else (seqs.n_probs(H),))
         if p_fc > 0:
             _note(cfg["site"] + "dropout", p_fc, seed_f, (N, S, dm))
-        if qkv_p is not None:
+        if seqs is not None:
+            o, probs = attn_var_fwd(q, k, v, seqs, H, dk, dv, table, index, p_attn, seed_a)
+            op = maybe_pack(o)
+        elif qkv_p is not None:
             op, probs = attn_fwd(qkv_p, None, None, N, S, H, dk, dv, table, index, p_attn, seed_a)
             o = None
         elif mask is None and xp is not None and attn_fwd_pack(N, S, H, dv) and wfc.shape[0] >= max(_x3_min[0], 1):
@@ -1516,6 +1690,7 @@ class MHAFunction(torch.autograd.Function):
         x2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs, y, mean, rstd = ctx.saved_tensors
         c = ctx.cfg
         N, S, H, dk, dv = c["N"], c["S"], c["n_head"], c["d_k"], c["d_v"]
+        seqs = c.get("seqs")
         dz2 = dz.contiguous().view(N * S, -1)
         dy, df, dln_w, dln_b, _ = layernorm_bwd_branch(dz2, y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"], False)
         xp, op = ctx.packs
@@ -1528,6 +1703,10 @@ class MHAFunction(torch.autograd.Function):
             rq, rk = wq.shape[0], wk.shape[0]
             if qkv_p is not None:
                 dqkv, _, _, dtable = attn_bwd(do, qkv_p, None, None, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"])
+            elif seqs is not None:
+                dqkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
+                outs = (dqkv[:, :rq], dqkv[:, rq: rq + rk], dqkv[:, rq + rk:])
+                _, _, _, dtable = attn_var_bwd(do, q, k, v, probs, seqs, H, dk, dv, table, index, c["p_attn"], c["seed_a"], out=outs)
             elif c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv) and N * S * wqkv.shape[0] * 2 < 2 ** 31:
                 # bf16 mode: the attention backward writes dQ | dK | dV straight into ONE packed bf16 operand
                 dqkv, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], packed="fused")
@@ -1541,9 +1720,12 @@ class MHAFunction(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = gemm(dqkv, wqkv, residual=dy).view(N, S, -1)   # dQ Wq + dK Wk + dV Wv + residual in one GEMM (K = 3*H*dk)
         else:
-            dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
-                                            packed=c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv),
-                                            mask=c.get("mask"))
+            if seqs is not None:
+                dq, dk_, dv_, dtable = attn_var_bwd(do, q, k, v, probs, seqs, H, dk, dv, table, index, c["p_attn"], c["seed_a"])
+            else:
+                dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
+                                                packed=c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv),
+                                                mask=c.get("mask"))
             dwq = deliver(wq, wgrad(dq, x2, xp, out=grad_sink(wq)))
             dwk = deliver(wk, wgrad(dk_, x2, xp, out=grad_sink(wk)))
             dwv = deliver(wv, wgrad(dv_, x2, xp, out=grad_sink(wv)))
@@ -1737,6 +1919,35 @@ def cls_outer(w1, u1, w2, u2, N, S, dm):
     return dx
 
 
+def cls_dot_var(u, x2, lay: "SeqLayout", mode, probs=None, p_drop=0.0, seed=0):
+    """``cls_dot`` over an unpadded X [M, d] (lstc_cls_dot_var): out / probs [N, H, S_max], exact zeros behind a sequence's keys."""
+    N, S, H, dm = lay.N, lay.S_max, u.shape[1], x2.shape[1]
+    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+    if mode == 1:
+        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+    check(_lib.load().lstc_cls_dot_var(dev_ptr(u), dev_ptr(x2), dev_ptr(lay.on(u.device, H)["row0"]), dev_ptr(out), dev_ptr(probs), N, S, H,
+                                       dm, mode, float(p_drop), int(seed), stream_ptr()), "lstc_cls_dot_var")
+    return out, probs
+
+
+def cls_wsum_var(w, x2, lay: "SeqLayout"):
+    N, S, H, dm = lay.N, lay.S_max, w.shape[1], x2.shape[1]
+    y = torch.empty((N, H, dm), device=w.device, dtype=torch.float32)
+    check(_lib.load().lstc_cls_wsum_var(dev_ptr(w), dev_ptr(x2), dev_ptr(lay.on(w.device, H)["row0"]), dev_ptr(y), N, S, H, dm,
+                                        stream_ptr()), "lstc_cls_wsum_var")
+    return y
+
+
+def cls_outer_var(w1, u1, w2, u2, add0, lay: "SeqLayout", dm):
+    """dX [M, d] of the unpadded batch (lstc_cls_outer_var); ``add0`` [N, d] or None joins each sequence's CLS row."""
+    H = w1.shape[1]
+    dx = torch.empty((lay.M, dm), device=w1.device, dtype=torch.float32)
+    check(_lib.load().lstc_cls_outer_var(dev_ptr(w1), dev_ptr(u1), dev_ptr(w2), dev_ptr(u2), dev_ptr(add0),
+                                         dev_ptr(lay.on(w1.device, H)["row0"]), dev_ptr(dx), lay.N, lay.S_max, H, dm, stream_ptr()),
+          "lstc_cls_outer_var")
+    return dx
+
+
 def unpack1_rows(pk: "Packed", row0: int = 0, step: int = 1, n: Optional[int] = None) -> torch.Tensor:
     """Rows ``row0 + i * step`` (i < n) of a packed bf16 operand as f32 [n, K] (lstc_unpack1_rows)."""
     if pk.kind != _lib.BF16P:
@@ -1795,7 +2006,12 @@ class MHAClsAssocFunction(torch.autograd.Function):
         # bf16 activation stream: x is the bf16 view of the pack of the last full layer's output (cfg["act_shape"]); the three
         # passes over X read the pack (half the bytes), the CLS rows come out of it widened
         xp = None
-        if x.dtype == torch.bfloat16:
+        seqs = cfg.get("seqs")          # unpadded batch (SeqLayout): x is [1, M, d], the three passes take the offset forms
+        if seqs is not None:
+            if x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[:2]) != (1, seqs.M):
+                raise RuntimeError(f"MHAClsAssocFunction: an unpadded batch is f32 [1, M, d] = [1, {seqs.M}, d], got {tuple(x.shape)}")
+            N, S, dm = seqs.N, seqs.S_max, x.shape[2]
+        elif x.dtype == torch.bfloat16:
             N, S, dm = cfg["act_shape"]
             xp = _act_pack(x, N * S, dm)
         else:
@@ -1805,7 +2021,10 @@ class MHAClsAssocFunction(torch.autograd.Function):
         p_attn = cfg["attn_dropout"] if training else 0.0
         p_fc = cfg["fc_dropout"] if training else 0.0
         ctx.table_shape = None if table is None else tuple(table.shape)
-        if xp is None:
+        if seqs is not None:
+            x = x.contiguous().view(seqs.M, dm)
+            xc = gather_rows(x, seqs.on(x.device, H)["row0_64"])       # the CLS rows [N, d]
+        elif xp is None:
             x = x.contiguous()
             xc = x[:, 0, :]
         else:
@@ -1821,7 +2040,10 @@ class MHAClsAssocFunction(torch.autograd.Function):
         if p_fc > 0:
             _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
         klen = cfg.get("key_lengths")
-        if klen is not None:
+        if seqs is not None:
+            pd, probs = cls_dot_var(u, x, seqs, 1, None, p_attn, seed_a)
+            xb = cls_wsum_var(pd, x, seqs)
+        elif klen is not None:
             if xp is not None:
                 raise RuntimeError("MHAClsAssocFunction: key lengths need the f32 activations")
             pd, probs = cls_dot_len(u, x, klen, 1, None, p_attn, seed_a)
@@ -1841,7 +2063,7 @@ class MHAClsAssocFunction(torch.autograd.Function):
             z, mean, rstd = y, None, None
         ctx.cfg = dict(cfg, N=N, S=S, dm=dm, is_act=xp is not None, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, scale=scale)
         ctx.save_for_backward(x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y if cfg["layer_norm"] else None, mean, rstd,
-                              xc if xp is not None else None)
+                              xc if (xp is not None or seqs is not None) else None)
         return z
 
     @staticmethod
@@ -1852,7 +2074,8 @@ class MHAClsAssocFunction(torch.autograd.Function):
         N, S, H, dk, dv, scale = c["N"], c["S"], c["n_head"], c["d_k"], c["d_v"], c["scale"]
         dm = c["dm"]
         xp = _act_pack(x, N * S, dm) if c["is_act"] else None
-        xc = xc_saved if xp is not None else x[:, 0, :]
+        seqs = c.get("seqs")
+        xc = xc_saved if xc_saved is not None else x[:, 0, :]
         dz = dz.contiguous()
         dln_w = dln_b = None
         if c["layer_norm"]:
@@ -1867,7 +2090,10 @@ class MHAClsAssocFunction(torch.autograd.Function):
         dwv = grad_sink(wv)
         dwv = torch.empty_like(wv) if dwv is None else dwv
         gemm_batched(doc, xb, dwv, dv, dm, N, H * dv, H * dm, dm, True, False, H, dv, dm, dv * dm)
-        if c.get("key_lengths") is not None:
+        if seqs is not None:
+            ds, _ = cls_dot_var(dxb, x, seqs, 2, probs, c["p_attn"], c["seed_a"])
+            du = cls_wsum_var(ds, x, seqs)
+        elif c.get("key_lengths") is not None:
             ds, _ = cls_dot_len(dxb, x, c["key_lengths"], 2, probs, c["p_attn"], c["seed_a"])
             du = cls_wsum(ds, x)
         elif xp is None:
@@ -1884,7 +2110,9 @@ class MHAClsAssocFunction(torch.autograd.Function):
         dwq = wgrad(dqc, xc, out=grad_sink(wq))
         dx = None
         if ctx.needs_input_grad[0]:
-            if xp is None:
+            if seqs is not None:      # the CLS rows' own terms dQ Wq + residual join row 0 of each sequence inside the pass: one writer per row
+                dx = cls_outer_var(pd, dxb, ds, u, gemm(dqc, wq, residual=dy), seqs, dm).view(1, seqs.M, dm)
+            elif xp is None:
                 dx = cls_outer(pd, dxb, ds, u, N, S, dm)                                  # K/V paths, every token
                 gemm(dqc, wq, out=dx[:, 0, :], accumulate=True, residual=dy)              # CLS rows: + dQ Wq + residual
             else:       # the gradient goes back as a pack; the CLS rows' own terms join row 0 before the one rounding
@@ -2281,6 +2509,48 @@ class ClsConcatLenFunction(torch.autograd.Function):
         if pos_shape is not None:
             dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
             dpos[0, :S] = tok
+        return dx, dcls, dpos, None
+
+
+class ClsConcatVarFunction(torch.autograd.Function):
+    """``ClsConcatFunction`` unpadded in and unpadded out: ``x`` [sum L_n, d] holds the patch tokens of the sequences back to back,
+    the result [M, d] each sequence's CLS row (the mean of its own tokens, or the learned token) and its tokens behind it, the
+    position table added on rows 0..L_n of every sequence (lstc_cls_concat_var_fwd / _bwd).  ``lay``: the batch's ``SeqLayout``."""
+
+    @staticmethod
+    def forward(ctx, x, cls_token, pos, lay):
+        if x.dim() != 2 or x.shape[0] != lay.in0[-1]:
+            raise ValueError(f"ClsConcatVarFunction: expected x [sum of lengths, d] = [{lay.in0[-1]}, d], got {tuple(x.shape)}")
+        dm = x.shape[1]
+        x = x.contiguous()
+        row0 = lay.on(x.device, 0)["row0"]
+        y = torch.empty((lay.M, dm), device=x.device, dtype=torch.float32)
+        pos_s = pos[0, :lay.S_max].contiguous() if pos is not None else None
+        cls_v = cls_token.reshape(-1) if cls_token is not None else None
+        check(_lib.load().lstc_cls_concat_var_fwd(dev_ptr(x), dev_ptr(row0), dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y), lay.N, dm,
+                                                  stream_ptr()), "lstc_cls_concat_var_fwd")
+        ctx.lay, ctx.row0 = lay, row0
+        ctx.meta = (dm, cls_token is not None, pos.shape if pos is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dm, learned, pos_shape = ctx.meta
+        lay = ctx.lay
+        dy = dy.contiguous()
+        dx = dcls = dpos = tok = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((lay.in0[-1], dm), device=dy.device, dtype=torch.float32)
+        if learned or pos_shape is not None:
+            tok = torch.empty((lay.S_max, dm), device=dy.device, dtype=torch.float32)
+        if dx is not None or tok is not None:
+            check(_lib.load().lstc_cls_concat_var_bwd(dev_ptr(dy), dev_ptr(ctx.row0), dev_ptr(dx), dev_ptr(tok), lay.N, lay.S_max, dm,
+                                                      int(not learned), stream_ptr()), "lstc_cls_concat_var_bwd")
+        if learned:
+            dcls = tok[0].clone().view(1, 1, dm)
+        if pos_shape is not None:
+            dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
+            dpos[0, :lay.S_max] = tok
         return dx, dcls, dpos, None
 
 

@@ -2,8 +2,8 @@
 import torch
 from torch import nn
 
-from ..functional import (ClsConcatFunction, ClsConcatLenFunction, DropoutFunction, LayerNormFunction, PackedAct, act_chain_ok,
-                          drop_producer_packs, lengths_arg)
+from ..functional import (ClsConcatFunction, ClsConcatLenFunction, ClsConcatVarFunction, DropoutFunction, LayerNormFunction, PackedAct,
+                          act_chain_ok, drop_producer_packs, lengths_arg, unpadded_layout)
 from .EncoderLayer import EncoderLayer
 from .MultiHeadAttention import key_padding_mask
 
@@ -184,6 +184,82 @@ class Encoder(nn.Module):
             layer.slf_attn._act16_out, layer.pos_ffn._act16_out = act, act and (i + 1 < n - 1 or cls_pack)
             enc_output = layer(enc_output, slf_attn_mask=src_mask)[0]
         out = self.layer_stack[-1].forward_cls(enc_output, slf_attn_mask=src_mask)
+        drop_producer_packs()
+        return out
+
+    def _unpadded(self, x, lengths, enc_output_hi=None, src_mask=None, return_attn=False, return_attn_v=False):
+        """An unpadded batch: refuse what the route does not take and check the lengths -> functional.SeqLayout.  Every refusal is
+        raised before any launch, and before the input's device matters."""
+        if src_mask is not None or return_attn or return_attn_v:
+            raise NotImplementedError("Encoder: the unpadded route takes no src_mask and returns no attention probabilities "
+                                      "(they are ragged); use forward(x, lengths=...) on a padded batch")
+        if isinstance(x, PackedAct):
+            raise NotImplementedError("Encoder: an unpadded batch needs f32 activations (no PackedAct input)")
+        if isinstance(x, tuple):
+            raise ValueError("Encoder: a gather spec cannot feed the unpadded route (materialise the tokens first)")
+        if enc_output_hi is not None:
+            raise ValueError("Encoder: an unpadded batch is one matrix: concatenate enc_output and enc_output_hi first")
+        if x.dim() != 2:
+            raise ValueError(f"Encoder: an unpadded batch is [sum of lengths, d_model], got {tuple(x.shape)}")
+        lay = unpadded_layout(lengths)
+        if lay.in0[-1] != x.shape[0]:
+            raise ValueError(f"Encoder: the lengths sum to {lay.in0[-1]} tokens, the input has {x.shape[0]} rows")
+        attn0 = self.layer_stack[0].slf_attn
+        if attn0.relative_pe_2D and any(v != attn0.window_size ** 2 for v in lay.lengths):
+            raise ValueError(f"Encoder: relative_pe_2D needs window_size**2 = {attn0.window_size ** 2} patch tokens in every sequence")
+        if (attn0.relative_pe or attn0.relative_pe_2D) and lay.S_max - 1 > attn0.relative_position_index.shape[0]:
+            raise ValueError(f"Encoder: {lay.S_max - 1} patch tokens exceed the relative position index "
+                             f"({attn0.relative_position_index.shape[0]} tokens)")
+        if self.position_encoding and lay.S_max > self.position_enc.shape[1]:
+            raise ValueError(f"Encoder: {lay.S_max} tokens exceed max_position_tokens = {self.position_enc.shape[1]}")
+        if not x.is_cuda:
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        return lay
+
+    def _embed_unpadded(self, x, lay):
+        """``_embed`` of an unpadded batch -> [1, M, d_model]: the input LayerNorm is row-wise, the concat knows the offsets."""
+        if self.input_layerNorm:
+            x = LayerNormFunction.apply(x, self.layer_norm.weight, self.layer_norm.bias)
+        x = ClsConcatVarFunction.apply(x, self.cls_token if self.CLS_learned else None,
+                                       self.position_enc if self.position_encoding else None, lay)
+        if self.position_encoding and self.training and self.position_dropout.p > 0:
+            x = DropoutFunction.apply(x, self.position_dropout.p, "position_dropout")
+        return x.view(1, lay.M, -1)
+
+    def forward_unpadded(self, enc_output, lengths, src_mask=None, return_attn=False, return_attn_v=False):
+        """``forward`` of an UNPADDED batch: ``enc_output`` [sum L_n, d_model] holds the patch tokens of N sequences back to back,
+        ``lengths`` (a Python sequence or a CPU tensor of N integers; on the host, because the output size depends on their sum)
+        their token counts L_n, 1 <= L_n <= 127.  Returns [M, d_model], M = sum (L_n + 1): rows ``row0[n] .. row0[n] + L_n`` (row0 =
+        the running sum of L_n + 1) are what ``forward(x_n[None])`` returns for sequence n alone, in ``eval()`` and in training with
+        every dropout rate 0.  With dropout on, the counters run over the unpadded rows and the ragged probabilities: a valid draw,
+        but not the draw the sequence would have got alone.  The GEMMs, LayerNorm, FFN, dropout and residual run on the M real
+        rows; the attention core and the CLS concat run over the sequence offsets (lstc_attn_var_*, lstc_cls_concat_var_*).
+        Refused before any launch: ``src_mask``, ``return_attn``, ``return_attn_v`` (NotImplementedError), a gather spec, a
+        PackedAct, ``relative_pe_2D`` unless every length is window_size**2, a sequence above 128 tokens, beyond the relative
+        index or beyond ``max_position_tokens`` (ValueError).  The bf16 activation stream, packed attention operands and the layer-0
+        distinct-rows path are off, as with a mask."""
+        lay = self._unpadded(enc_output, lengths, None, src_mask, return_attn, return_attn_v)
+        h = self._embed_unpadded(enc_output, lay)
+        for i, layer in enumerate(self.layer_stack):
+            layer.pos_ffn._emit_pack = i + 1 < len(self.layer_stack)
+            layer.slf_attn._act16_out = layer.pos_ffn._act16_out = False
+            h = layer(h, seqs=lay)[0]
+        drop_producer_packs()
+        return h.view(lay.M, -1)
+
+    def forward_cls_unpadded(self, enc_output, lengths, enc_output_hi=None, src_mask=None):
+        """``forward_unpadded(x, lengths)[row0[:-1]]`` -> [N, d_model], the CLS row of every sequence, without computing the other
+        rows of the last layer: its re-associated form over sequence offsets where it applies (``_cls_assoc_ok``), else the full
+        block and a gather of the CLS rows.  Row n is what ``forward_cls(x_n[None])`` returns for sequence n alone; in exact-f32
+        ``eval()`` bit for bit.  Arguments and refusals as in ``forward_unpadded``."""
+        lay = self._unpadded(enc_output, lengths, enc_output_hi, src_mask)
+        h = self._embed_unpadded(enc_output, lay)
+        n = len(self.layer_stack)
+        for i, layer in enumerate(self.layer_stack[:-1]):
+            layer.pos_ffn._emit_pack = i + 1 < n - 1
+            layer.slf_attn._act16_out = layer.pos_ffn._act16_out = False
+            h = layer(h, seqs=lay)[0]
+        out = self.layer_stack[-1].forward_cls(h, seqs=lay)
         drop_producer_packs()
         return out
 

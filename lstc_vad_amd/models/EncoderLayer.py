@@ -19,17 +19,24 @@ class EncoderLayer(nn.Module):
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=FFN_dropout, layerNorm=FFN_layerNorm)
         self.FFN_need = FFN_need
 
-    def forward(self, enc_input, slf_attn_mask=None, return_attn=False, return_attn_v=False):
+    def forward(self, enc_input, slf_attn_mask=None, return_attn=False, return_attn_v=False, seqs=None):
+        """``seqs``: an unpadded batch (functional.SeqLayout), ``enc_input`` [1, M, d]; see MultiHeadAttention.forward."""
+        if seqs is not None:
+            res = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask, return_attn=return_attn,
+                                return_attn_v=return_attn_v, seqs=seqs)
+            return (self.pos_ffn(res[0]) if self.FFN_need else res[0],) + tuple(res[1:])
         res = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask, return_attn=return_attn,
                             return_attn_v=return_attn_v)
         enc_output = self.pos_ffn(res[0]) if self.FFN_need else res[0]
         return (enc_output,) + tuple(res[1:])
 
-    def forward_cls(self, enc_input, slf_attn_mask=None, key_lengths=None):
+    def forward_cls(self, enc_input, slf_attn_mask=None, key_lengths=None, seqs=None):
         """Last-layer shortcut: returns only the CLS row [N, d]; attention output projection and FFN run on N rows
         instead of N*S (the rest of the layer's output is never read by the train loops).  ``key_lengths``: a padded batch
-        (MultiHeadAttention.forward_cls)."""
-        if key_lengths is None:
+        (MultiHeadAttention.forward_cls); ``seqs``: an unpadded one, ``enc_input`` [1, M, d]."""
+        if seqs is not None:
+            out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask, seqs=seqs)
+        elif key_lengths is None:
             out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask)
         else:
             out = self.slf_attn.forward_cls(enc_input, mask=slf_attn_mask, key_lengths=key_lengths)

@@ -8,8 +8,8 @@ arithmetic runs in ``MHAFunction`` (GEMM -> fused attention core -> GEMM epilogu
 import torch
 from torch import nn
 
-from ..functional import (MHAClsAssocFunction, MHAClsFunction, MHACrossFunction, MHAFunction, PackedAct, SDPAFunction, attn_mask_arg, dropout_apply,
-                          next_seed)
+from ..functional import (GatherRowsFunction, MHAClsAssocFunction, MHAClsFunction, MHACrossFunction, MHAFunction, PackedAct, SDPAFunction,
+                          attn_mask_arg, dropout_apply, next_seed)
 
 
 def relative_position_index_3d(window_depth: int, window_size: int) -> torch.Tensor:
@@ -130,8 +130,11 @@ class MultiHeadAttention(nn.Module):
         from ..functional import cls_pack_ok
         return self._cls_assoc_ok(S) and cls_pack_ok(N, S, self.n_head, self.d_model)
 
-    def forward_cls(self, x, mask=None, key_lengths=None):
+    def forward_cls(self, x, mask=None, key_lengths=None, seqs=None):
         """CLS-query attention for the last encoder layer: x [N, S, d] -> [N, d] (== ``forward(x, x, x, mask)[0][:, 0]``).
+        ``seqs``: an unpadded batch (functional.SeqLayout), x [1, M, d] -> [N, d], the CLS row of every sequence: the re-associated
+        form over sequence offsets (lstc_cls_dot_var ...) where ``_cls_assoc_ok`` holds, else the whole block on the M rows and a
+        gather of its CLS rows (correct, slower; no kernel of its own).  No mask, no key lengths, f32 activations.
         ``mask`` as in ``forward``; only its query row 0 is read.
         ``key_lengths``: int32 [N] on the device, the keys of each sequence of a padded batch (the CLS token counted, 1..S; the
         kernels clamp): keys beyond them do not exist.  Alone, and where the re-associated form applies (``_cls_assoc_ok``), it
@@ -140,7 +143,15 @@ class MultiHeadAttention(nn.Module):
         cfg = dict(n_head=self.n_head, d_k=self.d_k, d_v=self.d_v, layer_norm=self.layerNorm_flag,
                    attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
                    site=self._site)
-        if key_lengths is not None:
+        if seqs is not None:
+            if mask is not None or key_lengths is not None or isinstance(x, PackedAct):
+                raise NotImplementedError("an unpadded batch takes no mask, no key lengths and f32 activations")
+            if not self._cls_assoc_ok(seqs.S_max):
+                full = self.forward(x, x, x, seqs=seqs)[0]
+                return GatherRowsFunction.apply(full.view(seqs.M, -1), seqs.on(x.device, self.n_head)["row0_64"])
+            cfg.update(seqs=seqs)
+            fn = MHAClsAssocFunction
+        elif key_lengths is not None:
             if isinstance(x, PackedAct):
                 raise NotImplementedError("key lengths need the f32 activations (Encoder keeps the bf16 stream off when lengths are given)")
             if mask is None and self._cls_assoc_ok(x.shape[1]):
@@ -168,18 +179,27 @@ class MultiHeadAttention(nn.Module):
                                     self.relative_position_bias_table if (self.relative_pe or self.relative_pe_2D) else None,
                                     cfg)
 
-    def forward(self, q, k, v, mask=None, return_attn=False, return_attn_v=False):
+    def forward(self, q, k, v, mask=None, return_attn=False, return_attn_v=False, seqs=None):
         """``mask``: anything torch broadcasts against [N, H, S, S], any dtype, zero = masked (reference :105-106: the logit of a
-        masked position is -1e9 before the relative bias and the softmax; a fully masked row comes out uniform)."""
+        masked position is -1e9 before the relative bias and the softmax; a fully masked row comes out uniform).
+        ``seqs``: an unpadded batch (functional.SeqLayout): q [1, M, d] holds the tokens of all sequences back to back and the
+        attention core runs over the sequence offsets (lstc_attn_var_fwd / _bwd); everything else is row-wise and runs as it does
+        on M rows.  No mask, no returned probabilities (they are ragged), f32 activations; the caller (Encoder) has checked the
+        lengths against the relative index."""
         if not (q is k and k is v):
             raise NotImplementedError("only self-attention (q is k is v) here: three different inputs, with lengths of their own, "
                                       "go through forward_cross")
         has_bias = self.relative_pe or self.relative_pe_2D
-        if self.relative_pe_2D and q.shape[1] - 1 != self.window_size ** 2:
+        if seqs is not None:
+            if mask is not None or return_attn or return_attn_v or isinstance(q, PackedAct):
+                raise NotImplementedError("an unpadded batch takes no mask, returns no probabilities and needs f32 activations")
+        elif self.relative_pe_2D and q.shape[1] - 1 != self.window_size ** 2:
             raise RuntimeError("relative_pe_2D needs window_size**2 patch tokens (models/MultiHeadAttention.py:114)")
         cfg = dict(n_head=self.n_head, d_k=self.d_k, d_v=self.d_v, layer_norm=self.layerNorm_flag,
                    attn_dropout=self.attn_dropout.p, fc_dropout=self.dropout.p, training=self.training,
                    site=self._site)
+        if seqs is not None:
+            cfg.update(seqs=seqs)
         act = isinstance(q, PackedAct)
         if mask is not None:
             if act:

@@ -105,7 +105,7 @@ class _ScoreBoard:
         if not self.pool:
             return
         sc = scoring.ltn_sequence_scores(self.enc, self.head, [q for _, seqs in self.pool for q in seqs],
-                                         **({"ragged": True} if self.ragged else {}))
+                                         **({"ragged": self.ragged} if self.ragged else {}))
         o = 0
         for off, seqs in self.pool:
             self.parts.append((off, sc[o:o + len(seqs)]))
@@ -139,7 +139,8 @@ def generate_pseudo_labels(enc, head, mode, dataset, dataset_path, training_txt,
                            rank=None, world=None, group=None, exchange=None, ragged=False):
     """mode 'STN' | 'LTN'; dataset 'SHT' | 'UCF' | 'UBnormal'.  Returns the dict (and writes it when ``out_path`` - on rank 0
     only under several ranks; every rank returns the complete dict).  ``ragged``: the pooled LTN parts of all lengths (the short
-    tail parts of ``tail='short'``) share padded batches (scoring.ltn_sequence_scores)."""
+    tail parts of ``tail='short'``) share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: they share batches without
+    padding (parts of at most 127 patch tokens)."""
     device = next(enc.parameters()).device
     d_model = d_model or enc.layer_norm.normalized_shape[0]
     rank, world = _ranks(rank, world, group)
@@ -188,7 +189,7 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
     """``masks``: directory of ``<video>.npy`` frame masks (SHT / UBnormal, ``--test_mask_dir``) or the ground-truth
     archive (UCF, ``--test_mask_path``).  LTN only scores parts; STN scores clips (in-loop evaluation of the spatio
     scripts, Train/spatio_transformer_shanghaitech.py:118-150: every clip's score x segment_len).  ``ragged``: pooled LTN
-    parts of all lengths share padded batches (scoring.ltn_sequence_scores)."""
+    parts of all lengths share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: batches without padding."""
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
     board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged)

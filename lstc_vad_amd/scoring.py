@@ -49,13 +49,53 @@ def ragged_batches(seqs, max_batch=4096):
     return batches
 
 
+UNPADDED_ROWS_PER_SEQUENCE = 49      # 3 clips of 16 patches + the CLS token: the longest part of the LTN workloads
+
+
+def unpadded_batches(seqs, max_batch=4096, max_rows=None):
+    """The batches of ``ltn_sequence_scores(ragged="unpadded")``: consecutive chunks of sequences of ANY lengths, concatenated
+    without padding -> [(ids, x [sum of lengths, d], lengths)] with ``ids`` the positions in ``seqs`` (input order) and
+    ``x`` the rows of ``seqs[ids[0]]``, ``seqs[ids[1]]``, ... back to back.  A chunk holds up to ``max_batch`` sequences and up to
+    ``max_rows`` rows with the CLS tokens counted (default ``49 * max_batch``: a full chunk of 3-clip parts at 16 patches, the
+    largest [N * S, d] the grouped path forms on the LTN workloads, so the activations of a chunk stay that size); a single
+    sequence always fits.  A sequence above 127 patch tokens (128 with the CLS token, the unpadded attention kernels' tile) raises
+    ValueError before anything is launched: score such a pool with ``ragged=True``.  Pure torch; runs on CPU tensors."""
+    max_rows = UNPADDED_ROWS_PER_SEQUENCE * max_batch if max_rows is None else max_rows
+    for i, s in enumerate(seqs):
+        if s.shape[0] + 1 > 128:
+            raise ValueError(f"ragged='unpadded': sequence {i} has {s.shape[0]} patch tokens, the unpadded route takes at most 127 "
+                             "(128 tokens with the CLS token); use ragged=True for this pool")
+    batches, ids, rows = [], [], 0
+    for i, s in enumerate(seqs):
+        r = int(s.shape[0]) + 1
+        if ids and (len(ids) >= max_batch or rows + r > max_rows):
+            batches.append(ids)
+            ids, rows = [], 0
+        ids.append(i)
+        rows += r
+    if ids:
+        batches.append(ids)
+    return [(ids, torch.cat([seqs[i] for i in ids], 0), [int(seqs[i].shape[0]) for i in ids]) for ids in batches]
+
+
 def ltn_sequence_scores(enc, head, seqs, max_batch=4096, ragged=False):
     """seqs: list of [len_i * P, d] tensors (any mix of videos) -> tensor [len(seqs)] of P(abnormal).  Same-length
     sequences share a batch of up to ``max_batch`` rows, so a whole test set is scored in a handful of launch sequences
     that fill the GPU like a training step does.
     ``ragged``: sequences of ALL lengths share batches instead - padded to the longest of the call and scored through
     ``Encoder.forward_cls(x, lengths=...)``, one launch chain per ``max_batch`` sequences rather than one per distinct length;
-    every score is what the sequence gets alone (up to float re-association), in input order."""
+    every score is what the sequence gets alone (up to float re-association), in input order.
+    ``ragged="unpadded"``: sequences of all lengths share batches WITHOUT padding - concatenated (``unpadded_batches``) and scored
+    through ``Encoder.forward_cls_unpadded``: one launch chain per chunk that costs the real tokens only.  Sequences of at most
+    127 patch tokens; a longer one raises before any launch."""
+    if isinstance(ragged, str) and ragged != "unpadded":
+        raise ValueError(f"ragged: expected False, True or 'unpadded', got {ragged!r}")
+    if ragged == "unpadded":
+        batches = unpadded_batches(seqs, max_batch)
+        out = torch.empty(len(seqs), device=seqs[0].device, dtype=torch.float32)
+        for ids, x, lengths in batches:
+            out[ids[0]:ids[-1] + 1] = head(enc.forward_cls_unpadded(x, lengths)).view(-1, 2)[:, 1]
+        return out
     out = torch.empty(len(seqs), device=seqs[0].device, dtype=torch.float32)
     if ragged:
         for ids, x, lengths in ragged_batches(seqs, max_batch):

@@ -6,8 +6,8 @@
 OBJECT names files of lstc_vad_amd/csrc without their suffix (gemm_f32, rowops, ...); the default is the attention files.
 Each tree must have been built with `make` (the per-file objects lstc_vad_amd/csrc/OBJECT.o are read: one offload bundle
 each).  Every kernel of OLD is looked up in NEW by its demangled name (key(): the two spellings of a masked instantiation count
-as one) and its disassembly compared as text after the addresses are stripped (instruction words and operands stay).  Exit
-status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
+as one, and so do an instantiation and its spelling with further template arguments `false` behind it) and its disassembly
+compared as text after the addresses are stripped (instruction words and operands stay).  Exit status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
 import os
 import re
 import subprocess
@@ -53,8 +53,10 @@ def demangle(syms):
 
 def key(dem):
     """One name per kernel whichever way its tree spells the masked instantiation: the demangled name without the parameter list,
-    with `X_masked_kernel<A>` (a twin of its own) and `X_kernel<A, true>` (a last template argument MASKED, which the NoMask in
-    the parameter list gives away) both as `X_kernel<A> [masked]`.  Every other kernel keeps its name.
+    with `X_masked_kernel<A>` (a twin of its own) and `X_kernel<A, true>` (a template argument MASKED, which the
+    `conditional<true, MaskParams, NoMask>` in the parameter list gives away) both as `X_kernel<A> [masked]`.  Trailing template
+    arguments `false` are dropped first (`X_kernel<A, false, false>` is `X_kernel<A>`): a parameter added behind the others with that
+    default leaves the old instantiations their names, and one that is `true` names a kernel of its own.  Every other kernel keeps its name.
     This leans on how the mangling spells MaskArg<MASKED> (csrc/attention_common.h): as
     `std::conditional<B, MaskParams, NoMask>::type`, so both instantiations name NoMask.  Another definition of MaskArg or
     another demangler would leave the template form unrecognised: its kernels then come out MISSING / NEW, never as a false pass."""
@@ -65,11 +67,16 @@ def key(dem):
             cut = i
             break
     name, params = dem[:cut], dem[cut:]
+    # a template parameter added behind the others with the default `false` (VAR of the attention and CLS kernels): the tree
+    # without it spells the same instantiation without the trailing `, false`; a `true` stays and names a kernel of its own
+    while name.endswith(", false>"):
+        name = name[:-len(", false>")] + ">"
     masked = False
-    if "NoMask" in params and name.endswith(">"):
-        m = re.match(r"^(.*), (true|false)>$", name)
+    which = re.search(r"conditional<(true|false), [^<>]*MaskParams", params)
+    if which and which.group(1) == "true":
+        m = re.match(r"^(.*), true>$", name)
         if m:
-            name, masked = m.group(1) + ">", m.group(2) == "true"
+            name, masked = m.group(1) + ">", True
     elif "_masked_kernel<" in name:
         name, masked = name.replace("_masked_kernel<", "_kernel<"), True
     return name + (" [masked]" if masked else "")
