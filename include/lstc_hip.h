@@ -586,10 +586,23 @@ int lstc_head_out_bwd(const float* x, const float* W, const float* out, const fl
  * l1 = mean(score[l1_skip:]) (flat slice quirk: l1_skip = bs*pn*L for STN, bs for LTN / co-teach).
  * Soft targets are built in-kernel (Train/temporal_transformer_shanghaitech.py:103-112): normal parts
  * [1,0]; abnormal parts t1 = mean over label_len pseudo labels, t0 = 1-t1.
- * Data-parallel: the hinge couples all bs_global x bs_global pairs, so ranks exchange bag maxima
+ * Data-parallel: the hinge couples all bs_global x bs_global pairs, so ranks exchange bag values
  * (2*bs_global floats, one sum-all-reduce) between phase 0 and phase 1; every other term is a local sum
  * divided by a global count.  scalars = rank-local contributions (their sum over ranks is the reference
  * value; on one GPU they are the reference values).
+ *
+ * Top-k bags (`topk`; the reference parses --topk and pools with torch.max, so this is the project's own extension):
+ *   pm[v,p] = mean_l score[v,p,l], float32, summed over l in ascending order (the sum the maximum above is taken over).
+ *   With k = topk (0 means 1) the selected set of video v is the first k parts in the order (pm descending, part index
+ *   ascending): ties go to the lower index.  bag[v] = (float32 sum of the selected pm, in that order) / (float)k; for k = 1
+ *   bag[v] is the selected pm itself, undivided - bit for bit the maximum above.  Hinge, l1, CE / BCE and the scalars are
+ *   unchanged.  d err / d pm[v,p] = gbag[v] / k on the selected parts and 0 elsewhere, i.e. gbag[v] / (k * score_len) on their
+ *   elements of dout.  Data parallel is unchanged: a rank contributes its own videos' bag values to the exchange, and a video's
+ *   bag does not depend on how the batch is split.
+ *   Limits for topk > 1: 1 <= topk <= part_num and part_num <= 64 (one part per lane of a wave64).  Checked before any launch:
+ *   topk < 0 LSTC_E_SHAPE; topk > part_num LSTC_E_RANGE; topk > 1 with part_num > 64 LSTC_E_RANGE.
+ *   NaN scores: k = 1 behaves as before (a NaN mean is never the maximum); for k > 1 the result is unspecified (a NaN mean
+ *   ranks last), the launch completes and writes only dout / bag / scalars.
  */
 typedef struct LstcLossDesc {
     int32_t mode;                   /* 0 STN, 1 LTN (MIL + CE), 2 STN co-teaching (MIL + BCE) */
@@ -606,11 +619,13 @@ typedef struct LstcLossDesc {
     const float* targets;           /* optional explicit soft targets [parts_local, 2] (parts = rows for mode 1,
                                        [2*bs_local*part_num] for mode 2); overrides abn_labels — used by the
                                        reference-named get_CE_loss / get_BCE_loss wrappers */
-    float* bag;                     /* [2*bs_global] bag maxima, normal half then abnormal half.  phase 0 writes this
+    float* bag;                     /* [2*bs_global] bag values, normal half then abnormal half.  phase 0 writes this
                                        rank's entries (caller zeroes first, then sum-all-reduces); phase 1 reads all */
     float* dout;                    /* same shape as `out`: d(rank's loss contribution)/d(out) */
     float* scalars;                 /* [5] loss, mil, err, l1, aux — this rank's contributions */
     int32_t phase;                  /* 0 = bags only; 1 = loss + gradient from `bag`; 2 = both (single rank) */
+    int32_t topk;                   /* parts pooled into a bag (see above); 0 (a zero-initialised descriptor) means 1.  Last
+                                       field, in what was the struct's tail padding: offset 108, sizeof stays 112 */
 } LstcLossDesc;
 
 int lstc_vad_loss(const LstcLossDesc* d, void* stream);

@@ -105,7 +105,7 @@ class LossDesc(C.Structure):
                 ("lambda_1", C.c_float), ("lambda_MIL", C.c_float), ("lambda_aux", C.c_float),
                 ("lambda_normal", C.c_float), ("lambda_abnormal", C.c_float),
                 ("out", C.c_void_p), ("abn_labels", C.c_void_p), ("targets", C.c_void_p), ("bag", C.c_void_p), ("dout", C.c_void_p),
-                ("scalars", C.c_void_p), ("phase", C.c_int32)]
+                ("scalars", C.c_void_p), ("phase", C.c_int32), ("topk", C.c_int32)]
 
 
 _lib = None

@@ -126,6 +126,10 @@ def build_parser(script: str) -> argparse.ArgumentParser:
     p.add_argument("--compute_dtype", type=str, default=os.environ.get("LSTC_COMPUTE_DTYPE", "fp32"), choices=["fp32", "f32x3", "bf16"],
                    help="GEMM arithmetic: fp32 = exact-f32 MFMA (reference numerics); f32x3 = f32-accurate products on the f16 "
                         "matrix cores (2x faster); bf16 = bf16 matrix cores on f32 storage (BASELINE configs 3 / 5)")
+    p.add_argument("--mil_topk", type=int, default=1,
+                   help="MIL bag score = mean of the K largest part means of a video (1 = the maximum, as the reference computes; "
+                        "1..part_num, part_num <= 64 above 1).  The reference's own --topk (default 7) still parses and still does "
+                        "nothing, as upstream: wiring it up would change every existing run")
     return p
 
 
@@ -329,7 +333,10 @@ def train(script: str, argv=None, args=None):
                           lambda_1=args.lambda_1, lambda_MIL=getattr(args, "lambda_MIL", 1.0),
                           lambda_CE=getattr(args, "lambda_CE", 0.0), lambda_BCE=getattr(args, "lambda_BCE", 1.0),
                           lambda_normal=getattr(args, "lambda_normal", 0.2), lambda_abnormal=getattr(args, "lambda_abnormal", 2.0),
-                          temporal_only=getattr(args, "temporal_only", False), clip_grad=getattr(args, "clip_grad", False))
+                          temporal_only=getattr(args, "temporal_only", False), clip_grad=getattr(args, "clip_grad", False),
+                          mil_topk=getattr(args, "mil_topk", 1))
+    if step_args.mil_topk != 1 and rank == 0:
+        logger.info("--mil_topk %d: a bag is the mean of its %d largest part means (of %d parts)" % (step_args.mil_topk, step_args.mil_topk, args.part_num))
     ts = TrainStep(step_args, mode, enc, head, _get(args, "lr_encoder", pre, 1e-4), lr_head, args.weight_decay)
 
     if script == "spatio_transformer_MIL_CE":

@@ -3,6 +3,8 @@
 // (Train/temporal_transformer_shanghaitech.py:29-31) and formats four device scalars per step (:143);
 // here one 256-thread workgroup does everything: the score vector is at most a few thousand floats, so
 // the kernel is latency-bound by construction and the design goal is simply "one launch, no host sync".
+// Top-k bags (LstcLossDesc.topk > 1; the contract is in include/lstc_hip.h, cost and history in DESIGN 3.4) are step 1's other
+// branch inside the same launch: a wavefront per video, a lane per part, topk wave arg-max rounds.
 #include "lstc_common.h"
 
 namespace {
@@ -16,10 +18,13 @@ struct LossParams {
 
 __device__ __forceinline__ float score_at(const LstcLossDesc& d, int c, int e) { return d.out[(size_t)e * c + (c - 1)]; }
 
+constexpr int TOPK_U = 4;     // videos a wavefront selects for side by side: independent chains that hide each other's shuffle latency
+
 __global__ void __launch_bounds__(NT) vad_loss_kernel(const LstcLossDesc d) {
     __shared__ float bag[MAXV];          // global bag vector (normal half, abnormal half)
     __shared__ float gbag[MAXV];         // d loss / d bag for this rank's videos (local numbering)
-    __shared__ int argp[MAXV];           // argmax part of this rank's videos
+    __shared__ int argp[MAXV];           // argmax part of this rank's videos (topk <= 1)
+    __shared__ unsigned long long selp[MAXV];   // bit p = part p is one of the topk selected parts of the video (topk > 1)
     __shared__ float red[NT / 64];
     const int c = d.mode == 1 ? 2 : 1;
     const int Ls = d.score_len, pn = d.part_num;
@@ -28,18 +33,64 @@ __global__ void __launch_bounds__(NT) vad_loss_kernel(const LstcLossDesc d) {
     const int bsg = d.bs_global, bsl = d.bs_local;
     const int nelem = nloc * rpv;                    // local score elements
 
-    // ---- 1. bag maxima + argmax of this rank's videos
-    for (int v = threadIdx.x; v < nloc; v += NT) {
-        float best = -INFINITY;
-        int bp = 0;
-        for (int p = 0; p < pn; ++p) {
-            float s = 0.f;
-            for (int l = 0; l < Ls; ++l) s += score_at(d, c, (v * pn + p) * Ls + l);
-            s = s / (float)Ls;
-            if (s > best) { best = s; bp = p; }
+    const int topk = d.topk;                         // <= 1: the maximum; > 1: mean of the topk largest part means (pn <= 64)
+    // ---- 1. bag values + selected parts of this rank's videos
+    if (topk > 1) {
+        // one wavefront per video, one part per lane: the part means are formed once, then topk rounds of a wave arg-max over
+        // the parts not yet taken - the wave maximum (wave_max: __shfl_xor butterfly), then the lowest free lane that holds it
+        // (ballot + find-first-set), so ties go to the lower index.  The selected means are summed in the order they are taken.
+        // A wavefront carries TOPK_U videos through the rounds at once; a slot past the last video selects nothing and writes nothing.
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const unsigned long long parts = pn >= 64 ? ~0ull : (1ull << pn) - 1ull;
+        for (int v0 = wave; v0 < nloc; v0 += (NT / 64) * TOPK_U) {
+            float key[TOPK_U], sum[TOPK_U];
+            unsigned long long avail[TOPK_U];              // wave-uniform: bit p = part p not yet taken
+#pragma unroll
+            for (int u = 0; u < TOPK_U; ++u) {
+                const int v = v0 + u * (NT / 64);
+                float pm = -INFINITY;
+                if (v < nloc && lane < pn) {
+                    float s = 0.f;
+                    for (int l = 0; l < Ls; ++l) s += score_at(d, c, (v * pn + lane) * Ls + l);
+                    pm = s / (float)Ls;
+                }
+                key[u] = pm == pm ? pm : -INFINITY;        // NaN ranks last: such a round takes the lowest free index
+                avail[u] = v < nloc ? parts : 0ull;
+                sum[u] = 0.f;
+            }
+            for (int r = 0; r < topk; ++r) {
+#pragma unroll
+                for (int u = 0; u < TOPK_U; ++u) {
+                    const bool mine = (avail[u] >> lane) & 1ull;
+                    const float m = wave_max(mine ? key[u] : -INFINITY);
+                    const unsigned long long hit = __ballot(mine && key[u] == m);
+                    const int bi = hit ? __ffsll((long long)hit) - 1 : 0;      // hit != 0 while a part is free (topk <= pn)
+                    sum[u] += m;
+                    avail[u] &= ~(1ull << bi);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < TOPK_U; ++u) {
+                const int v = v0 + u * (NT / 64);
+                if (v < nloc && lane == 0) {
+                    selp[v] = parts & ~avail[u];
+                    gbag[v] = sum[u] / (float)topk;      // temporarily holds the bag value
+                }
+            }
         }
-        argp[v] = bp;
-        gbag[v] = best;       // temporarily holds the bag value
+    } else {
+        for (int v = threadIdx.x; v < nloc; v += NT) {
+            float best = -INFINITY;
+            int bp = 0;
+            for (int p = 0; p < pn; ++p) {
+                float s = 0.f;
+                for (int l = 0; l < Ls; ++l) s += score_at(d, c, (v * pn + p) * Ls + l);
+                s = s / (float)Ls;
+                if (s > best) { best = s; bp = p; }
+            }
+            argp[v] = bp;
+            gbag[v] = best;       // temporarily holds the bag value
+        }
     }
     __syncthreads();
     if (d.phase == 0) {
@@ -93,7 +144,11 @@ __global__ void __launch_bounds__(NT) vad_loss_kernel(const LstcLossDesc d) {
         const int ge = v < bsl ? d.rank_off * rpv + e : bsg * rpv + d.rank_off * rpv + (e - bsl * rpv);
         const float sc = score_at(d, c, e);
         float g = 0.f;
-        if (part == argp[v]) g += gbag[v] / (float)Ls;
+        if (topk > 1) {
+            if ((selp[v] >> part) & 1ull) g += gbag[v] / ((float)topk * (float)Ls);
+        } else if (part == argp[v]) {
+            g += gbag[v] / (float)Ls;
+        }
         if (ge >= d.l1_skip) {
             l1 += sc;
             g += d.lambda_1 / n_l1;
@@ -163,7 +218,10 @@ extern "C" int lstc_vad_loss(const LstcLossDesc* d, void* stream) {
     if (d->phase == 2 && d->bs_local != d->bs_global) return LSTC_E_SHAPE;
     if (d->mode == 1 && d->score_len != 1) return LSTC_E_SHAPE;
     if (d->abn_labels && !d->targets && d->label_len <= 0) return LSTC_E_SHAPE;
+    if (d->topk < 0) return LSTC_E_SHAPE;
     if (2 * d->bs_global > MAXV) return LSTC_E_RANGE;
+    if (d->topk > d->part_num) return LSTC_E_RANGE;
+    if (d->topk > 1 && d->part_num > 64) return LSTC_E_RANGE;     // one part per lane of a wave64
     if (d->l1_skip < 0 || d->l1_skip >= 2 * d->bs_global * d->part_num * d->score_len) return LSTC_E_SHAPE;
     hipLaunchKernelGGL(vad_loss_kernel, 1, NT, 0, (hipStream_t)stream, *d);
     return lstc_launch_status();

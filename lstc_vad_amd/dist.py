@@ -6,7 +6,7 @@ the full encoder output (~822 MB) to GPU 0 and reduces the gradients there (SURV
 is its own process holding a replica; videos are sharded across ranks (sequences are independent through
 encoder and head), the loss kernel divides by GLOBAL counts, so the only exchange is
 
-  * 2*bs floats of bag maxima inside the loss (lstc_vad_amd.functional.VadLossFunction), and
+  * 2*bs floats of bag values (maxima, or top-k means under mil_topk) inside the loss (lstc_vad_amd.functional.VadLossFunction), and
   * a SUM all-reduce of the parameter gradients — bucketed per encoder layer in backward order and
     launched asynchronously from autograd hooks, so the reduction of layer i overlaps the backward
     of layers < i.  xGMI is point-to-point (7 links/GPU): a few large buckets (~130 MB each for the

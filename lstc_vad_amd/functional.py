@@ -2693,6 +2693,7 @@ class VadLossFunction(torch.autograd.Function):
         d.part_num, d.score_len, d.label_len, d.l1_skip = cfg["part_num"], cfg["score_len"], cfg["label_len"], cfg["l1_skip"]
         d.lambda_1, d.lambda_MIL, d.lambda_aux = cfg["lambda_1"], cfg["lambda_MIL"], cfg["lambda_aux"]
         d.lambda_normal, d.lambda_abnormal = cfg.get("lambda_normal", 0.0), cfg.get("lambda_abnormal", 0.0)
+        d.topk = cfg.get("topk", 1)
         dout = torch.empty_like(out)
         scalars = torch.empty((5,), device=dev, dtype=torch.float32)
         # the bag vector is an exchange buffer: only a rank-sharded batch needs it (zero-filled: the other ranks' slots are summed in)
@@ -2708,7 +2709,7 @@ class VadLossFunction(torch.autograd.Function):
             d.phase = 2
             check(lib.lstc_vad_loss(C.byref(d), stream_ptr()), "lstc_vad_loss")
         else:
-            # rank-sharded batch: phase 0 writes this rank's bag maxima into its slots of the zero-padded global vector,
+            # rank-sharded batch: phase 0 writes this rank's bag values into its slots of the zero-padded global vector,
             # the ranks SUM it (2*bs floats: the only coupling between ranks besides the gradient all-reduce), phase 1
             # evaluates the hinge of the local videos against the global vector.  ``cfg["exchange"]`` replaces the
             # collective in tests that emulate several ranks on one device.

@@ -21,6 +21,17 @@ def _dist_info(group=None):
     return 0, 1
 
 
+def _mil_topk(args):
+    """``args.mil_topk`` (absent: 1), checked against ``args.part_num`` before anything is launched: the bag of a video is the
+    mean of its ``mil_topk`` largest part means (include/lstc_hip.h, LstcLossDesc.topk); 1 is the reference's maximum."""
+    k, pn = getattr(args, "mil_topk", 1), args.part_num
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= pn:
+        raise ValueError(f"mil_topk must be an int in 1..part_num = 1..{pn}, got {k!r}")
+    if k > 1 and pn > 64:
+        raise ValueError(f"mil_topk = {k} > 1 needs part_num <= 64 (one part per lane of a wavefront), got part_num = {pn}")
+    return k
+
+
 def training_loss(args, mode: str, head_out: torch.Tensor, abnorm_labs=None, group=None, distributed=None, exchange=None):
     """Loss of one training step from the head output of THIS rank's sequences.
 
@@ -29,13 +40,15 @@ def training_loss(args, mode: str, head_out: torch.Tensor, abnorm_labs=None, gro
                 "STN_MIL_CE": Train/spatio_transformer_MIL_CE.py:176-181.
     ``args.batch_size`` is this rank's number of normal/abnormal pairs; under data parallelism the global
     batch is ``world_size * args.batch_size`` pairs and the hinge couples all of them.
+    ``args.mil_topk`` (absent: 1, the reference's maximum): a video's bag is the mean of its ``mil_topk`` largest part means
+    (DESIGN 3.4); the reference's own ``args.topk`` is not read, as upstream.
     ``distributed=(rank, world)`` overrides the process-group lookup and ``exchange(bag)`` the bag all-reduce (tests that
     emulate ranks on one device).  Returns ``(loss, scalars)`` with scalars = [loss, MIL, err, l1, aux] (rank-local
     contributions: summing them over ranks gives the single-process values)."""
     rank, world = _dist_info(group) if distributed is None else distributed
     bs_l, pn, L = args.batch_size, args.part_num, args.part_len
     bs_g = bs_l * world
-    cfg = dict(bs_global=bs_g, bs_local=bs_l, rank_off=rank * bs_l, part_num=pn, label_len=L,
+    cfg = dict(bs_global=bs_g, bs_local=bs_l, rank_off=rank * bs_l, part_num=pn, label_len=L, topk=_mil_topk(args),
                lambda_1=float(args.lambda_1), lambda_normal=0.0, lambda_abnormal=0.0, group=group, exchange=exchange)
     if mode == "LTN":
         use_ce = not getattr(args, "temporal_only", False)
@@ -62,11 +75,12 @@ def get_MIL_loss(args, y_pred, part_len=None):
     (Train/temporal_transformer_shanghaitech.py:25-36) and co-teaching ``get_MIL_loss(args, y, part_len)``
     (Train/spatio_transformer_MIL_CE.py:32-44).  ``y_pred[batch_size:]`` slices the first dim, as upstream."""
     bs, pn = args.batch_size, args.part_num
+    topk = _mil_topk(args)
     per_video = y_pred.numel() // (2 * bs)
     L = part_len if part_len is not None else per_video // pn
     skip = bs * (y_pred.numel() // y_pred.shape[0])
     cfg = dict(mode=MODE_STN, bs_global=bs, bs_local=bs, rank_off=0, part_num=pn, score_len=L, label_len=L,
-               l1_skip=skip, lambda_1=float(args.lambda_1), lambda_MIL=1.0, lambda_aux=0.0)
+               l1_skip=skip, lambda_1=float(args.lambda_1), lambda_MIL=1.0, lambda_aux=0.0, topk=topk)
     loss, sc = VadLossFunction.apply(y_pred.reshape(-1, 1), None, None, cfg)
     return loss, sc[2], sc[3]
 
