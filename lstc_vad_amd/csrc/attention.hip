@@ -1885,114 +1885,91 @@ int assoc_check(const void* a, const void* b, const void* c, int64_t N, int S, i
         else hipLaunchKernelGGL((KERN<16, VAR>), __VA_ARGS__);                          \
     } while (0)
 
+// The three f32 passes, one launcher each for every sequence layout: fixed S, LEN (`tab` = klen [N]) and VAR (`tab` = row0 [N + 1],
+// S = S_max).  `own` is the entry point's own refusal (0: none); it ranks behind the operand checks all layouts share.
+template <bool LEN, bool VAR>
+int launch_cls_dot(const float* U, const float* X, const int32_t* tab, float* out, float* probs, int64_t N, int32_t S, int32_t H,
+                   int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream, int own) {
+    int rc = assoc_check(U, X, out, N, S, H, d);
+    if (rc) return rc;
+    if (own) return own;
+    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
+    if (mode != 0 && !probs) return LSTC_E_NULL;
+    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
+    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
+    if (lds > 96 * 1024) return LSTC_E_RANGE;
+    const DropKey dk = make_drop_key(dropout_p, seed);
+    const int has_drop = dropout_p > 0.f;
+    const dim3 grid((unsigned)N);
+    hipStream_t st = (hipStream_t)stream;
+    if (H <= 2) launch_big_lds<cls_dot_kernel<2, LEN, VAR>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, tab);
+    else if (H <= 4) launch_big_lds<cls_dot_kernel<4, LEN, VAR>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, tab);
+    else if (H <= 8) launch_big_lds<cls_dot_kernel<8, LEN, VAR>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, tab);
+    else launch_big_lds<cls_dot_kernel<16, LEN, VAR>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, tab);
+    return lstc_launch_status();
+}
+
+template <bool VAR>
+int launch_cls_wsum(const float* W, const float* X, const int32_t* row0, float* Y, int64_t N, int32_t S, int32_t H, int32_t d,
+                    void* stream) {
+    int rc = assoc_check(X, Y, X, N, S, H, d);
+    if (rc) return rc;
+    if (!W || (VAR && !row0)) return LSTC_E_NULL;
+    const size_t lds = (size_t)H * S * sizeof(float);
+    LSTC_H_DISPATCH(cls_wsum_kernel, VAR, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S, H, d, row0);
+    return lstc_launch_status();
+}
+
+template <bool VAR>
+int launch_cls_outer(const float* W1, const float* U1, const float* W2, const float* U2, const float* add0, const int32_t* row0,
+                     float* dX, int64_t N, int32_t S, int32_t H, int32_t d, void* stream) {
+    int rc = assoc_check(U1, U2, dX, N, S, H, d);
+    if (rc) return rc;
+    if (!W1 || !W2 || (VAR && !row0)) return LSTC_E_NULL;
+    if (add0 && !aligned16(add0)) return LSTC_E_ALIGN;
+    const size_t lds = (size_t)2 * H * S * sizeof(float);
+    LSTC_H_DISPATCH(cls_outer_kernel, VAR, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S, H, d, row0,
+                    add0);
+    return lstc_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
 
 int lstc_cls_dot(const float* U, const float* X, float* out, float* probs, int64_t N, int32_t S, int32_t H, int32_t d,
                  int32_t mode, float dropout_p, uint64_t seed, void* stream) {
-    int rc = assoc_check(U, X, out, N, S, H, d);
-    if (rc) return rc;
-    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
-    if (mode != 0 && !probs) return LSTC_E_NULL;
-    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
-    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
-    if (lds > 96 * 1024) return LSTC_E_RANGE;
-    const DropKey dk = make_drop_key(dropout_p, seed);
-    const int has_drop = dropout_p > 0.f;
-    const dim3 grid((unsigned)N);
-    hipStream_t st = (hipStream_t)stream;
-    if (H <= 2) launch_big_lds<cls_dot_kernel<2>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
-    else if (H <= 4) launch_big_lds<cls_dot_kernel<4>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
-    else if (H <= 8) launch_big_lds<cls_dot_kernel<8>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
-    else launch_big_lds<cls_dot_kernel<16>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, (const int32_t*)nullptr);
-    return lstc_launch_status();
+    return launch_cls_dot<false, false>(U, X, nullptr, out, probs, N, S, H, d, mode, dropout_p, seed, stream, 0);
 }
 
 int lstc_cls_dot_len(const float* U, const float* X, const int32_t* klen, float* out, float* probs, int64_t N, int32_t S, int32_t H,
                      int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream) {
-    int rc = assoc_check(U, X, out, N, S, H, d);
-    if (rc) return rc;
-    if (!klen) return LSTC_E_NULL;
-    if (S < 2) return LSTC_E_SHAPE;
-    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
-    if (mode != 0 && !probs) return LSTC_E_NULL;
-    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
-    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
-    if (lds > 96 * 1024) return LSTC_E_RANGE;
-    const DropKey dk = make_drop_key(dropout_p, seed);
-    const int has_drop = dropout_p > 0.f;
-    const dim3 grid((unsigned)N);
-    hipStream_t st = (hipStream_t)stream;
-    if (H <= 2) launch_big_lds<cls_dot_kernel<2, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
-    else if (H <= 4) launch_big_lds<cls_dot_kernel<4, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
-    else if (H <= 8) launch_big_lds<cls_dot_kernel<8, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
-    else launch_big_lds<cls_dot_kernel<16, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, klen);
-    return lstc_launch_status();
+    return launch_cls_dot<true, false>(U, X, klen, out, probs, N, S, H, d, mode, dropout_p, seed, stream,
+                                       !klen ? LSTC_E_NULL : S < 2 ? LSTC_E_SHAPE : 0);
 }
 
 int lstc_cls_dot_var(const float* U, const float* X, const int32_t* row0, float* out, float* probs, int64_t N, int32_t S_max, int32_t H,
                      int32_t d, int32_t mode, float dropout_p, uint64_t seed, void* stream) {
-    const int32_t S = S_max;
-    int rc = assoc_check(U, X, out, N, S, H, d);
-    if (rc) return rc;
-    if (!row0) return LSTC_E_NULL;
-    if (mode < 0 || mode > 2) return LSTC_E_UNSUPPORTED;
-    if (mode != 0 && !probs) return LSTC_E_NULL;
-    if ((uint64_t)N * H * S * S > 0xffffffffull) return LSTC_E_RANGE;
-    const size_t lds = ((size_t)H * d + (size_t)H * S) * sizeof(float);
-    if (lds > 96 * 1024) return LSTC_E_RANGE;
-    const DropKey dk = make_drop_key(dropout_p, seed);
-    const int has_drop = dropout_p > 0.f;
-    const dim3 grid((unsigned)N);
-    hipStream_t st = (hipStream_t)stream;
-    if (H <= 2) launch_big_lds<cls_dot_kernel<2, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
-    else if (H <= 4) launch_big_lds<cls_dot_kernel<4, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
-    else if (H <= 8) launch_big_lds<cls_dot_kernel<8, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
-    else launch_big_lds<cls_dot_kernel<16, false, true>, 96 * 1024>(grid, NT, lds, st, U, X, out, probs, S, H, d, mode, dk, has_drop, row0);
-    return lstc_launch_status();
+    return launch_cls_dot<false, true>(U, X, row0, out, probs, N, S_max, H, d, mode, dropout_p, seed, stream, !row0 ? LSTC_E_NULL : 0);
+}
+
+int lstc_cls_wsum(const float* W, const float* X, float* Y, int64_t N, int32_t S, int32_t H, int32_t d, void* stream) {
+    return launch_cls_wsum<false>(W, X, nullptr, Y, N, S, H, d, stream);
 }
 
 int lstc_cls_wsum_var(const float* W, const float* X, const int32_t* row0, float* Y, int64_t N, int32_t S_max, int32_t H, int32_t d,
                       void* stream) {
-    int rc = assoc_check(X, Y, X, N, S_max, H, d);
-    if (rc) return rc;
-    if (!W || !row0) return LSTC_E_NULL;
-    const size_t lds = (size_t)H * S_max * sizeof(float);
-    LSTC_H_DISPATCH(cls_wsum_kernel, true, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S_max, H, d, row0);
-    return lstc_launch_status();
-}
-
-int lstc_cls_outer_var(const float* W1, const float* U1, const float* W2, const float* U2, const float* add0, const int32_t* row0,
-                       float* dX, int64_t N, int32_t S_max, int32_t H, int32_t d, void* stream) {
-    int rc = assoc_check(U1, U2, dX, N, S_max, H, d);
-    if (rc) return rc;
-    if (!W1 || !W2 || !row0) return LSTC_E_NULL;
-    if (add0 && !aligned16(add0)) return LSTC_E_ALIGN;
-    const size_t lds = (size_t)2 * H * S_max * sizeof(float);
-    LSTC_H_DISPATCH(cls_outer_kernel, true, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S_max, H, d, row0,
-                    add0);
-    return lstc_launch_status();
-}
-
-int lstc_cls_wsum(const float* W, const float* X, float* Y, int64_t N, int32_t S, int32_t H, int32_t d, void* stream) {
-    int rc = assoc_check(X, Y, X, N, S, H, d);
-    if (rc) return rc;
-    if (!W) return LSTC_E_NULL;
-    const size_t lds = (size_t)H * S * sizeof(float);
-    LSTC_H_DISPATCH(cls_wsum_kernel, false, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W, X, Y, S, H, d, (const int32_t*)nullptr);
-    return lstc_launch_status();
+    return launch_cls_wsum<true>(W, X, row0, Y, N, S_max, H, d, stream);
 }
 
 int lstc_cls_outer(const float* W1, const float* U1, const float* W2, const float* U2, float* dX, int64_t N, int32_t S,
                    int32_t H, int32_t d, void* stream) {
-    int rc = assoc_check(U1, U2, dX, N, S, H, d);
-    if (rc) return rc;
-    if (!W1 || !W2) return LSTC_E_NULL;
-    const size_t lds = (size_t)2 * H * S * sizeof(float);
-    LSTC_H_DISPATCH(cls_outer_kernel, false, H, dim3((unsigned)N), dim3(NT), lds, (hipStream_t)stream, W1, U1, W2, U2, dX, S, H, d,
-                    (const int32_t*)nullptr, (const float*)nullptr);
-    return lstc_launch_status();
+    return launch_cls_outer<false>(W1, U1, W2, U2, nullptr, nullptr, dX, N, S, H, d, stream);
+}
+
+int lstc_cls_outer_var(const float* W1, const float* U1, const float* W2, const float* U2, const float* add0, const int32_t* row0,
+                       float* dX, int64_t N, int32_t S_max, int32_t H, int32_t d, void* stream) {
+    return launch_cls_outer<true>(W1, U1, W2, U2, add0, row0, dX, N, S_max, H, d, stream);
 }
 
 int lstc_cls_dot_pack(const float* U, const void* X_pack, float* out, float* probs, int64_t N, int32_t S, int32_t H, int32_t d,

@@ -2,6 +2,8 @@
 // column sums, dropout replay, the fused last head layer, Adagrad, squared-norm.
 // All of them stream their operands once with 16-B-per-lane accesses where the layout allows
 // (cdna_hip_programming Guideline 13) and reduce with wave shuffles.
+#include <initializer_list>
+#include <type_traits>
 #include "lstc_common.h"
 
 namespace {
@@ -582,217 +584,199 @@ __global__ void __launch_bounds__(NT) colsum_pack1_kernel(const __bf16* __restri
 }
 
 // ------------------------------------------------------------------------------ CLS concat
-// grid (N, ceil(d/NT)); thread owns one column (coalesced across the workgroup), walks the tokens.
-__global__ void __launch_bounds__(NT) cls_concat_fwd_kernel(const float* __restrict__ x, const float* __restrict__ x_hi,
-                                                             int64_t n_lo, const float* __restrict__ cls,
-                                                             const float* __restrict__ pos, float* __restrict__ y, int S,
-                                                             int d, __bf16* __restrict__ packed, int KBp) {
-    const int64_t n = blockIdx.x;
-    const int c = blockIdx.y * NT + threadIdx.x;
-    if (c >= d) return;
-    // sequences [0, n_lo) come from x, [n_lo, N) from x_hi: the reference's cat([normal, abnormal]) fused away
-    const float* xr = (x_hi && n >= n_lo ? x_hi + (n - n_lo) * (int64_t)(S - 1) * d : x + n * (int64_t)(S - 1) * d) + c;
-    float* yr = y + n * (int64_t)S * d + c;
-    float s = 0.f;
-    for (int t = 0; t < S - 1; ++t) {
-        const float v = xr[(int64_t)t * d];
-        s += v;
-        const float w = pos ? v + pos[(int64_t)(t + 1) * d + c] : v;
-        yr[(int64_t)(t + 1) * d] = w;
-        if (packed) packed[p1_offset(n * S + t + 1, c, KBp)] = (__bf16)w;       // bf16 mode: layer 0's packed A operand
-    }
-    float cv = cls ? cls[c] : s / (float)(S - 1);
-    if (pos) cv += pos[c];
-    yr[0] = cv;
-    if (packed) packed[p1_offset(n * S, c, KBp)] = (__bf16)cv;
-}
+// y = [CLS row, the sequence's tokens]: CLS = `cls` or the mean of the tokens, `pos` added on every row written.  One kernel text each
+// for the forward, the input gradient and the token-row gradient; the template arguments choose
+//   V        the access pattern: 4-B (float) or 16-B (float4: d % 4 == 0, aligned operands); `dv` counts V's per row.  A column's
+//            arithmetic is a sequential walk over the tokens in both, so the two give the same bits (at the headline batch in bf16
+//            mode the 4-B loads and 2-B pack stores took 569 us, 2.0 GB moved: 3.6 TB/s);
+//   LAY      where the sequences lie (concat_seq), its arguments in a ConcatArg<LAY> by value, so that an instantiation holds no
+//            trace of the other layouts:
+//     CONCAT_FIXED  x [N, S-1, d] -> y [N, S, d].  Sequences [0, n_lo) come from x and [n_lo, N) from x_hi when that is set: the
+//                   reference's cat([normal, abnormal]) fused away.  `packed` (bf16 mode: layer 0's packed A operand, lstc_pack1 of
+//                   [N*S, d]) is written next to y, or alone (y null: the bf16 activation stream).
+//                   GATHER (round 5): `clip_idx` makes x a feature BANK [clips, P, d] and token t of sequence n the patch t % P of
+//                   clip clip_idx[n * (S - 1) / P + t / P] - the batch formation (lstc_gather_rows: 805 MB written and read again at
+//                   the headline shape) is fused into this pass.  The index of a token is wave-uniform (one sequence per
+//                   workgroup): a scalar load, which the compiler issues only for a pointer it knows the stores to y cannot
+//                   reach - a __restrict__ kernel parameter, not a member of the by-value struct (as a member the loads went
+//                   through the vector path and the headline gather took 363 us instead of 337).
+//     CONCAT_LEN    the same padded shapes, sequence n has lens[n] real tokens (clamped to [1, S-1]); the rest of its row of x is
+//                   padding that is never read, and its rows of y / dx behind the tokens are written as exact zeros.
+//     CONCAT_VAR    unpadded in and out: sequence n owns rows row0[n] .. row0[n + 1] - 1 of y [M, d] (CLS first) and, having one
+//                   token fewer, rows row0[n] - n .. of x [M - N, d].  A sequence's bits depend neither on the path nor on its
+//                   neighbours.
+enum ConcatLayout { CONCAT_FIXED, CONCAT_LEN, CONCAT_VAR };
+struct ConcatFixed {
+    const void* x_hi;
+    int64_t n_lo;
+    __bf16* packed;
+    int KBp;
+    int P;
+};
+struct ConcatLen { const int32_t* lens; };
+struct ConcatVar { const int32_t* row0; };
+template <int LAY>
+using ConcatArg = std::conditional_t<LAY == CONCAT_FIXED, ConcatFixed, std::conditional_t<LAY == CONCAT_LEN, ConcatLen, ConcatVar>>;
 
-// The same with FOUR columns per thread (d a multiple of 4, 16-B aligned operands): 16-B loads / stores, 8-B pack stores, the
-// token loop unrolled so that several rows are in flight per lane.  Same per-column arithmetic in the same order (the mean CLS
-// token is a sequential sum over the tokens), so the results are bitwise those of the scalar kernel, which took 569 us for the
-// headline batch in bf16 mode (2.0 GB moved: 3.6 TB/s) with its 4-B loads and 2-B pack stores.
-// GATHER (round 5): ``clip_idx`` != NULL makes x a feature BANK [clips, P, d] and token t of sequence n the patch t % P of clip
-// clip_idx[n * (S - 1) / P + t / P] - the batch formation (lstc_gather_rows: 805 MB written and read again at the headline shape) is
-// fused into this pass.  The index of a token is wave-uniform (one sequence per workgroup): a scalar load.
-template <bool GATHER>
-__global__ void __launch_bounds__(NT) cls_concat_fwd_vec4_kernel(const float4* __restrict__ x, const float4* __restrict__ x_hi,
-                                                                  int64_t n_lo, const float4* __restrict__ cls,
-                                                                  const float4* __restrict__ pos, float4* __restrict__ y, int S,
-                                                                  int d4, __bf16* __restrict__ packed, int KBp,
-                                                                  const int64_t* __restrict__ clip_idx, int P) {
-    const int64_t n = blockIdx.x;
-    const int c4 = blockIdx.y * NT + threadIdx.x;
-    if (c4 >= d4) return;
-    const float4* xr = (x_hi && n >= n_lo ? x_hi + (n - n_lo) * (int64_t)(S - 1) * d4 : x + n * (int64_t)(S - 1) * d4) + c4;
-    const int64_t* ci = GATHER ? clip_idx + n * (int64_t)((S - 1) / P) : nullptr;
-    float4* yr = y ? y + n * (int64_t)S * d4 + c4 : nullptr;       // NULL: pack only (bf16 activation stream)
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto emit = [&](int64_t row, const float4& w) {
-        bf16x4v h;
-        h[0] = (__bf16)w.x; h[1] = (__bf16)w.y; h[2] = (__bf16)w.z; h[3] = (__bf16)w.w;
-        *reinterpret_cast<bf16x4v*>(packed + p1_offset(row, 4 * c4, KBp)) = h;
-    };
-    // 8 loads in flight per thread: 4 -> 8 took the kernel 319 -> 286 us (f32 only), 480 -> 395 us (with the pack); 16: 303 / 387
-#pragma unroll 8
-    for (int t = 0; t < S - 1; ++t) {
-        float4 v;
-        if constexpr (GATHER) v = x[(ci[t / P] * P + t % P) * (int64_t)d4 + c4];
-        else v = xr[(int64_t)t * d4];
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        float4 w = v;
-        if (pos) {
-            const float4 pv = pos[(int64_t)(t + 1) * d4 + c4];
-            w.x += pv.x; w.y += pv.y; w.z += pv.z; w.w += pv.w;
-        }
-        if (yr) yr[(int64_t)(t + 1) * d4] = w;
-        if (packed) emit(n * S + t + 1, w);
-    }
-    float4 cv;
-    if (cls) cv = cls[c4];
-    else { const float r = (float)(S - 1); cv = make_float4(s.x / r, s.y / r, s.z / r, s.w / r); }
-    if (pos) { const float4 pv = pos[c4]; cv.x += pv.x; cv.y += pv.y; cv.z += pv.z; cv.w += pv.w; }
-    if (yr) yr[0] = cv;
-    if (packed) emit(n * S, cv);
-}
-
-// dx[n,t,:] = dy[n,t+1,:] + (mean_cls ? dy[n,0,:]/(S-1) : 0)
-__global__ void __launch_bounds__(NT) cls_concat_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int S,
-                                                             int d, int mean_cls) {
-    const int64_t n = blockIdx.x;
-    const int c = blockIdx.y * NT + threadIdx.x;
-    if (c >= d) return;
-    const float* dr = dy + n * (int64_t)S * d + c;
-    float* xr = dx + n * (int64_t)(S - 1) * d + c;
-    const float g0 = mean_cls ? dr[0] / (float)(S - 1) : 0.f;
-    for (int t = 0; t < S - 1; ++t) xr[(int64_t)t * d] = dr[(int64_t)(t + 1) * d] + g0;
-}
-
-// ------------------------------------------------------------------------------ CLS concat of padded batches (per-sequence lengths)
-// Sequence n has lens[n] real tokens (clamped to [1, S-1]); the rest of its row of x is padding that is never read.  One kernel text
-// for the 4-B (V = float) and the 16-B (V = float4: d % 4 == 0, aligned operands) access pattern; `dv` counts V's per row.  A column's
-// arithmetic is a sequential walk over the tokens in both, so the two paths give the same bits.
 __device__ inline int concat_len(const int32_t* __restrict__ lens, int64_t n, int S) { return min(max((int)lens[n], 1), S - 1); }
+
+// Sequence n: its first row of y (the CLS row) and of x, its token count L, the divisor of its mean (L; an empty unpadded
+// sequence divides by 1), and whether its rows behind the tokens, up to S - 1, are written as zeros.
+struct ConcatSeq {
+    int64_t y0, x0;
+    int L, div;
+    bool tail;
+};
+template <int LAY>
+__device__ inline ConcatSeq concat_seq(const ConcatArg<LAY>& a, int64_t n, int S) {
+    if constexpr (LAY == CONCAT_VAR) {
+        const int64_t b = a.row0[n];
+        const int L = (int)(a.row0[n + 1] - b) - 1;
+        return {b, b - n, L, max(L, 1), false};
+    } else {
+        int L = S - 1;
+        if constexpr (LAY == CONCAT_LEN) L = concat_len(a.lens, n, S);
+        return {n * S, n * (int64_t)(S - 1), L, L, LAY == CONCAT_LEN};
+    }
+}
+
 __device__ inline float vzero(float) { return 0.f; }
 __device__ inline float4 vzero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ inline float vadd(float a, float b) { return a + b; }
 __device__ inline float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ inline float vdiv(float a, float r) { return a / r; }
 __device__ inline float4 vdiv(const float4& a, float r) { return make_float4(a.x / r, a.y / r, a.z / r, a.w / r); }
+// element c (in V's) of row `row` of the pack: a 2-B store, or the 8 B of four columns
+__device__ inline void pack_put(__bf16* packed, int64_t row, int c, int KBp, float w) { packed[p1_offset(row, c, KBp)] = (__bf16)w; }
+__device__ inline void pack_put(__bf16* packed, int64_t row, int c, int KBp, const float4& w) {
+    bf16x4v h;
+    h[0] = (__bf16)w.x; h[1] = (__bf16)w.y; h[2] = (__bf16)w.z; h[3] = (__bf16)w.w;
+    *reinterpret_cast<bf16x4v*>(packed + p1_offset(row, 4 * c, KBp)) = h;
+}
 
-// grid (N, ceil(dv/NT)).  y[n,0] = cls or mean(x[n,:L]); y[n,1+t] = x[n,t] for t < L; pos on rows 0..L; rows > L exact zeros.
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_len_fwd_kernel(const V* __restrict__ x, const int32_t* __restrict__ lens,
-                                                                 const V* __restrict__ cls, const V* __restrict__ pos,
-                                                                 V* __restrict__ y, int S, int dv) {
+// grid (N, ceil(dv/NT)); a thread owns one V of columns (coalesced across the workgroup) and walks the tokens.
+// y[0] = cls or mean(x[:L]); y[1+t] = x[t] for t < L; pos on rows 0..L.
+template <typename V, int LAY, bool GATHER = false>
+__global__ void __launch_bounds__(NT) cls_concat_fwd_kernel(const V* __restrict__ x, ConcatArg<LAY> a, const V* __restrict__ cls,
+                                                             const V* __restrict__ pos, V* __restrict__ y, int S, int dv,
+                                                             const int64_t* __restrict__ clip_idx) {
     const int64_t n = blockIdx.x;
     const int c = blockIdx.y * NT + threadIdx.x;
     if (c >= dv) return;
-    const int L = concat_len(lens, n, S);
-    const V* xr = x + n * (int64_t)(S - 1) * dv + c;
-    V* yr = y + n * (int64_t)S * dv + c;
-    V s = vzero(V{});
-#pragma unroll 8
-    for (int t = 0; t < L; ++t) {
-        const V v = xr[(int64_t)t * dv];
-        s = vadd(s, v);
-        yr[(int64_t)(t + 1) * dv] = pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v;
+    const ConcatSeq q = concat_seq<LAY>(a, n, S);
+    const V* xr = x + q.x0 * dv + c;
+    const int64_t* ci = nullptr;
+    if constexpr (LAY == CONCAT_FIXED) {
+        if (a.x_hi && n >= a.n_lo) xr = (const V*)a.x_hi + (n - a.n_lo) * (int64_t)(S - 1) * dv + c;
+        if constexpr (GATHER) ci = clip_idx + n * (int64_t)((S - 1) / a.P);
     }
-    for (int t = L; t < S - 1; ++t) yr[(int64_t)(t + 1) * dv] = vzero(V{});
-    V cv = cls ? cls[c] : vdiv(s, (float)L);
+    V* yr = LAY != CONCAT_FIXED || y ? y + q.y0 * dv + c : nullptr;       // NULL: pack only
+    auto put = [&](int t, const V& w) {        // row t of the sequence
+        if constexpr (LAY == CONCAT_FIXED) {
+            if (yr) yr[(int64_t)t * dv] = w;
+            if (a.packed) pack_put(a.packed, q.y0 + t, c, a.KBp, w);
+        } else {
+            yr[(int64_t)t * dv] = w;
+        }
+    };
+    V s = vzero(V{});
+    // 8 loads in flight per thread: 4 -> 8 took the kernel 319 -> 286 us (f32 only), 480 -> 395 us (with the pack); 16: 303 / 387
+#pragma unroll 8
+    for (int t = 0; t < q.L; ++t) {
+        V v;
+        if constexpr (GATHER) v = x[(ci[t / a.P] * a.P + t % a.P) * (int64_t)dv + c];
+        else v = xr[(int64_t)t * dv];
+        s = vadd(s, v);
+        put(t + 1, pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v);
+    }
+    if (q.tail)
+        for (int t = q.L; t < S - 1; ++t) put(t + 1, vzero(V{}));
+    V cv = cls ? cls[c] : vdiv(s, (float)q.div);
     if (pos) cv = vadd(cv, pos[c]);
-    yr[0] = cv;
+    put(0, cv);
 }
 
-// dx[n,t] = dy[n,t+1] + (mean_cls ? dy[n,0] / L : 0) for t < L, exact zeros beyond.
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_len_bwd_kernel(const V* __restrict__ dy, const int32_t* __restrict__ lens,
-                                                                 V* __restrict__ dx, int S, int dv, int mean_cls) {
+// dx[t] = dy[1+t] + (mean_cls ? dy[0] / L : 0) for t < L.  Same grid.
+template <typename V, int LAY>
+__global__ void __launch_bounds__(NT) cls_concat_bwd_kernel(const V* __restrict__ dy, ConcatArg<LAY> a, V* __restrict__ dx, int S, int dv,
+                                                             int mean_cls) {
     const int64_t n = blockIdx.x;
     const int c = blockIdx.y * NT + threadIdx.x;
     if (c >= dv) return;
-    const int L = concat_len(lens, n, S);
-    const V* dr = dy + n * (int64_t)S * dv + c;
-    V* xr = dx + n * (int64_t)(S - 1) * dv + c;
-    const V g0 = mean_cls ? vdiv(dr[0], (float)L) : vzero(V{});
+    const ConcatSeq q = concat_seq<LAY>(a, n, S);
+    const V* dr = dy + q.y0 * dv + c;
+    V* xr = dx + q.x0 * dv + c;
+    const V g0 = mean_cls ? vdiv(dr[0], (float)q.div) : vzero(V{});
 #pragma unroll 8
-    for (int t = 0; t < L; ++t) xr[(int64_t)t * dv] = vadd(dr[(int64_t)(t + 1) * dv], g0);
-    for (int t = L; t < S - 1; ++t) xr[(int64_t)t * dv] = vzero(V{});
+    for (int t = 0; t < q.L; ++t) xr[(int64_t)t * dv] = vadd(dr[(int64_t)(t + 1) * dv], g0);
+    if (q.tail)
+        for (int t = q.L; t < S - 1; ++t) xr[(int64_t)t * dv] = vzero(V{});
 }
 
-// dtok[t, :] = sum over the sequences with t <= L_n of dy[n, t, :] (the gradient of a learned CLS token: row 0, and of the position
-// table: rows 0..S-1).  grid (S, ceil(dv/NT)); the sequences are walked in order, so the sum is deterministic.
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_len_dtok_kernel(const V* __restrict__ dy, const int32_t* __restrict__ lens,
-                                                                  V* __restrict__ dtok, int64_t N, int S, int dv) {
+// dtok[t, :] = sum over the sequences that have row t (t <= L_n) of their dy[t, :]: the gradient of a learned CLS token (row 0) and
+// of the position table.  grid (rows of dtok, ceil(dv/NT)); the sequences are walked in order, so the sum is deterministic.  (The
+// fixed layout's sums are column sums of dy viewed [N, S * d]: lstc_colsum, another order.)
+template <typename V, int LAY>
+__global__ void __launch_bounds__(NT) cls_concat_dtok_kernel(const V* __restrict__ dy, ConcatArg<LAY> a, V* __restrict__ dtok, int64_t N,
+                                                              int S, int dv) {
     const int t = blockIdx.x;
     const int c = blockIdx.y * NT + threadIdx.x;
     if (c >= dv) return;
     V s = vzero(V{});
-    for (int64_t n = 0; n < N; ++n)
-        if (t <= concat_len(lens, n, S)) s = vadd(s, dy[(n * S + t) * (int64_t)dv + c]);
-    dtok[(int64_t)t * dv + c] = s;
-}
-
-// ------------------------------------------------------------------------------ CLS concat, unpadded in and unpadded out
-// Sequence n owns rows row0[n] .. row0[n + 1] - 1 of y [M, d] (CLS first) and, having one token fewer, rows row0[n] - n .. of x
-// [M - N, d].  The same two access patterns and the same sequential per-column walk as the length kernels above: a sequence's bits
-// depend neither on the path nor on its neighbours.
-// grid (N, ceil(dv/NT)).  y[row0[n]] = cls or mean(x_n); y[row0[n] + 1 + t] = x_n[t]; pos on rows 0..L_n of the sequence.
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_var_fwd_kernel(const V* __restrict__ x, const int32_t* __restrict__ row0,
-                                                                 const V* __restrict__ cls, const V* __restrict__ pos,
-                                                                 V* __restrict__ y, int dv) {
-    const int64_t n = blockIdx.x;
-    const int c = blockIdx.y * NT + threadIdx.x;
-    if (c >= dv) return;
-    const int64_t b = row0[n];
-    const int L = (int)(row0[n + 1] - b) - 1;
-    const V* xr = x + (b - n) * dv + c;
-    V* yr = y + b * dv + c;
-    V s = vzero(V{});
-#pragma unroll 8
-    for (int t = 0; t < L; ++t) {
-        const V v = xr[(int64_t)t * dv];
-        s = vadd(s, v);
-        yr[(int64_t)(t + 1) * dv] = pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v;
-    }
-    V cv = cls ? cls[c] : vdiv(s, (float)max(L, 1));
-    if (pos) cv = vadd(cv, pos[c]);
-    yr[0] = cv;
-}
-
-// dx_n[t] = dy[row0[n] + 1 + t] + (mean_cls ? dy[row0[n]] / L_n : 0)
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_var_bwd_kernel(const V* __restrict__ dy, const int32_t* __restrict__ row0,
-                                                                 V* __restrict__ dx, int dv, int mean_cls) {
-    const int64_t n = blockIdx.x;
-    const int c = blockIdx.y * NT + threadIdx.x;
-    if (c >= dv) return;
-    const int64_t b = row0[n];
-    const int L = (int)(row0[n + 1] - b) - 1;
-    const V* dr = dy + b * dv + c;
-    V* xr = dx + (b - n) * dv + c;
-    const V g0 = mean_cls ? vdiv(dr[0], (float)max(L, 1)) : vzero(V{});
-#pragma unroll 8
-    for (int t = 0; t < L; ++t) xr[(int64_t)t * dv] = vadd(dr[(int64_t)(t + 1) * dv], g0);
-}
-
-// dtok[t, :] = sum over the sequences that have token t (t < S_n) of dy[row0[n] + t, :], the sequences walked in order.
-// grid (S_max, ceil(dv/NT)).
-template <typename V>
-__global__ void __launch_bounds__(NT) cls_concat_var_dtok_kernel(const V* __restrict__ dy, const int32_t* __restrict__ row0,
-                                                                  V* __restrict__ dtok, int64_t N, int dv) {
-    const int t = blockIdx.x;
-    const int c = blockIdx.y * NT + threadIdx.x;
-    if (c >= dv) return;
-    V s = vzero(V{});
-    int64_t b = row0[0];
     for (int64_t n = 0; n < N; ++n) {
-        const int64_t e = row0[n + 1];
-        if (b + t < e) s = vadd(s, dy[(b + t) * dv + c]);
-        b = e;
+        const ConcatSeq q = concat_seq<LAY>(a, n, S);
+        if (t <= q.L) s = vadd(s, dy[(q.y0 + t) * dv + c]);
     }
     dtok[(int64_t)t * dv + c] = s;
+}
+
+// ---- CLS concat: every launch goes through concat_launch
+// 16-B accesses are possible: d % 4 == 0 and every operand 16-B aligned (a null operand counts as aligned)
+static bool concat_vec16(int32_t d, std::initializer_list<const void*> ops) {
+    bool ok = d % 4 == 0;
+    for (const void* p : ops) ok = ok && aligned16(p);
+    return ok;
+}
+
+// Chooses the access type V (float4 where concat_vec16 allows, float otherwise), counts the V's of a row and sizes the grid
+// (`rows` x column groups), then calls go(V{}, grid, dv), which launches that instantiation.
+template <typename Go>
+static void concat_launch(int32_t d, std::initializer_list<const void*> ops, int64_t rows, Go go) {
+    const bool v4 = concat_vec16(d, ops);
+    const int dv = v4 ? d / 4 : d;
+    const dim3 grid((unsigned)rows, (unsigned)((dv + NT - 1) / NT));
+    if (v4) go(float4{}, grid, dv);
+    else go(float{}, grid, dv);
+}
+
+template <int LAY, bool GATHER = false>
+static void concat_fwd(const float* x, const ConcatArg<LAY>& a, const float* cls, const float* pos, float* y, int64_t N, int32_t S,
+                       int32_t d, hipStream_t st, const int64_t* clip_idx = nullptr) {
+    const void* x_hi = nullptr;
+    if constexpr (LAY == CONCAT_FIXED) x_hi = a.x_hi;
+    concat_launch(d, {x, x_hi, y, cls, pos}, N, [&](auto v, dim3 grid, int dv) {
+        using V = decltype(v);
+        if constexpr (!GATHER || std::is_same_v<V, float4>)       // the gather exists on the 16-B path (its entry point refuses the rest)
+            hipLaunchKernelGGL((cls_concat_fwd_kernel<V, LAY, GATHER>), grid, NT, 0, st, (const V*)x, a, (const V*)cls, (const V*)pos,
+                               (V*)y, S, dv, clip_idx);
+    });
+}
+
+// dx (N sequences) and / or dtok (`tok_rows` rows; the len and var layouts only), each may be null
+template <int LAY>
+static void concat_bwd(const float* dy, const ConcatArg<LAY>& a, float* dx, float* dtok, int64_t N, int32_t tok_rows, int32_t S, int32_t d,
+                       int32_t mean_cls, hipStream_t st) {
+    if (dx)
+        concat_launch(d, {dy, dx, dtok}, N, [&](auto v, dim3 grid, int dv) {
+            using V = decltype(v);
+            hipLaunchKernelGGL((cls_concat_bwd_kernel<V, LAY>), grid, NT, 0, st, (const V*)dy, a, (V*)dx, S, dv, mean_cls);
+        });
+    if constexpr (LAY != CONCAT_FIXED)
+        if (dtok)
+            concat_launch(d, {dy, dx, dtok}, tok_rows, [&](auto v, dim3 grid, int dv) {
+                using V = decltype(v);
+                hipLaunchKernelGGL((cls_concat_dtok_kernel<V, LAY>), grid, NT, 0, st, (const V*)dy, a, (V*)dtok, N, S, dv);
+            });
 }
 
 // ---------------------------------------------------------------------------------- colsum
@@ -1431,24 +1415,11 @@ int lstc_layernorm_bwd_act(const float* dy, const void* dy_pack, const void* x_p
     return lstc_launch_status();
 }
 
-static void launch_cls_concat_fwd(const float* x, const float* x_hi, int64_t n_lo, const float* cls_token, const float* pos, float* y,
-                                  int64_t N, int32_t S, int32_t d, __bf16* packed, int KBp, hipStream_t st) {
-    if (d % 4 == 0 && aligned16(x) && aligned16(y) && (!x_hi || aligned16(x_hi)) && (!cls_token || aligned16(cls_token)) &&
-        (!pos || aligned16(pos))) {
-        hipLaunchKernelGGL(cls_concat_fwd_vec4_kernel<false>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, st, (const float4*)x,
-                           (const float4*)x_hi, n_lo, (const float4*)cls_token, (const float4*)pos, (float4*)y, S, d / 4, packed, KBp,
-                           (const int64_t*)nullptr, 1);
-        return;
-    }
-    hipLaunchKernelGGL(cls_concat_fwd_kernel, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, st, x, x_hi, n_lo, cls_token, pos, y, S, d,
-                       packed, KBp);
-}
-
 int lstc_cls_concat_fwd(const float* x, const float* x_hi, int64_t n_lo, const float* cls_token, const float* pos,
                         float* y, int64_t N, int32_t S, int32_t d, void* stream) {
     if (!x || !y) return LSTC_E_NULL;
     if (N <= 0 || S < 2 || d <= 0 || (x_hi && (n_lo < 0 || n_lo > N))) return LSTC_E_SHAPE;
-    launch_cls_concat_fwd(x, x_hi, n_lo, cls_token, pos, y, N, S, d, nullptr, 0, (hipStream_t)stream);
+    concat_fwd<CONCAT_FIXED>(x, ConcatFixed{x_hi, n_lo, nullptr, 0, 1}, cls_token, pos, y, N, S, d, (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1458,10 +1429,10 @@ int lstc_cls_concat_fwd_pack(const float* x, const float* x_hi, int64_t n_lo, co
     if (N <= 0 || S < 2 || d <= 0 || (x_hi && (n_lo < 0 || n_lo > N))) return LSTC_E_SHAPE;
     if ((N * S) % 256 != 0 || d % 64 != 0) return LSTC_E_UNSUPPORTED;      // the rows fill the pack's even tile grid exactly
     if (!aligned16(packed)) return LSTC_E_ALIGN;
-    // y == NULL (pack only: the bf16 activation stream) exists on the 16-B kernel
-    if (!y && !(d % 4 == 0 && aligned16(x) && (!x_hi || aligned16(x_hi)) && (!cls_token || aligned16(cls_token)) && (!pos || aligned16(pos))))
-        return LSTC_E_ALIGN;
-    launch_cls_concat_fwd(x, x_hi, n_lo, cls_token, pos, y, N, S, d, (__bf16*)packed, d / 32, (hipStream_t)stream);
+    // y == NULL (pack only: the bf16 activation stream) exists on the 16-B path
+    if (!y && !concat_vec16(d, {x, x_hi, cls_token, pos})) return LSTC_E_ALIGN;
+    concat_fwd<CONCAT_FIXED>(x, ConcatFixed{x_hi, n_lo, (__bf16*)packed, d / 32, 1}, cls_token, pos, y, N, S, d,
+                             (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1470,19 +1441,16 @@ int lstc_cls_concat_gather_fwd(const float* bank, int64_t bank_clips, const int6
     if (!bank || !clip_idx || (!y && !packed)) return LSTC_E_NULL;
     if (N <= 0 || S < 2 || d <= 0 || P <= 0 || bank_clips <= 0 || (S - 1) % P != 0) return LSTC_E_SHAPE;
     if (packed && ((N * S) % 256 != 0 || d % 64 != 0)) return LSTC_E_UNSUPPORTED;      // the rows fill the pack's even tile grid exactly
-    if (d % 4 != 0 || !aligned16(bank) || !aligned16(y) || !aligned16(packed) || (cls_token && !aligned16(cls_token)) || (pos && !aligned16(pos)))
-        return LSTC_E_ALIGN;
-    hipLaunchKernelGGL(cls_concat_fwd_vec4_kernel<true>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, (hipStream_t)stream,
-                       (const float4*)bank, (const float4*)nullptr, (int64_t)0, (const float4*)cls_token, (const float4*)pos, (float4*)y, S,
-                       d / 4, (__bf16*)packed, d / 32, clip_idx, P);
+    if (!concat_vec16(d, {bank, y, packed, cls_token, pos})) return LSTC_E_ALIGN;
+    concat_fwd<CONCAT_FIXED, true>(bank, ConcatFixed{nullptr, 0, (__bf16*)packed, d / 32, P}, cls_token, pos, y, N, S, d,
+                                   (hipStream_t)stream, clip_idx);
     return lstc_launch_status();
 }
 
 int lstc_cls_concat_bwd(const float* dy, float* dx, int64_t N, int32_t S, int32_t d, int32_t mean_cls, void* stream) {
     if (!dy || !dx) return LSTC_E_NULL;
     if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
-    hipLaunchKernelGGL(cls_concat_bwd_kernel, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, (hipStream_t)stream, dy, dx,
-                       S, d, mean_cls);
+    concat_bwd<CONCAT_FIXED>(dy, ConcatFixed{}, dx, nullptr, N, 0, S, d, mean_cls, (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1490,13 +1458,7 @@ int lstc_cls_concat_len_fwd(const float* x, const int32_t* lens, const float* cl
                             int32_t S, int32_t d, void* stream) {
     if (!x || !lens || !y) return LSTC_E_NULL;
     if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (d % 4 == 0 && aligned16(x) && aligned16(y) && (!cls_token || aligned16(cls_token)) && (!pos || aligned16(pos)))
-        hipLaunchKernelGGL(cls_concat_len_fwd_kernel<float4>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, st, (const float4*)x, lens,
-                           (const float4*)cls_token, (const float4*)pos, (float4*)y, S, d / 4);
-    else
-        hipLaunchKernelGGL(cls_concat_len_fwd_kernel<float>, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, st, x, lens, cls_token, pos, y,
-                           S, d);
+    concat_fwd<CONCAT_LEN>(x, ConcatLen{lens}, cls_token, pos, y, N, S, d, (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1504,20 +1466,7 @@ int lstc_cls_concat_len_bwd(const float* dy, const int32_t* lens, float* dx, flo
                             int32_t mean_cls, void* stream) {
     if (!dy || !lens || (!dx && !dtok)) return LSTC_E_NULL;
     if (N <= 0 || S < 2 || d <= 0) return LSTC_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const bool v4 = d % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(dtok);
-    const int dv = v4 ? d / 4 : d;
-    const unsigned gy = (unsigned)((dv + NT - 1) / NT);
-    if (dx) {
-        if (v4) hipLaunchKernelGGL(cls_concat_len_bwd_kernel<float4>, dim3((unsigned)N, gy), NT, 0, st, (const float4*)dy, lens, (float4*)dx,
-                                   S, dv, mean_cls);
-        else hipLaunchKernelGGL(cls_concat_len_bwd_kernel<float>, dim3((unsigned)N, gy), NT, 0, st, dy, lens, dx, S, dv, mean_cls);
-    }
-    if (dtok) {
-        if (v4) hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float4>, dim3((unsigned)S, gy), NT, 0, st, (const float4*)dy, lens,
-                                   (float4*)dtok, N, S, dv);
-        else hipLaunchKernelGGL(cls_concat_len_dtok_kernel<float>, dim3((unsigned)S, gy), NT, 0, st, dy, lens, dtok, N, S, dv);
-    }
+    concat_bwd<CONCAT_LEN>(dy, ConcatLen{lens}, dx, dtok, N, S, S, d, mean_cls, (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1525,12 +1474,7 @@ int lstc_cls_concat_var_fwd(const float* x, const int32_t* row0, const float* cl
                             int32_t d, void* stream) {
     if (!x || !row0 || !y) return LSTC_E_NULL;
     if (N <= 0 || d <= 0) return LSTC_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (d % 4 == 0 && aligned16(x) && aligned16(y) && (!cls_token || aligned16(cls_token)) && (!pos || aligned16(pos)))
-        hipLaunchKernelGGL(cls_concat_var_fwd_kernel<float4>, dim3((unsigned)N, (d / 4 + NT - 1) / NT), NT, 0, st, (const float4*)x, row0,
-                           (const float4*)cls_token, (const float4*)pos, (float4*)y, d / 4);
-    else
-        hipLaunchKernelGGL(cls_concat_var_fwd_kernel<float>, dim3((unsigned)N, (d + NT - 1) / NT), NT, 0, st, x, row0, cls_token, pos, y, d);
+    concat_fwd<CONCAT_VAR>(x, ConcatVar{row0}, cls_token, pos, y, N, 0, d, (hipStream_t)stream);
     return lstc_launch_status();
 }
 
@@ -1538,20 +1482,7 @@ int lstc_cls_concat_var_bwd(const float* dy, const int32_t* row0, float* dx, flo
                             int32_t mean_cls, void* stream) {
     if (!dy || !row0 || (!dx && !dtok)) return LSTC_E_NULL;
     if (N <= 0 || d <= 0 || (dtok && S_max < 1)) return LSTC_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const bool v4 = d % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(dtok);
-    const int dv = v4 ? d / 4 : d;
-    const unsigned gy = (unsigned)((dv + NT - 1) / NT);
-    if (dx) {
-        if (v4) hipLaunchKernelGGL(cls_concat_var_bwd_kernel<float4>, dim3((unsigned)N, gy), NT, 0, st, (const float4*)dy, row0, (float4*)dx,
-                                   dv, mean_cls);
-        else hipLaunchKernelGGL(cls_concat_var_bwd_kernel<float>, dim3((unsigned)N, gy), NT, 0, st, dy, row0, dx, dv, mean_cls);
-    }
-    if (dtok) {
-        if (v4) hipLaunchKernelGGL(cls_concat_var_dtok_kernel<float4>, dim3((unsigned)S_max, gy), NT, 0, st, (const float4*)dy, row0,
-                                   (float4*)dtok, N, dv);
-        else hipLaunchKernelGGL(cls_concat_var_dtok_kernel<float>, dim3((unsigned)S_max, gy), NT, 0, st, dy, row0, dtok, N, dv);
-    }
+    concat_bwd<CONCAT_VAR>(dy, ConcatVar{row0}, dx, dtok, N, S_max, 0, d, mean_cls, (hipStream_t)stream);
     return lstc_launch_status();
 }
 

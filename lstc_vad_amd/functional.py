@@ -1878,76 +1878,6 @@ def gemm_batched(a, b, c, M, N, K, lda, ldb, ldc, trans_a, trans_b, batch, sa, s
     return c
 
 
-def cls_dot(u, x3, mode, probs=None, p_drop=0.0, seed=0):
-    N, S, dm = x3.shape
-    H = u.shape[1]
-    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    if mode == 1:
-        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_dot(dev_ptr(u), dev_ptr(x3), dev_ptr(out), dev_ptr(probs), N, S, H, dm, mode, float(p_drop),
-                                   int(seed), stream_ptr()), "lstc_cls_dot")
-    return out, probs
-
-
-def cls_dot_len(u, x3, klen, mode, probs=None, p_drop=0.0, seed=0):
-    """``cls_dot`` on a padded batch (lstc_cls_dot_len): ``klen`` int32 [N] on the device, keys per sequence with the CLS token."""
-    N, S, dm = x3.shape
-    H = u.shape[1]
-    if klen.dtype != torch.int32 or klen.numel() != N or not klen.is_contiguous():
-        raise ValueError("cls_dot_len: klen must be a contiguous int32 tensor of N entries")
-    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    if mode == 1:
-        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_dot_len(dev_ptr(u), dev_ptr(x3), dev_ptr(klen), dev_ptr(out), dev_ptr(probs), N, S, H, dm, mode,
-                                       float(p_drop), int(seed), stream_ptr()), "lstc_cls_dot_len")
-    return out, probs
-
-
-def cls_wsum(w, x3):
-    N, S, dm = x3.shape
-    H = w.shape[1]
-    y = torch.empty((N, H, dm), device=w.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_wsum(dev_ptr(w), dev_ptr(x3), dev_ptr(y), N, S, H, dm, stream_ptr()), "lstc_cls_wsum")
-    return y
-
-
-def cls_outer(w1, u1, w2, u2, N, S, dm):
-    H = w1.shape[1]
-    dx = torch.empty((N, S, dm), device=w1.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_outer(dev_ptr(w1), dev_ptr(u1), dev_ptr(w2), dev_ptr(u2), dev_ptr(dx), N, S, H, dm,
-                                     stream_ptr()), "lstc_cls_outer")
-    return dx
-
-
-def cls_dot_var(u, x2, lay: "SeqLayout", mode, probs=None, p_drop=0.0, seed=0):
-    """``cls_dot`` over an unpadded X [M, d] (lstc_cls_dot_var): out / probs [N, H, S_max], exact zeros behind a sequence's keys."""
-    N, S, H, dm = lay.N, lay.S_max, u.shape[1], x2.shape[1]
-    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    if mode == 1:
-        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_dot_var(dev_ptr(u), dev_ptr(x2), dev_ptr(lay.on(u.device, H)["row0"]), dev_ptr(out), dev_ptr(probs), N, S, H,
-                                       dm, mode, float(p_drop), int(seed), stream_ptr()), "lstc_cls_dot_var")
-    return out, probs
-
-
-def cls_wsum_var(w, x2, lay: "SeqLayout"):
-    N, S, H, dm = lay.N, lay.S_max, w.shape[1], x2.shape[1]
-    y = torch.empty((N, H, dm), device=w.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_wsum_var(dev_ptr(w), dev_ptr(x2), dev_ptr(lay.on(w.device, H)["row0"]), dev_ptr(y), N, S, H, dm,
-                                        stream_ptr()), "lstc_cls_wsum_var")
-    return y
-
-
-def cls_outer_var(w1, u1, w2, u2, add0, lay: "SeqLayout", dm):
-    """dX [M, d] of the unpadded batch (lstc_cls_outer_var); ``add0`` [N, d] or None joins each sequence's CLS row."""
-    H = w1.shape[1]
-    dx = torch.empty((lay.M, dm), device=w1.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_outer_var(dev_ptr(w1), dev_ptr(u1), dev_ptr(w2), dev_ptr(u2), dev_ptr(add0),
-                                         dev_ptr(lay.on(w1.device, H)["row0"]), dev_ptr(dx), lay.N, lay.S_max, H, dm, stream_ptr()),
-          "lstc_cls_outer_var")
-    return dx
-
-
 def unpack1_rows(pk: "Packed", row0: int = 0, step: int = 1, n: Optional[int] = None) -> torch.Tensor:
     """Rows ``row0 + i * step`` (i < n) of a packed bf16 operand as f32 [n, K] (lstc_unpack1_rows)."""
     if pk.kind != _lib.BF16P:
@@ -1964,29 +1894,136 @@ def cls_pack_ok(N: int, S: int, H: int, dm: int) -> bool:
     return _ACT16 and H <= 8 and S <= 128 and act_rows_ok(N * S, dm)
 
 
+class ClsTokens:
+    """The token matrix X of the CLS-only layer and the three passes over it (include/lstc_hip.h, lstc_cls_dot / _wsum / _outer),
+    in one of four forms:
+        f32 fixed       x [N, S, d]                                                    lstc_cls_*
+        f32 + lengths   the same, ``klen`` int32 [N] on the device (keys per sequence, the CLS token counted): the softmax runs over
+                        a sequence's own keys (lstc_cls_dot_len); the other two passes see zero weights behind them
+        f32 unpadded    x [M, d] with a ``SeqLayout``, S = the longest sequence             lstc_cls_*_var
+        bf16 pack       the ``Packed`` [N * S, d] of the bf16 activation stream             lstc_cls_*_pack
+    This is the one place that knows which form a batch has."""
+
+    def __init__(self, x, N, S, dm, klen=None, seqs=None, pack=None):
+        if klen is not None and (klen.dtype != torch.int32 or klen.numel() != N or not klen.is_contiguous()):
+            raise ValueError("cls_dot_len: klen must be a contiguous int32 tensor of N entries")
+        self.x, self.N, self.S, self.dm, self.klen, self.seqs, self.pack = x, N, S, dm, klen, seqs, pack
+        self.tag = "_var" if seqs is not None else "_pack" if pack is not None else ""
+        self.add0 = self.tag != ""          # outer() takes the CLS rows' own terms (the var and pack entry points do)
+
+    @classmethod
+    def of(cls, x, cfg):
+        """From the layer's input (or the ``x`` it saved for the backward pass) and its cfg."""
+        seqs = cfg.get("seqs")
+        if seqs is not None:          # unpadded batch: x is [1, M, d]
+            return cls(x.contiguous().view(seqs.M, x.shape[-1]), seqs.N, seqs.S_max, x.shape[-1], seqs=seqs)
+        if x.dtype == torch.bfloat16:          # the bf16 view of the pack of the last full layer's output (cfg["act_shape"])
+            if cfg.get("key_lengths") is not None:
+                raise RuntimeError("MHAClsAssocFunction: key lengths need the f32 activations")
+            N, S, dm = cfg["act_shape"]
+            return cls(x, N, S, dm, pack=_act_pack(x, N * S, dm))
+        return cls(x.contiguous(), *x.shape, klen=cfg.get("key_lengths"))
+
+    def _call(self, name, like, head, tail):
+        """lstc_<name>(head..., [row0,] tail..., stream): the row table of an unpadded batch sits behind the inputs; ``like`` is
+        an [N, H, .] operand of the call."""
+        table = (dev_ptr(self.seqs.on(like.device, like.shape[1])["row0"]),) if self.seqs is not None else ()
+        check(getattr(_lib.load(), name)(*head, *table, *tail, stream_ptr()), name)
+
+    @property
+    def _x(self):
+        return dev_ptr(self.x if self.pack is None else self.pack.buf)
+
+    def cls_rows(self, H):
+        """The CLS rows [N, d] in f32."""
+        if self.seqs is not None:
+            return gather_rows(self.x, self.seqs.on(self.x.device, H)["row0_64"])
+        return self.x[:, 0, :] if self.pack is None else unpack1_rows(self.pack, 0, self.S, self.N)
+
+    def dot(self, u, mode, probs=None, p_drop=0.0, seed=0):
+        """u [N, H, d] -> (out, probs) [N, H, S]; mode 0 raw dot products | 1 softmax, ``out`` = dropout(probs) | 2 the softmax /
+        dropout backward of ``u`` = d(weighted sum), ``probs`` an input.  Exact zeros behind a sequence's own keys.  A pack is read
+        through ``cls_dot_pack``, the name under which the step tests count the layer's reads of the bf16 stream."""
+        if self.pack is not None:
+            return cls_dot_pack(u, self.pack, self.N, self.S, mode, probs, p_drop, seed)
+        return self._dot(u, mode, probs, p_drop, seed)
+
+    def _dot(self, u, mode, probs, p_drop, seed):
+        N, S, H = self.N, self.S, u.shape[1]
+        out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+        if mode == 1:
+            probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
+        tail = (dev_ptr(out), dev_ptr(probs), N, S, H, self.dm, mode, float(p_drop), int(seed))
+        if self.klen is not None:
+            self._call("lstc_cls_dot_len", u, (dev_ptr(u), self._x, dev_ptr(self.klen)), tail)
+        else:
+            self._call("lstc_cls_dot" + self.tag, u, (dev_ptr(u), self._x), tail)
+        return out, probs
+
+    def wsum(self, w):
+        """w [N, H, S] -> y [N, H, d] = sum_j w[n, h, j] x[n, j]."""
+        H = w.shape[1]
+        y = torch.empty((self.N, H, self.dm), device=w.device, dtype=torch.float32)
+        self._call("lstc_cls_wsum" + self.tag, w, (dev_ptr(w), self._x), (dev_ptr(y), self.N, self.S, H, self.dm))
+        return y
+
+    def outer(self, w1, u1, w2, u2, add0=None):
+        """dX[n, j] = sum_h w1[n, h, j] u1[n, h] + w2[n, h, j] u2[n, h] in the form of the layer's input: f32 [N, S, d], f32
+        [1, M, d], or the bf16 view of a pack.  ``add0`` [N, d] joins row 0 of every sequence inside the pass (one writer per row, one
+        rounding of a pack) where ``self.add0`` says the form has that; the fixed form's caller accumulates onto dX[:, 0] instead."""
+        H, dm = w1.shape[1], self.dm
+        if add0 is not None and not self.add0:
+            raise RuntimeError("ClsTokens.outer: the fixed-shape pass has no add0")
+        if self.pack is not None:
+            dx = torch.empty((int(_lib.load().lstc_pack1_bytes(self.N * self.S, dm)),), device=w1.device, dtype=torch.uint8)
+        else:
+            dx = torch.empty((self.seqs.M, dm) if self.seqs is not None else (self.N, self.S, dm), device=w1.device, dtype=torch.float32)
+        self._call("lstc_cls_outer" + self.tag, w1, (dev_ptr(w1), dev_ptr(u1), dev_ptr(w2), dev_ptr(u2)) + ((dev_ptr(add0),) if self.add0 else ()),
+                   (dev_ptr(dx), self.N, self.S, H, dm))
+        if self.pack is not None:
+            return _act_tensor(Packed(dx, self.N * self.S, dm, _lib.BF16P))
+        return dx.view(1, self.seqs.M, dm) if self.seqs is not None else dx
+
+
+# Single passes under the names of their entry points, for the tests and timing tools that run one pass alone.
+def cls_dot(u, x3, *a):
+    return ClsTokens(x3, *x3.shape).dot(u, *a)
+
+
+def cls_dot_len(u, x3, klen, *a):
+    return ClsTokens(x3, *x3.shape, klen=klen).dot(u, *a)
+
+
+def cls_dot_var(u, x2, lay: "SeqLayout", *a):
+    return ClsTokens(x2, lay.N, lay.S_max, x2.shape[1], seqs=lay).dot(u, *a)
+
+
 def cls_dot_pack(u, xp: "Packed", N, S, mode, probs=None, p_drop=0.0, seed=0):
-    H = u.shape[1]
-    out = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    if mode == 1:
-        probs = torch.empty((N, H, S), device=u.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_dot_pack(dev_ptr(u), dev_ptr(xp.buf), dev_ptr(out), dev_ptr(probs), N, S, H, xp.K, mode, float(p_drop),
-                                        int(seed), stream_ptr()), "lstc_cls_dot_pack")
-    return out, probs
+    return ClsTokens(None, N, S, xp.K, pack=xp)._dot(u, mode, probs, p_drop, seed)
+
+
+def cls_wsum(w, x3):
+    return ClsTokens(x3, *x3.shape).wsum(w)
+
+
+def cls_wsum_var(w, x2, lay: "SeqLayout"):
+    return ClsTokens(x2, lay.N, lay.S_max, x2.shape[1], seqs=lay).wsum(w)
 
 
 def cls_wsum_pack(w, xp: "Packed", N, S):
-    H = w.shape[1]
-    y = torch.empty((N, H, xp.K), device=w.device, dtype=torch.float32)
-    check(_lib.load().lstc_cls_wsum_pack(dev_ptr(w), dev_ptr(xp.buf), dev_ptr(y), N, S, H, xp.K, stream_ptr()), "lstc_cls_wsum_pack")
-    return y
+    return ClsTokens(None, N, S, xp.K, pack=xp).wsum(w)
+
+
+def cls_outer(w1, u1, w2, u2, N, S, dm):
+    return ClsTokens(None, N, S, dm).outer(w1, u1, w2, u2)
+
+
+def cls_outer_var(w1, u1, w2, u2, add0, lay: "SeqLayout", dm):
+    return ClsTokens(None, lay.N, lay.S_max, dm, seqs=lay).outer(w1, u1, w2, u2, add0)[0]
 
 
 def cls_outer_pack(w1, u1, w2, u2, add0, N, S, dm) -> "Packed":
-    H = w1.shape[1]
-    buf = torch.empty((int(_lib.load().lstc_pack1_bytes(N * S, dm)),), device=w1.device, dtype=torch.uint8)
-    check(_lib.load().lstc_cls_outer_pack(dev_ptr(w1), dev_ptr(u1), dev_ptr(w2), dev_ptr(u2), dev_ptr(add0), dev_ptr(buf), N, S, H, dm,
-                                          stream_ptr()), "lstc_cls_outer_pack")
-    return Packed(buf, N * S, dm, _lib.BF16P)
+    return _act_pack(ClsTokens(None, N, S, dm, pack=True).outer(w1, u1, w2, u2, add0), N * S, dm)
 
 
 class MHAClsAssocFunction(torch.autograd.Function):
@@ -2003,32 +2040,17 @@ class MHAClsAssocFunction(torch.autograd.Function):
     @staticmethod
     @_small_m_fwd
     def forward(ctx, x, wq, wk, wv, wfc, ln_w, ln_b, table, cfg):
-        # bf16 activation stream: x is the bf16 view of the pack of the last full layer's output (cfg["act_shape"]); the three
-        # passes over X read the pack (half the bytes), the CLS rows come out of it widened
-        xp = None
-        seqs = cfg.get("seqs")          # unpadded batch (SeqLayout): x is [1, M, d], the three passes take the offset forms
-        if seqs is not None:
-            if x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[:2]) != (1, seqs.M):
-                raise RuntimeError(f"MHAClsAssocFunction: an unpadded batch is f32 [1, M, d] = [1, {seqs.M}, d], got {tuple(x.shape)}")
-            N, S, dm = seqs.N, seqs.S_max, x.shape[2]
-        elif x.dtype == torch.bfloat16:
-            N, S, dm = cfg["act_shape"]
-            xp = _act_pack(x, N * S, dm)
-        else:
-            N, S, dm = x.shape
+        seqs = cfg.get("seqs")          # unpadded batch (SeqLayout): x is [1, M, d]
+        if seqs is not None and (x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[:2]) != (1, seqs.M)):
+            raise RuntimeError(f"MHAClsAssocFunction: an unpadded batch is f32 [1, M, d] = [1, {seqs.M}, d], got {tuple(x.shape)}")
+        tok = ClsTokens.of(x, cfg)
+        N, S, dm = tok.N, tok.S, tok.dm
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
         training = cfg["training"]
         p_attn = cfg["attn_dropout"] if training else 0.0
         p_fc = cfg["fc_dropout"] if training else 0.0
         ctx.table_shape = None if table is None else tuple(table.shape)
-        if seqs is not None:
-            x = x.contiguous().view(seqs.M, dm)
-            xc = gather_rows(x, seqs.on(x.device, H)["row0_64"])       # the CLS rows [N, d]
-        elif xp is None:
-            x = x.contiguous()
-            xc = x[:, 0, :]
-        else:
-            xc = unpack1_rows(xp, 0, S, N)
+        xc = tok.cls_rows(H)
         scale = 1.0 / (dk ** 0.5)
         qc = gemm(xc, wq, trans_b=True)                                                   # [N, H*dk]
         u = torch.empty((N, H, dm), device=x.device, dtype=torch.float32)
@@ -2039,21 +2061,8 @@ class MHAClsAssocFunction(torch.autograd.Function):
             _note(cfg["site"] + "attn_dropout#cls", p_attn, seed_a, (N, H, S, S))
         if p_fc > 0:
             _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
-        klen = cfg.get("key_lengths")
-        if seqs is not None:
-            pd, probs = cls_dot_var(u, x, seqs, 1, None, p_attn, seed_a)
-            xb = cls_wsum_var(pd, x, seqs)
-        elif klen is not None:
-            if xp is not None:
-                raise RuntimeError("MHAClsAssocFunction: key lengths need the f32 activations")
-            pd, probs = cls_dot_len(u, x, klen, 1, None, p_attn, seed_a)
-            xb = cls_wsum(pd, x)
-        elif xp is None:
-            pd, probs = cls_dot(u, x, 1, None, p_attn, seed_a)                            # dropped probs, probs
-            xb = cls_wsum(pd, x)                                                          # [N, H, d]
-        else:
-            pd, probs = cls_dot_pack(u, xp, N, S, 1, None, p_attn, seed_a)
-            xb = cls_wsum_pack(pd, xp, N, S)
+        pd, probs = tok.dot(u, 1, None, p_attn, seed_a)                                   # dropped probs, probs
+        xb = tok.wsum(pd)                                                                 # [N, H, d]
         oc = torch.empty((N, H * dv), device=x.device, dtype=torch.float32)
         per_head_rows_wT(xb, wv, oc, N, dv, dm, H)
         y = gemm(oc, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xc)
@@ -2061,21 +2070,18 @@ class MHAClsAssocFunction(torch.autograd.Function):
             z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6)
         else:
             z, mean, rstd = y, None, None
-        ctx.cfg = dict(cfg, N=N, S=S, dm=dm, is_act=xp is not None, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, scale=scale)
-        ctx.save_for_backward(x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y if cfg["layer_norm"] else None, mean, rstd,
-                              xc if (xp is not None or seqs is not None) else None)
+        ctx.cfg = dict(cfg, N=N, S=S, dm=dm, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, scale=scale)
+        ctx.save_for_backward(tok.x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y if cfg["layer_norm"] else None, mean, rstd, xc)
         return z
 
     @staticmethod
     @_small_m_bwd
     def backward(ctx, dz):
-        x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y, mean, rstd, xc_saved = ctx.saved_tensors
+        x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y, mean, rstd, xc = ctx.saved_tensors
         c = ctx.cfg
-        N, S, H, dk, dv, scale = c["N"], c["S"], c["n_head"], c["d_k"], c["d_v"], c["scale"]
+        N, H, dk, dv, scale = c["N"], c["n_head"], c["d_k"], c["d_v"], c["scale"]
         dm = c["dm"]
-        xp = _act_pack(x, N * S, dm) if c["is_act"] else None
-        seqs = c.get("seqs")
-        xc = xc_saved if xc_saved is not None else x[:, 0, :]
+        tok = ClsTokens.of(x, c)
         dz = dz.contiguous()
         dln_w = dln_b = None
         if c["layer_norm"]:
@@ -2090,18 +2096,8 @@ class MHAClsAssocFunction(torch.autograd.Function):
         dwv = grad_sink(wv)
         dwv = torch.empty_like(wv) if dwv is None else dwv
         gemm_batched(doc, xb, dwv, dv, dm, N, H * dv, H * dm, dm, True, False, H, dv, dm, dv * dm)
-        if seqs is not None:
-            ds, _ = cls_dot_var(dxb, x, seqs, 2, probs, c["p_attn"], c["seed_a"])
-            du = cls_wsum_var(ds, x, seqs)
-        elif c.get("key_lengths") is not None:
-            ds, _ = cls_dot_len(dxb, x, c["key_lengths"], 2, probs, c["p_attn"], c["seed_a"])
-            du = cls_wsum(ds, x)
-        elif xp is None:
-            ds, _ = cls_dot(dxb, x, 2, probs, c["p_attn"], c["seed_a"])                   # d(logit) [N,H,S]
-            du = cls_wsum(ds, x)                                                          # [N, H, d]
-        else:
-            ds, _ = cls_dot_pack(dxb, xp, N, S, 2, probs, c["p_attn"], c["seed_a"])
-            du = cls_wsum_pack(ds, xp, N, S)
+        ds, _ = tok.dot(dxb, 2, probs, c["p_attn"], c["seed_a"])                          # d(logit) [N, H, S]
+        du = tok.wsum(ds)                                                                 # [N, H, d]
         dqc = torch.empty_like(qc)
         per_head_rows_wT(du, wk, dqc, N, dk, dm, H, alpha=scale)
         dwk = grad_sink(wk)
@@ -2110,13 +2106,13 @@ class MHAClsAssocFunction(torch.autograd.Function):
         dwq = wgrad(dqc, xc, out=grad_sink(wq))
         dx = None
         if ctx.needs_input_grad[0]:
-            if seqs is not None:      # the CLS rows' own terms dQ Wq + residual join row 0 of each sequence inside the pass: one writer per row
-                dx = cls_outer_var(pd, dxb, ds, u, gemm(dqc, wq, residual=dy), seqs, dm).view(1, seqs.M, dm)
-            elif xp is None:
-                dx = cls_outer(pd, dxb, ds, u, N, S, dm)                                  # K/V paths, every token
-                gemm(dqc, wq, out=dx[:, 0, :], accumulate=True, residual=dy)              # CLS rows: + dQ Wq + residual
-            else:       # the gradient goes back as a pack; the CLS rows' own terms join row 0 before the one rounding
-                dx = _act_tensor(cls_outer_pack(pd, dxb, ds, u, gemm(dqc, wq, residual=dy), N, S, dm))
+            # K/V paths, every token; the CLS rows' own terms dQ Wq + residual join row 0 of each sequence inside the pass where the
+            # form has that (one writer per row; a pack is rounded once), behind it otherwise
+            if tok.add0:
+                dx = tok.outer(pd, dxb, ds, u, gemm(dqc, wq, residual=dy))
+            else:
+                dx = tok.outer(pd, dxb, ds, u)
+                gemm(dqc, wq, out=dx[:, 0, :], accumulate=True, residual=dy)
         dtable = None if ctx.table_shape is None else torch.zeros(ctx.table_shape, device=x.device, dtype=torch.float32)
         return dx, deliver(wq, dwq), deliver(wk, dwk), deliver(wv, dwv), dwfc, dln_w, dln_b, dtable, None
 
@@ -2401,6 +2397,22 @@ class LayerNormFunction(torch.autograd.Function):
         return (dx.view(dy.shape) if ctx.needs_input_grad[0] else None), dw, db
 
 
+def _concat_operands(cls_token, pos, S):
+    """The CLS concat kernels' view of the parameters: (learned token [d] or None, the first S rows of the position table or None)."""
+    return (cls_token.reshape(-1) if cls_token is not None else None), (pos[0, :S].contiguous() if pos is not None else None)
+
+
+def _concat_param_grads(tok, learned, pos_shape):
+    """Sums over the sequences of dy's token rows, ``tok`` [S, d] (None when neither is wanted) -> (dcls [1, 1, d], dpos)."""
+    dcls = dpos = None
+    if learned:
+        dcls = tok[0].clone().view(1, 1, -1)
+    if pos_shape is not None:
+        dpos = torch.zeros(pos_shape, device=tok.device, dtype=torch.float32)
+        dpos[0, :tok.shape[0]] = tok
+    return dcls, dpos
+
+
 class ClsConcatFunction(torch.autograd.Function):
     """models/Encoder.py:51-58: CLS (token mean or learned) prepended, optional learned position table added."""
 
@@ -2430,8 +2442,7 @@ class ClsConcatFunction(torch.autograd.Function):
             ctx.meta = (N, S, dm, False, None)
             return buf.view(torch.bfloat16)
         y = torch.empty((N, S, dm), device=x.device, dtype=torch.float32)
-        pos_s = pos[0, :S].contiguous() if pos is not None else None
-        cls_v = cls_token.reshape(-1) if cls_token is not None else None
+        cls_v, pos_s = _concat_operands(cls_token, pos, S)
         if _fused_pack_shape(N * S, dm):
             # bf16 mode: the kernel also writes layer 0's packed A operand
             lib = _lib.load()
@@ -2446,7 +2457,35 @@ class ClsConcatFunction(torch.autograd.Function):
         ctx.meta = (N, S, dm, cls_token is not None, pos.shape if pos is not None else None)
         return y
 
-    _forward_gather = None          # bound below: functional._cls_concat_gather
+    @staticmethod
+    def _forward_gather(ctx, bank, cls_token, pos, pack_only, gather):
+        idx, N, Lc = gather[:3]
+        lazy = gather[3] if len(gather) > 3 else None        # the feed.LazyRows behind ``idx``: knows the batch's distinct clips
+        clips, P, dm = bank.shape
+        S = Lc * P + 1
+        if bank.dtype != torch.float32 or not bank.is_contiguous() or idx.dtype != torch.int64 or idx.numel() != N * Lc or bank.requires_grad:
+            raise RuntimeError("ClsConcatFunction(gather): bank must be a contiguous float32 [clips, P, d] tensor without gradient and idx int64 [N * Lc]")
+        lib = _lib.load()
+        want_pack = pack_only or _fused_pack_shape(N * S, dm)
+        if pack_only and (cls_token is not None or pos is not None or not act_rows_ok(N * S, dm)):
+            raise RuntimeError("ClsConcatFunction(pack_only): nothing upstream may need a gradient and [N*S, d] must fit the bf16 stream")
+        y = None if pack_only else torch.empty((N, S, dm), device=bank.device, dtype=torch.float32)
+        buf = torch.empty((int(lib.lstc_pack1_bytes(N * S, dm)),), device=bank.device, dtype=torch.uint8) if want_pack else None
+        cls_v, pos_s = _concat_operands(cls_token, pos, S)
+        check(lib.lstc_cls_concat_gather_fwd(dev_ptr(bank), clips, dev_ptr(idx.contiguous()), P, dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y),
+                                             N, S, dm, dev_ptr(buf), stream_ptr()), "lstc_cls_concat_gather_fwd")
+        ctx.pack_only = bool(pack_only)
+        ctx.two = False
+        ctx.meta = (N, S, dm, cls_token is not None, pos.shape if pos is not None else None)
+        if pack_only:
+            return buf.view(torch.bfloat16)
+        if want_pack:
+            _register_pack(y.view(N * S, dm), Packed(buf, N * S, dm, _lib.BF16P))
+        spec = _dedup_spec(lazy, idx, N, Lc, S, cls_token is not None, pos is not None, pack_only)
+        _dedup_rows.clear()
+        if spec is not None:
+            _dedup_rows[_pack_key(y)] = (y, y._version, spec)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -2454,7 +2493,7 @@ class ClsConcatFunction(torch.autograd.Function):
         if ctx.pack_only:
             return None, None, None, None, None, None
         dy = dy.contiguous()
-        dx = dcls = dpos = None
+        dx = tok = None
         if ctx.needs_input_grad[0]:
             if ctx.two:
                 raise RuntimeError("input gradients with a split batch are not supported: concatenate first")
@@ -2462,13 +2501,8 @@ class ClsConcatFunction(torch.autograd.Function):
             check(_lib.load().lstc_cls_concat_bwd(dev_ptr(dy), dev_ptr(dx), N, S, dm, int(not learned), stream_ptr()),
                   "lstc_cls_concat_bwd")
         if learned or pos_shape is not None:
-            tok = colsum(dy.view(N, S * dm))                 # sum over sequences of every (token, channel)
-            if learned:
-                dcls = tok[:dm].clone().view(1, 1, dm)
-            if pos_shape is not None:
-                dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
-                dpos[0, :S] = tok.view(S, dm)
-        return dx, dcls, dpos, None, None, None
+            tok = colsum(dy.view(N, S * dm)).view(S, dm)     # sum over sequences of every (token, channel)
+        return (dx, *_concat_param_grads(tok, learned, pos_shape), None, None, None)
 
 
 class ClsConcatLenFunction(torch.autograd.Function):
@@ -2484,8 +2518,7 @@ class ClsConcatLenFunction(torch.autograd.Function):
             raise ValueError("ClsConcatLenFunction: lens must be a contiguous int32 tensor of N entries")
         x = x.contiguous()
         y = torch.empty((N, S, dm), device=x.device, dtype=torch.float32)
-        pos_s = pos[0, :S].contiguous() if pos is not None else None
-        cls_v = cls_token.reshape(-1) if cls_token is not None else None
+        cls_v, pos_s = _concat_operands(cls_token, pos, S)
         check(_lib.load().lstc_cls_concat_len_fwd(dev_ptr(x), dev_ptr(lens), dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y), N, S, dm,
                                                   stream_ptr()), "lstc_cls_concat_len_fwd")
         ctx.lens = lens
@@ -2496,7 +2529,7 @@ class ClsConcatLenFunction(torch.autograd.Function):
     def backward(ctx, dy):
         N, S, dm, learned, pos_shape = ctx.meta
         dy = dy.contiguous()
-        dx = dcls = dpos = tok = None
+        dx = tok = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((N, S - 1, dm), device=dy.device, dtype=torch.float32)
         if learned or pos_shape is not None:
@@ -2504,12 +2537,7 @@ class ClsConcatLenFunction(torch.autograd.Function):
         if dx is not None or tok is not None:
             check(_lib.load().lstc_cls_concat_len_bwd(dev_ptr(dy), dev_ptr(ctx.lens), dev_ptr(dx), dev_ptr(tok), N, S, dm,
                                                       int(not learned), stream_ptr()), "lstc_cls_concat_len_bwd")
-        if learned:
-            dcls = tok[0].clone().view(1, 1, dm)
-        if pos_shape is not None:
-            dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
-            dpos[0, :S] = tok
-        return dx, dcls, dpos, None
+        return (dx, *_concat_param_grads(tok, learned, pos_shape), None)
 
 
 class ClsConcatVarFunction(torch.autograd.Function):
@@ -2525,8 +2553,7 @@ class ClsConcatVarFunction(torch.autograd.Function):
         x = x.contiguous()
         row0 = lay.on(x.device, 0)["row0"]
         y = torch.empty((lay.M, dm), device=x.device, dtype=torch.float32)
-        pos_s = pos[0, :lay.S_max].contiguous() if pos is not None else None
-        cls_v = cls_token.reshape(-1) if cls_token is not None else None
+        cls_v, pos_s = _concat_operands(cls_token, pos, lay.S_max)
         check(_lib.load().lstc_cls_concat_var_fwd(dev_ptr(x), dev_ptr(row0), dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y), lay.N, dm,
                                                   stream_ptr()), "lstc_cls_concat_var_fwd")
         ctx.lay, ctx.row0 = lay, row0
@@ -2538,7 +2565,7 @@ class ClsConcatVarFunction(torch.autograd.Function):
         dm, learned, pos_shape = ctx.meta
         lay = ctx.lay
         dy = dy.contiguous()
-        dx = dcls = dpos = tok = None
+        dx = tok = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((lay.in0[-1], dm), device=dy.device, dtype=torch.float32)
         if learned or pos_shape is not None:
@@ -2546,12 +2573,7 @@ class ClsConcatVarFunction(torch.autograd.Function):
         if dx is not None or tok is not None:
             check(_lib.load().lstc_cls_concat_var_bwd(dev_ptr(dy), dev_ptr(ctx.row0), dev_ptr(dx), dev_ptr(tok), lay.N, lay.S_max, dm,
                                                       int(not learned), stream_ptr()), "lstc_cls_concat_var_bwd")
-        if learned:
-            dcls = tok[0].clone().view(1, 1, dm)
-        if pos_shape is not None:
-            dpos = torch.zeros(pos_shape, device=dy.device, dtype=torch.float32)
-            dpos[0, :lay.S_max] = tok
-        return dx, dcls, dpos, None
+        return (dx, *_concat_param_grads(tok, learned, pos_shape), None)
 
 
 def lengths_arg(lengths, N, S, device):
@@ -2580,40 +2602,6 @@ def lengths_arg(lengths, N, S, device):
     if bad:
         raise ValueError(f"lengths: every sequence needs 1 <= length <= {S - 1} (its token slots); got length {bad[0][1]} for sequence {bad[0][0]}")
     return torch.tensor(host, dtype=torch.int32).to(device), host
-
-
-def _cls_concat_gather(ctx, bank, cls_token, pos, pack_only, gather):
-    idx, N, Lc = gather[:3]
-    lazy = gather[3] if len(gather) > 3 else None        # the feed.LazyRows behind ``idx``: knows the batch's distinct clips
-    clips, P, dm = bank.shape
-    S = Lc * P + 1
-    if bank.dtype != torch.float32 or not bank.is_contiguous() or idx.dtype != torch.int64 or idx.numel() != N * Lc or bank.requires_grad:
-        raise RuntimeError("ClsConcatFunction(gather): bank must be a contiguous float32 [clips, P, d] tensor without gradient and idx int64 [N * Lc]")
-    lib = _lib.load()
-    want_pack = pack_only or _fused_pack_shape(N * S, dm)
-    if pack_only and (cls_token is not None or pos is not None or not act_rows_ok(N * S, dm)):
-        raise RuntimeError("ClsConcatFunction(pack_only): nothing upstream may need a gradient and [N*S, d] must fit the bf16 stream")
-    y = None if pack_only else torch.empty((N, S, dm), device=bank.device, dtype=torch.float32)
-    buf = torch.empty((int(lib.lstc_pack1_bytes(N * S, dm)),), device=bank.device, dtype=torch.uint8) if want_pack else None
-    pos_s = pos[0, :S].contiguous() if pos is not None else None
-    cls_v = cls_token.reshape(-1) if cls_token is not None else None
-    check(lib.lstc_cls_concat_gather_fwd(dev_ptr(bank), clips, dev_ptr(idx.contiguous()), P, dev_ptr(cls_v), dev_ptr(pos_s), dev_ptr(y),
-                                         N, S, dm, dev_ptr(buf), stream_ptr()), "lstc_cls_concat_gather_fwd")
-    ctx.pack_only = bool(pack_only)
-    ctx.two = False
-    ctx.meta = (N, S, dm, cls_token is not None, pos.shape if pos is not None else None)
-    if pack_only:
-        return buf.view(torch.bfloat16)
-    if want_pack:
-        _register_pack(y.view(N * S, dm), Packed(buf, N * S, dm, _lib.BF16P))
-    spec = _dedup_spec(lazy, idx, N, Lc, S, cls_token is not None, pos is not None, pack_only)
-    _dedup_rows.clear()
-    if spec is not None:
-        _dedup_rows[_pack_key(y)] = (y, y._version, spec)
-    return y
-
-
-ClsConcatFunction._forward_gather = staticmethod(_cls_concat_gather)
 
 
 class DropoutFunction(torch.autograd.Function):

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Compare the gfx950 machine code of the kernels of two builds, symbol by symbol.
 
-    python tools/isa_diff.py OLD_TREE NEW_TREE [OBJECT ...] [> profiles/attn_template_isa_diff.txt]
+    python tools/isa_diff.py [--same 'OLD_KEY=NEW_KEY' ...] OLD_TREE NEW_TREE [OBJECT ...] [> profiles/attn_template_isa_diff.txt]
 
 OBJECT names files of lstc_vad_amd/csrc without their suffix (gemm_f32, rowops, ...); the default is the attention files.
 Each tree must have been built with `make` (the per-file objects lstc_vad_amd/csrc/OBJECT.o are read: one offload bundle
 each).  Every kernel of OLD is looked up in NEW by its demangled name (key(): the two spellings of a masked instantiation count
 as one, and so do an instantiation and its spelling with further template arguments `false` behind it) and its disassembly
-compared as text after the addresses are stripped (instruction words and operands stay).  Exit status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
+compared as text after the addresses are stripped (instruction words and operands stay).  --same names a kernel of OLD and the
+kernel of NEW that took its place under another name (both as the keys this tool prints); it is compared with that one, and a
+name that matches nothing leaves its kernels MISSING / NEW.  A kernel that DIFFERS is listed with the registers, scratch bytes
+and code bytes of both builds.  Exit status 1 if an OLD kernel is missing or differs, or if NEW has a kernel that OLD has not."""
 import os
 import re
 import subprocess
@@ -16,6 +19,7 @@ import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 FILES = ("attention", "attention_long", "attention_pk")
+STATS = {}      # (tree, symbol) -> registers, scratch and code size, from the code object's metadata
 
 
 def kernels(tree, name, tmp):
@@ -40,6 +44,14 @@ def kernels(tree, name, tmp):
             continue
         if cur is not None and ln.strip() and ln.strip() != "...":      # "...": objdump's mark for alignment padding after a function
             out[cur].append(re.sub(r"\s*//.*$", "", ln).strip())      # drop the address comment
+    size = {ln.split()[-1]: int(ln.split()[-3], 16) for ln in syms.splitlines() if " F .text" in ln}
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    for entry in re.split(r"^  - ", notes, flags=re.M)[1:]:      # one block of amdhsa.kernels per kernel
+        f = dict(re.findall(r"^\s+\.(name|vgpr_count|sgpr_count|private_segment_fixed_size):\s+(\S+)$", entry, flags=re.M))
+        f["name"] = f.get("name", "").strip("'")      # quoted where the mangling holds a `$`
+        if f["name"] in out:
+            STATS[(tree, f["name"])] = (f"{f['vgpr_count']} VGPRs, {f['sgpr_count']} SGPRs, {f['private_segment_fixed_size']} B scratch, "
+                                        f"{size[f['name']]} B code")
     return out
 
 
@@ -82,32 +94,42 @@ def key(dem):
     return name + (" [masked]" if masked else "")
 
 
-def keyed(kern):
+def keyed(kern, tree):
     dem = demangle(sorted(kern))
     out = {}
     for sym, body in kern.items():
         k = key(dem[sym])
         assert k not in out, f"two kernels named {k}"
-        out[k] = body
+        out[k] = (body, STATS.get((tree, sym), "?"))
     return out
 
 
 def main():
-    old, new = sys.argv[1], sys.argv[2]
+    argv, same = sys.argv[1:], {}
+    while argv and argv[0] == "--same":
+        o, n = argv[1].split("=", 1)
+        same[o.strip()] = n.strip()
+        argv = argv[2:]
+    old, new = argv[0], argv[1]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
-        for name in sys.argv[3:] or FILES:
-            a, b = keyed(kernels(old, name, tmp)), keyed(kernels(new, name, tmp))
+        for name in argv[2:] or FILES:
+            a, b = keyed(kernels(old, name, tmp), old), keyed(kernels(new, name, tmp), new)
             print(f"== csrc/{name}.hip: {len(a)} kernels before, {len(b)} after")
+            taken = set()
             for k in sorted(a):
-                if k not in b:
+                kb = same[k] if k not in b and same.get(k) in b else k      # the kernel that took this one's place
+                as_new = f"  as {kb}" if kb != k else ""
+                taken.add(kb)
+                if kb not in b:
                     print(f"MISSING   {k}"); bad += 1
-                elif a[k] != b[k]:
-                    print(f"DIFFERS   {k}  ({len(a[k])} -> {len(b[k])} instructions)"); bad += 1
+                elif a[k][0] != b[kb][0]:
+                    print(f"DIFFERS   {k}{as_new}  ({len(a[k][0])} -> {len(b[kb][0])} instructions)\n"
+                          f"            before: {a[k][1]}\n            after:  {b[kb][1]}"); bad += 1
                 else:
-                    print(f"identical {k}  ({len(a[k])} instructions)")
-            for k in sorted(set(b) - set(a)):
-                print(f"NEW       {k}  ({len(b[k])} instructions)"); bad += 1
+                    print(f"identical {k}{as_new}  ({len(a[k][0])} instructions)")
+            for k in sorted(set(b) - taken):
+                print(f"NEW       {k}  ({len(b[k][0])} instructions)"); bad += 1
     print(f"== {bad} kernel(s) missing, changed or without a counterpart in the old tree")
     return 1 if bad else 0
 
