@@ -519,6 +519,17 @@ int lstc_cls_concat_var_fwd(const float* x, const int32_t* row0, const float* cl
 int lstc_cls_concat_var_bwd(const float* dy, const int32_t* row0, float* dx, float* dtok, int64_t N, int32_t S_max, int32_t d,
                             int32_t mean_cls, void* stream);
 
+/* lstc_cls_concat_var_fwd fed from SPANS of an HBM-resident bank of rows [bank_rows, d]: y, row0, cls_token and pos as there, but the
+ * L_n = row0[n+1] - row0[n] - 1 patch tokens of sequence n are rows src0[n] .. src0[n] + L_n - 1 of `bank` (src0: device int64 [N])
+ * instead of rows of a packed input - the token matrix of an evaluation or label pass is never materialised.  Spans may overlap,
+ * repeat and come in any order.  The same kernel text and the same sequential walk per column: for the same tokens y is bit-identical
+ * to lstc_cls_concat_var_fwd, on the 16-B path (d % 4 == 0, aligned operands) and on the 4-B one, and a sequence's bits depend neither
+ * on its neighbours nor on where it lies in the bank.  The offsets are trusted: every span must lie inside [0, bank_rows).  There is
+ * no backward entry - a bank takes no gradient; a learned CLS token and the position table get theirs from lstc_cls_concat_var_bwd
+ * with dx = NULL. */
+int lstc_cls_concat_span_fwd(const float* bank, int64_t bank_rows, const int64_t* src0, const int32_t* row0, const float* cls_token,
+                             const float* pos, float* y, int64_t N, int32_t d, void* stream);
+
 /* out[c] = sum_r x[r, c] for x [rows, ld] (first `cols` columns); deterministic two-pass reduction.
  * `partial` is caller workspace of n_partial*cols floats.  Bias / LayerNorm / pos-enc gradients. */
 int lstc_colsum(const float* x, int64_t rows, int32_t cols, int32_t ld, float* partial, int32_t n_partial,
@@ -686,6 +697,16 @@ int lstc_cast_bf16_f32(const void* x, float* y, int64_t n, void* stream);
  * default collate), so no feature bytes cross PCIe per step.  idx entries must lie in [0, src_rows). */
 int lstc_gather_rows(const float* src, int64_t src_rows, const int64_t* idx, float* dst, int64_t n_rows,
                      int64_t row_floats, void* stream);
+
+/* Means of runs of clips of a bank [bank_clips, P, d] -> out [n_seg, P, d] (the 32 bins of a UCF video, Test/evaluation_UCF.py:54-62,
+ * one launch for every video of a pool): out[s, p, :] = (sum over c < count[s] of bank[first[s] + c, p, :]) / count[s], the sum in
+ * order from the first clip.  first (device int64 [n_seg]) and count (device int32 [n_seg]) are clamped into the bank and count to
+ * >= 1, so a count of 1 is a bit-exact copy (the reference's `feats[r[i]]` arm of an empty bin).  With l2_normalize != 0 each row of
+ * d values is then divided by max(||row||_2, 1e-12) (F.normalize(p=2, dim=-1) on token rows); the squares are reduced in a fixed
+ * order.  A segment's bits do not depend on what shares the launch.  16-B accesses when d % 4 == 0 and both bases are 16-B aligned,
+ * 4-B ones otherwise (the means are the same bits; the norm's summation order differs between the two). */
+int lstc_segment_mean(const float* bank, int64_t bank_clips, const int64_t* first, const int32_t* count, int64_t n_seg, int32_t P,
+                      int32_t d, int32_t l2_normalize, float* out, void* stream);
 
 /* dst[j][m, :] = src[j][map[m], :] for m < rows and j < n (1 <= n <= 3) matrices of `cols` floats per row, in ONE launch: the
  * ordinary [M, H d_k] Q, K and V of layer 0 out of the projections of the unique rows of a batch whose windows overlap

@@ -22,6 +22,7 @@ EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
     "lstc_attn_var_fwd", "lstc_attn_var_bwd", "lstc_cls_dot_var", "lstc_cls_wsum_var", "lstc_cls_outer_var", "lstc_cls_concat_var_fwd", "lstc_cls_concat_var_bwd",
+    "lstc_cls_concat_span_fwd", "lstc_segment_mean",
     "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_dot_len", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
@@ -139,6 +140,8 @@ def load():
         "lstc_cls_outer_var": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_concat_var_fwd": [vp, vp, vp, vp, vp, i64, i32, vp],
         "lstc_cls_concat_var_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, vp],
+        "lstc_cls_concat_span_fwd": [vp, i64, vp, vp, vp, vp, vp, i64, i32, vp],
+        "lstc_segment_mean": [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp],
         "lstc_sdpa_fwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_sdpa_bwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_cls_dot": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],

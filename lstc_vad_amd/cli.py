@@ -130,6 +130,11 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                    help="MIL bag score = mean of the K largest part means of a video (1 = the maximum, as the reference computes; "
                         "1..part_num, part_num <= 64 above 1).  The reference's own --topk (default 7) still parses and still does "
                         "nothing, as upstream: wiring it up would change every existing run")
+    p.add_argument("--resident_eval", action="store_true",
+                   help="evaluation and pseudo-label passes score from HBM: the test / label set is uploaded once "
+                        "(pipeline.ResidentSet), the train-AUC pass reads the training bank already there, and every pass describes "
+                        "its sequences as spans of the bank instead of re-reading and re-uploading every video.  A set beyond 60 %% "
+                        "of the free HBM stays host-fed")
     return p
 
 
@@ -448,7 +453,9 @@ def train(script: str, argv=None, args=None):
         dataset = str(getattr(args, "dataset", "SHT"))
         gen(enc.eval(), head.eval(), "STN", dataset if dataset in ("UCF", "UBnormal") else "SHT", args.dataset_path, args.training_txt,
             args.threshold, part_len=1, n_patch=args.n_patch, d_model=d_model, segment_len=args.segment_len,
-            out_path=args.temporal_pseudo_path, rank=rank, world=world)      # sharded over the ranks; rank 0 writes the file
+            out_path=args.temporal_pseudo_path, rank=rank, world=world,      # sharded over the ranks; rank 0 writes the file
+            resident=_resident_set(args, dev, args.dataset_path, _list_keys(dataset, args.training_txt, train=True), None, False,
+                                   rank, world))
         enc.train(); head.train()
         if rank == 0:
             logger.info("temporal pseudo label generation finished.")
@@ -488,6 +495,34 @@ class _HostPairs:
 
     def shuffle_keys(self):
         self.ds.shuffle_keys()
+
+
+def _list_keys(dataset, txt, train=False):
+    """Archive keys of a list file in file order (the three dialects; SHT / UBnormal test and train lists: first comma field)."""
+    from .load_dataset import _ucf_line
+    from .pipeline import _train_keys
+    if train:
+        return [k for _, k in _train_keys(dataset, txt)]
+    if dataset == "UCF":
+        return [_ucf_line(line)[0] for line in open(txt, "r").readlines()]
+    return [line.strip().split(",")[0] for line in open(txt, "r").readlines()]
+
+
+def _resident_set(args, dev, archive, keys, n_patch, view, rank=0, world=1):
+    """--resident_eval: the videos ``keys`` of ``archive`` this rank scores (``i % world == rank``) as a pipeline.ResidentSet, or
+    None - the host-fed pass - without the flag or when the bank would exceed 60 % of the free HBM (one logged line)."""
+    if not getattr(args, "resident_eval", False):
+        return None
+    import torch
+    from .pipeline import ResidentSet
+    owns = (lambda i: i % world == rank) if world > 1 else None
+    need = ResidentSet.bytes(ResidentSet.archive_shapes(archive, keys), n_patch, view, owns)
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need >= 0.6 * free:
+        print(f"--resident_eval: {archive} needs {need / 2**30:.1f} GiB, beyond 60 % of the {free / 2**30:.1f} GiB free: host-fed pass",
+              file=sys.stderr)
+        return None
+    return ResidentSet.from_archive(archive, keys, dev, n_patch, view, owns)
 
 
 def _real_data(script, args, mode, part_len, pseudo_path, dev, rank, world, enc, head):
@@ -535,17 +570,27 @@ def _real_data(script, args, mode, part_len, pseudo_path, dev, rank, world, enc,
     if script == "spatio_transformer_MIL_CE" and dataset in ("UCF", "UBnormal"):
         train_flag = None                                        # Train/spatio_transformer_MIL_CE.py:344-345: auc_train = 0
     train_arc = getattr(args, train_flag, "") if train_flag else ""
+    # --resident_eval: the test set goes to HBM once, here, before the loop; the train-AUC pass reads the training bank the feed
+    # already holds (single-crop, and only when it was built from the archive that pass names)
+    test_set = train_set = None
+    if getattr(args, "resident_eval", False):
+        if getattr(args, "testing_txt", ""):
+            test_set = _resident_set(args, dev, test_arc, _list_keys(dataset, args.testing_txt), args.n_patch, dataset == "UCF", rank, world)
+        if train_arc and dataset != "UCF" and resident and data.crops == 1 and data.bank.dim() == 3 and \
+                data.bank.shape[1] == args.n_patch and os.path.abspath(train_arc) == os.path.abspath(args.dataset_path):
+            from .pipeline import ResidentSet
+            train_set = ResidentSet.from_pairs(data)
 
     def eval_fn():
         """(test AUC, train AUC) as the script's in-loop evaluation computes them (0 where it does not)."""
         auc_test = auc_train = 0.0
         if getattr(args, "testing_txt", ""):
             auc_test = evaluate_auc(enc.eval(), head.eval(), kind, dataset, test_arc, args.testing_txt, masks, part_len,
-                                    args.n_patch, args.segment_len, rank=rank, world=world)
+                                    args.n_patch, args.segment_len, rank=rank, world=world, resident=test_set)
         if train_arc and dataset != "UCF":
             auc_train = evaluate_train_auc(enc.eval(), head.eval(), kind, dataset, train_arc, args.training_txt,
                                            getattr(args, "test_mask_dir", ""), part_len, args.n_patch, args.segment_len,
-                                           rank=rank, world=world)
+                                           rank=rank, world=world, resident=train_set)
         return auc_test, auc_train
     return data, eval_fn
 
@@ -627,10 +672,14 @@ def generate_pseudo_labels(script: str, argv=None, args=None):
     if not args.synthetic and args.dataset_path:
         from .pipeline import generate_pseudo_labels as run
         import time as _time
+        ucf_ltn = mode == "LTN" and args.dataset == "UCF"         # the only generator route that views the rows as [-1, n_patch, d]
+        label_set = _resident_set(args, dev, args.dataset_path, _list_keys(args.dataset, args.training_txt, train=True),
+                                  args.n_patch if ucf_ltn else None, ucf_ltn, rank, world)
         torch.cuda.synchronize(); t0 = _time.perf_counter()
         out = run(enc, head, mode, args.dataset, args.dataset_path, args.training_txt, args.threshold, part_len=part_len,
                   n_patch=args.n_patch, d_model=args.d_model, segment_len=args.segment_len,
-                  classifier_head=(mode == "STN" and args.n_layers == 1), out_path=args.pseudo_labels_path, rank=rank, world=world)
+                  classifier_head=(mode == "STN" and args.n_layers == 1), out_path=args.pseudo_labels_path, rank=rank, world=world,
+                  resident=label_set)
         torch.cuda.synchronize()
         LAST_RUN.clear()
         LAST_RUN.update(script=script, clips=int(sum(v.shape[0] for v in out.values())) if args.dataset != "UCF" else None,
@@ -699,9 +748,11 @@ def evaluate_cli(script: str, argv=None, args=None):
         from .pipeline import evaluate_auc
         masks = args.test_mask_path if ucf else args.test_mask_dir
         import time as _time
+        test_set = _resident_set(args, dev, args.dataset_path, _list_keys("UCF" if ucf else args.dataset, args.testing_txt),
+                                 args.n_patch, ucf)
         torch.cuda.synchronize(); t0 = _time.perf_counter()
         auc, fs, _ = evaluate_auc(enc, head, "LTN", "UCF" if ucf else args.dataset, args.dataset_path, args.testing_txt, masks,
-                                  part_len, args.n_patch, seg, return_frames=True)
+                                  part_len, args.n_patch, seg, return_frames=True, resident=test_set)
         torch.cuda.synchronize()
         LAST_RUN.clear()
         LAST_RUN.update(script=script, clips=int(fs.shape[0]) // seg, score_s=_time.perf_counter() - t0, world=1)
@@ -715,8 +766,9 @@ def evaluate_cli(script: str, argv=None, args=None):
             lab = labs.reshape(-1)
             if ucf:
                 r = np.linspace(0, n, 33, dtype=np.int32)
-                bins = torch.stack([feats[r[i]] if r[i] == r[i + 1] else feats[r[i]:r[i + 1]].mean(dim=0) for i in range(32)])
-                bins = torch.nn.functional.normalize(bins, p=2, dim=-1)
+                # the 32 bins and their L2 normalisation in one launch (lstc_segment_mean); an empty bin is clip r[i] alone
+                from . import functional as Fn
+                bins = Fn.segment_mean(feats.contiguous(), [int(v) for v in r[:32]], [max(int(r[i + 1] - r[i]), 1) for i in range(32)], l2=True)
                 nparts = (32 + part_len - 1) // part_len
                 begs = [min(i * part_len, 32 - part_len) for i in range(nparts)]
                 ends = [min((i + 1) * part_len, 32) for i in range(nparts)]

@@ -605,6 +605,10 @@ __global__ void __launch_bounds__(NT) colsum_pack1_kernel(const __bf16* __restri
 //     CONCAT_VAR    unpadded in and out: sequence n owns rows row0[n] .. row0[n + 1] - 1 of y [M, d] (CLS first) and, having one
 //                   token fewer, rows row0[n] - n .. of x [M - N, d].  A sequence's bits depend neither on the path nor on its
 //                   neighbours.
+//                   GATHER (spans): x is a BANK of rows [bank_rows, d] and the tokens of sequence n are its rows clip_idx[n] ..
+//                   clip_idx[n] + L_n - 1 (here the table holds one first ROW per sequence): spans may overlap, repeat and lie in
+//                   any order, y keeps the unpadded layout.  Only where x0 comes from differs, so the bits are those of the packed
+//                   input; the table is the same __restrict__ parameter, read with scalar loads.
 enum ConcatLayout { CONCAT_FIXED, CONCAT_LEN, CONCAT_VAR };
 struct ConcatFixed {
     const void* x_hi;
@@ -627,12 +631,14 @@ struct ConcatSeq {
     int L, div;
     bool tail;
 };
-template <int LAY>
-__device__ inline ConcatSeq concat_seq(const ConcatArg<LAY>& a, int64_t n, int S) {
+template <int LAY, bool GATHER = false>
+__device__ inline ConcatSeq concat_seq(const ConcatArg<LAY>& a, int64_t n, int S, const int64_t* __restrict__ src0 = nullptr) {
     if constexpr (LAY == CONCAT_VAR) {
         const int64_t b = a.row0[n];
         const int L = (int)(a.row0[n + 1] - b) - 1;
-        return {b, b - n, L, max(L, 1), false};
+        int64_t x0 = b - n;
+        if constexpr (GATHER) x0 = src0[n];        // a span of bank rows
+        return {b, x0, L, max(L, 1), false};
     } else {
         int L = S - 1;
         if constexpr (LAY == CONCAT_LEN) L = concat_len(a.lens, n, S);
@@ -663,7 +669,7 @@ __global__ void __launch_bounds__(NT) cls_concat_fwd_kernel(const V* __restrict_
     const int64_t n = blockIdx.x;
     const int c = blockIdx.y * NT + threadIdx.x;
     if (c >= dv) return;
-    const ConcatSeq q = concat_seq<LAY>(a, n, S);
+    const ConcatSeq q = concat_seq<LAY, GATHER>(a, n, S, clip_idx);
     const V* xr = x + q.x0 * dv + c;
     const int64_t* ci = nullptr;
     if constexpr (LAY == CONCAT_FIXED) {
@@ -684,7 +690,7 @@ __global__ void __launch_bounds__(NT) cls_concat_fwd_kernel(const V* __restrict_
 #pragma unroll 8
     for (int t = 0; t < q.L; ++t) {
         V v;
-        if constexpr (GATHER) v = x[(ci[t / a.P] * a.P + t % a.P) * (int64_t)dv + c];
+        if constexpr (GATHER && LAY == CONCAT_FIXED) v = x[(ci[t / a.P] * a.P + t % a.P) * (int64_t)dv + c];
         else v = xr[(int64_t)t * dv];
         s = vadd(s, v);
         put(t + 1, pos ? vadd(v, pos[(int64_t)(t + 1) * dv + c]) : v);
@@ -756,7 +762,8 @@ static void concat_fwd(const float* x, const ConcatArg<LAY>& a, const float* cls
     if constexpr (LAY == CONCAT_FIXED) x_hi = a.x_hi;
     concat_launch(d, {x, x_hi, y, cls, pos}, N, [&](auto v, dim3 grid, int dv) {
         using V = decltype(v);
-        if constexpr (!GATHER || std::is_same_v<V, float4>)       // the gather exists on the 16-B path (its entry point refuses the rest)
+        // the fixed layout's gather exists on the 16-B path (its entry point refuses the rest); the spans on both
+        if constexpr (!GATHER || LAY == CONCAT_VAR || std::is_same_v<V, float4>)
             hipLaunchKernelGGL((cls_concat_fwd_kernel<V, LAY, GATHER>), grid, NT, 0, st, (const V*)x, a, (const V*)cls, (const V*)pos,
                                (V*)y, S, dv, clip_idx);
     });
@@ -1243,6 +1250,45 @@ __global__ void __launch_bounds__(NT) expand_rows_kernel(ExpandArgs a, int n, co
     }
 }
 
+// ---------------------------------------------------------------------------------- segment mean
+// out[s, p, :] = mean over the count[s] clips from first[s] of bank[., p, :] (the UCF bins), optionally divided by
+// max(||row||_2, 1e-12) (F.normalize on token rows).  One workgroup per (segment, patch); a thread owns the V's c, c + NT, .. of the
+// row and walks the clips in order from the first (a count of 1 copies the row bit for bit), 8 loads in flight as in the CLS concat:
+// 32 KiB per workgroup on the 16-B path, which a CU's resident workgroups multiply past what hides an HBM miss.  The squares are
+// summed per thread in column order, then by block_sum's fixed tree: nothing depends on what shares the launch.  With l2 a thread
+// reads back the means it wrote itself and scales them.  HBM-bound: (count + 1) rows moved per row written.  first / count are
+// wave-uniform __restrict__ parameters (scalar loads) and are clamped into the bank: a bad table cannot fault.
+__device__ inline float vsq(float a) { return a * a; }
+__device__ inline float vsq(const float4& a) { return a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w; }
+template <typename V>
+__global__ void __launch_bounds__(NT) segment_mean_kernel(const V* __restrict__ bank, int64_t bank_clips, const int64_t* __restrict__ first,
+                                                           const int32_t* __restrict__ count, int P, int dv, int l2,
+                                                           V* __restrict__ out) {
+    __shared__ float red[NT / 64];
+    const int64_t seg = blockIdx.x / P;
+    const int p = blockIdx.x % P;
+    int64_t f = first[seg];
+    f = f < 0 ? 0 : (f >= bank_clips ? bank_clips - 1 : f);
+    int64_t cnt = count[seg];
+    cnt = cnt < 1 ? 1 : (cnt > bank_clips - f ? bank_clips - f : cnt);
+    const int64_t step = (int64_t)P * dv;
+    const V* xr = bank + (f * P + p) * dv;
+    V* o = out + (int64_t)blockIdx.x * dv;
+    const float div = (float)cnt;
+    float sq = 0.f;
+    for (int c = threadIdx.x; c < dv; c += NT) {
+        V s = xr[c];
+#pragma unroll 8
+        for (int64_t k = 1; k < cnt; ++k) s = vadd(s, xr[k * step + c]);
+        s = vdiv(s, div);
+        o[c] = s;
+        sq += vsq(s);
+    }
+    if (!l2) return;                                    // uniform over the launch
+    const float nrm = fmaxf(sqrtf(block_sum<NT>(sq, red)), 1e-12f);
+    for (int c = threadIdx.x; c < dv; c += NT) o[c] = vdiv(o[c], nrm);
+}
+
 inline int grid_for(int64_t work_items, int per_block, int cap = 2048) {
     int64_t g = (work_items + per_block - 1) / per_block;
     if (g < 1) g = 1;
@@ -1475,6 +1521,14 @@ int lstc_cls_concat_var_fwd(const float* x, const int32_t* row0, const float* cl
     if (!x || !row0 || !y) return LSTC_E_NULL;
     if (N <= 0 || d <= 0) return LSTC_E_SHAPE;
     concat_fwd<CONCAT_VAR>(x, ConcatVar{row0}, cls_token, pos, y, N, 0, d, (hipStream_t)stream);
+    return lstc_launch_status();
+}
+
+int lstc_cls_concat_span_fwd(const float* bank, int64_t bank_rows, const int64_t* src0, const int32_t* row0, const float* cls_token,
+                             const float* pos, float* y, int64_t N, int32_t d, void* stream) {
+    if (!bank || !src0 || !row0 || !y) return LSTC_E_NULL;
+    if (N <= 0 || d <= 0 || bank_rows <= 0) return LSTC_E_SHAPE;
+    concat_fwd<CONCAT_VAR, true>(bank, ConcatVar{row0}, cls_token, pos, y, N, 0, d, (hipStream_t)stream, src0);
     return lstc_launch_status();
 }
 
@@ -1741,6 +1795,21 @@ int lstc_gather_rows(const float* src, int64_t src_rows, const int64_t* idx, flo
     if (chunks > 64) chunks = 64;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)n_rows, (unsigned)chunks), NT, 0, (hipStream_t)stream,
                        (const float4*)src, src_rows, idx, (float4*)dst, row_vec);
+    return lstc_launch_status();
+}
+
+int lstc_segment_mean(const float* bank, int64_t bank_clips, const int64_t* first, const int32_t* count, int64_t n_seg, int32_t P,
+                      int32_t d, int32_t l2_normalize, float* out, void* stream) {
+    if (!bank || !first || !count || !out) return LSTC_E_NULL;
+    if (bank_clips <= 0 || n_seg <= 0 || P <= 0 || d <= 0 || n_seg * P > 0x7fffffffLL) return LSTC_E_SHAPE;
+    const bool v4 = d % 4 == 0 && aligned16(bank) && aligned16(out);
+    const dim3 grid((unsigned)(n_seg * P));
+    if (v4)
+        hipLaunchKernelGGL(segment_mean_kernel<float4>, grid, NT, 0, (hipStream_t)stream, (const float4*)bank, bank_clips, first, count,
+                           (int)P, (int)(d / 4), (int)l2_normalize, (float4*)out);
+    else
+        hipLaunchKernelGGL(segment_mean_kernel<float>, grid, NT, 0, (hipStream_t)stream, bank, bank_clips, first, count, (int)P, (int)d,
+                           (int)l2_normalize, out);
     return lstc_launch_status();
 }
 

@@ -2576,6 +2576,80 @@ class ClsConcatVarFunction(torch.autograd.Function):
         return (dx, *_concat_param_grads(tok, learned, pos_shape), None)
 
 
+def span_starts(starts, lay, bank_rows):
+    """Host ``starts`` (a Python sequence or a CPU tensor of N integers) of the spans of ``lay``'s sequences in a bank of
+    ``bank_rows`` rows -> a list of ints.  ValueError unless there is one per sequence and every span lies inside [0, bank_rows].
+    Pure Python."""
+    host = [int(v) for v in (starts.tolist() if torch.is_tensor(starts) else starts)]
+    if len(host) != lay.N:
+        raise ValueError(f"spans: {len(host)} starts for {lay.N} lengths")
+    bad = [(n, s, v) for n, (s, v) in enumerate(zip(host, lay.lengths)) if s < 0 or s + v > bank_rows]
+    if bad:
+        n, s, v = bad[0]
+        raise ValueError(f"spans: span {n} = rows [{s}, {s + v}) lies outside the bank's [0, {bank_rows}]")
+    return host
+
+
+class ClsConcatSpanFunction(torch.autograd.Function):
+    """``ClsConcatVarFunction`` fed from spans of an HBM-resident ``bank`` [R, d]: the patch tokens of sequence n are its rows
+    ``src0[n] .. src0[n] + L_n - 1`` (``src0``: int64 [N] on the bank's device; spans may overlap, repeat and come in any order), so
+    the token matrix is never materialised (lstc_cls_concat_span_fwd).  The same bits as ``ClsConcatVarFunction`` on the same
+    tokens.  The bank takes no gradient; a learned CLS token and the position table get theirs from lstc_cls_concat_var_bwd."""
+
+    @staticmethod
+    def forward(ctx, bank, src0, cls_token, pos, lay):
+        if bank.dim() != 2 or bank.dtype != torch.float32 or not bank.is_contiguous():
+            raise ValueError(f"ClsConcatSpanFunction: expected a contiguous float32 bank [rows, d], got {tuple(bank.shape)} {bank.dtype}")
+        if src0.dtype != torch.int64 or src0.numel() != lay.N:
+            raise ValueError(f"ClsConcatSpanFunction: expected src0 int64 [{lay.N}], got {tuple(src0.shape)} {src0.dtype}")
+        dm = bank.shape[1]
+        row0 = lay.on(bank.device, 0)["row0"]
+        y = torch.empty((lay.M, dm), device=bank.device, dtype=torch.float32)
+        cls_v, pos_s = _concat_operands(cls_token, pos, lay.S_max)
+        check(_lib.load().lstc_cls_concat_span_fwd(dev_ptr(bank), bank.shape[0], dev_ptr(src0.contiguous()), dev_ptr(row0), dev_ptr(cls_v),
+                                                   dev_ptr(pos_s), dev_ptr(y), lay.N, dm, stream_ptr()), "lstc_cls_concat_span_fwd")
+        ctx.lay, ctx.row0 = lay, row0
+        ctx.meta = (dm, cls_token is not None, pos.shape if pos is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dm, learned, pos_shape = ctx.meta
+        lay = ctx.lay
+        tok = None
+        if learned or pos_shape is not None:
+            dy = dy.contiguous()
+            tok = torch.empty((lay.S_max, dm), device=dy.device, dtype=torch.float32)
+            check(_lib.load().lstc_cls_concat_var_bwd(dev_ptr(dy), dev_ptr(ctx.row0), None, dev_ptr(tok), lay.N, lay.S_max, dm,
+                                                      int(not learned), stream_ptr()), "lstc_cls_concat_var_bwd")
+        return (None, None, *_concat_param_grads(tok, learned, pos_shape), None)
+
+
+def segment_mean(bank: torch.Tensor, first, count, l2: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[s] = the mean of the ``count[s]`` clips ``bank[first[s] : first[s] + count[s]]`` of a bank [clips, P, d] -> [n_seg, P, d]
+    (``lstc_segment_mean``: the 32 bins of every UCF video of a pool in one launch).  The clips are added in order; a count of 1
+    (and anything below: it is clamped) copies the clip bit for bit.  ``l2``: every row of d values is then divided by
+    max(its 2-norm, 1e-12), ``F.normalize(p=2, dim=-1)``.  ``first`` int64 / ``count`` int32 device tensors, or host lists, which are
+    uploaded in one copy each."""
+    if bank.dim() != 3 or bank.dtype != torch.float32 or not bank.is_contiguous():
+        raise TypeError(f"segment_mean: bank must be contiguous float32 [clips, P, d], got {tuple(bank.shape)} {bank.dtype}")
+    if not torch.is_tensor(first):
+        first = torch.tensor([int(v) for v in first], dtype=torch.int64)
+    if not torch.is_tensor(count):
+        count = torch.tensor([int(v) for v in count], dtype=torch.int32)
+    if first.dtype != torch.int64 or count.dtype != torch.int32 or first.dim() != 1 or first.shape != count.shape or first.numel() == 0:
+        raise TypeError("segment_mean: first int64 [n_seg] and count int32 [n_seg], n_seg >= 1")
+    if not bank.is_cuda:
+        raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+    first, count = first.to(bank.device).contiguous(), count.to(bank.device).contiguous()
+    n_seg, (_, P, d) = first.numel(), bank.shape
+    if out is None:
+        out = torch.empty((n_seg, P, d), device=bank.device, dtype=torch.float32)
+    check(_lib.load().lstc_segment_mean(dev_ptr(bank), bank.shape[0], dev_ptr(first), dev_ptr(count), n_seg, P, d, int(bool(l2)),
+                                        dev_ptr(out), stream_ptr()), "lstc_segment_mean")
+    return out
+
+
 def lengths_arg(lengths, N, S, device):
     """Normalise the ``lengths`` of a padded batch of N sequences with S - 1 token slots: a Python sequence or a CPU tensor is
     range-checked here (ValueError; 1 <= L <= S - 1) and copied to ``device``; a device tensor is taken as it is, without a host

@@ -225,6 +225,20 @@ def _test_set(dialect, txt_path, mask_dir, h5_file, return_names, reshape=None):
     return (feats, labels, annos, names) if return_names else (feats, labels, annos)
 
 
+def test_list(dialect, txt_path, mask_dir):
+    """The list side of ``_test_set`` without a feature read -> (keys, annos) in file order: what a pass over an HBM-resident
+    test set (pipeline.ResidentSet) still needs from the host.  ``dialect``: "sht" | "ubnormal"."""
+    keys, annos = [], []
+    for line in open(txt_path, "r").readlines():
+        parts = line.strip().split(",")
+        key = parts[0]
+        abnormal = (parts[1] == "1") if dialect == _SHT else (key.split("_")[0] == "abnormal")
+        n_frames = parts[-1] if dialect == _SHT else parts[1]
+        annos.append(np.load(os.path.join(mask_dir, key + ".npy")) if abnormal else np.zeros(int(n_frames)))
+        keys.append(key)
+    return keys, annos
+
+
 def shanghaitech_test(txt_path, mask_dir, h5_file, return_names=False):
     """utils/load_dataset.py:108-132: lines ``name,label,...,n_frames``; frame masks ``<mask_dir>/<name>.npy``."""
     return _test_set(_SHT, txt_path, mask_dir, h5_file, return_names)

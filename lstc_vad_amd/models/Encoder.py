@@ -2,8 +2,8 @@
 import torch
 from torch import nn
 
-from ..functional import (ClsConcatFunction, ClsConcatLenFunction, ClsConcatVarFunction, DropoutFunction, LayerNormFunction, PackedAct,
-                          act_chain_ok, drop_producer_packs, lengths_arg, unpadded_layout)
+from ..functional import (ClsConcatFunction, ClsConcatLenFunction, ClsConcatSpanFunction, ClsConcatVarFunction, DropoutFunction,
+                          LayerNormFunction, PackedAct, act_chain_ok, drop_producer_packs, lengths_arg, span_starts, unpadded_layout)
 from .EncoderLayer import EncoderLayer
 from .MultiHeadAttention import key_padding_mask
 
@@ -204,6 +204,13 @@ class Encoder(nn.Module):
         lay = unpadded_layout(lengths)
         if lay.in0[-1] != x.shape[0]:
             raise ValueError(f"Encoder: the lengths sum to {lay.in0[-1]} tokens, the input has {x.shape[0]} rows")
+        self._layout_fits(lay)
+        if not x.is_cuda:
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        return lay
+
+    def _layout_fits(self, lay):
+        """ValueError where a sequence of the unpadded layout ``lay`` is beyond what the attention bias or the position table hold."""
         attn0 = self.layer_stack[0].slf_attn
         if attn0.relative_pe_2D and any(v != attn0.window_size ** 2 for v in lay.lengths):
             raise ValueError(f"Encoder: relative_pe_2D needs window_size**2 = {attn0.window_size ** 2} patch tokens in every sequence")
@@ -212,9 +219,6 @@ class Encoder(nn.Module):
                              f"({attn0.relative_position_index.shape[0]} tokens)")
         if self.position_encoding and lay.S_max > self.position_enc.shape[1]:
             raise ValueError(f"Encoder: {lay.S_max} tokens exceed max_position_tokens = {self.position_enc.shape[1]}")
-        if not x.is_cuda:
-            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
-        return lay
 
     def _embed_unpadded(self, x, lay):
         """``_embed`` of an unpadded batch -> [1, M, d_model]: the input LayerNorm is row-wise, the concat knows the offsets."""
@@ -254,6 +258,48 @@ class Encoder(nn.Module):
         ``eval()`` bit for bit.  Arguments and refusals as in ``forward_unpadded``."""
         lay = self._unpadded(enc_output, lengths, enc_output_hi, src_mask)
         h = self._embed_unpadded(enc_output, lay)
+        n = len(self.layer_stack)
+        for i, layer in enumerate(self.layer_stack[:-1]):
+            layer.pos_ffn._emit_pack = i + 1 < n - 1
+            layer.slf_attn._act16_out = layer.pos_ffn._act16_out = False
+            h = layer(h, seqs=lay)[0]
+        out = self.layer_stack[-1].forward_cls(h, seqs=lay)
+        drop_producer_packs()
+        return out
+
+    def forward_cls_spans(self, bank, starts, lengths):
+        """``forward_cls_unpadded`` fed from SPANS of an HBM-resident bank: ``bank`` is [R, d_model] float32 on the device (or
+        [clips, P, d_model], viewed as its clips * P rows), sequence n the rows ``starts[n] .. starts[n] + lengths[n] - 1``.  ``starts``
+        and ``lengths`` are host integers (Python sequences or CPU tensors); the lengths obey ``forward_cls_unpadded``'s rules.  Spans
+        may overlap, repeat and come in any order.  Returns [N, d_model]: row n is what ``forward_cls_unpadded(bank[starts[n] :
+        starts[n] + L_n], [L_n])`` returns - in ``eval()`` bit for bit in every compute mode, because only the CLS concat differs
+        (lstc_cls_concat_span_fwd) and it writes the same bits; the tokens are never materialised.  The bank takes no gradient; in
+        training mode ``cls_token`` and ``position_enc`` get theirs.  Refused before any launch, and before the bank's device
+        matters: ``input_layerNorm`` (it would need the tokens materialised), a bank that requires grad, a span outside [0, R], a
+        different number of starts and lengths (ValueError), a PackedAct (NotImplementedError)."""
+        if isinstance(bank, PackedAct):
+            raise NotImplementedError("Encoder: spans need an f32 bank (no PackedAct input)")
+        if self.input_layerNorm:
+            raise ValueError("Encoder: spans of a bank cannot feed the input LayerNorm (materialise the tokens and use forward_cls_unpadded)")
+        if not torch.is_tensor(bank) or bank.dim() not in (2, 3) or bank.dtype != torch.float32:
+            raise ValueError("Encoder: spans need a float32 bank [rows, d_model] or [clips, P, d_model], got "
+                             f"{tuple(bank.shape) if torch.is_tensor(bank) else type(bank).__name__}")
+        if bank.requires_grad:
+            raise ValueError("Encoder: a bank takes no gradient (detach it, or materialise the tokens and use forward_cls_unpadded)")
+        rows = bank.reshape(-1, bank.shape[-1]) if bank.is_contiguous() else None
+        if rows is None:
+            raise ValueError("Encoder: spans need a contiguous bank")
+        lay = unpadded_layout(lengths)
+        src0 = span_starts(starts, lay, rows.shape[0])
+        self._layout_fits(lay)
+        if not bank.is_cuda:
+            raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+        src0 = torch.tensor(src0, dtype=torch.int64).to(bank.device)
+        h = ClsConcatSpanFunction.apply(rows, src0, self.cls_token if self.CLS_learned else None,
+                                        self.position_enc if self.position_encoding else None, lay)
+        if self.position_encoding and self.training and self.position_dropout.p > 0:
+            h = DropoutFunction.apply(h, self.position_dropout.p, "position_dropout")
+        h = h.view(1, lay.M, -1)
         n = len(self.layer_stack)
         for i, layer in enumerate(self.layer_stack[:-1]):
             layer.pos_ffn._emit_pack = i + 1 < n - 1

@@ -22,6 +22,11 @@ computed from the complete vector on every rank and are bit-identical to a singl
 sequence's score does not depend on what shares its batch).  In the reference this evaluation runs on GPU 0 every
 ``inter_epoch`` epochs over all test AND train videos (Train/temporal_transformer_shanghaitech.py:151-229) while the other
 GPUs idle.
+
+**Resident sets.**  ``resident=ResidentSet`` on any pass: the videos were uploaded once into one HBM bank, a pass registers every
+part of every video as a SPAN of bank rows (``scoring.part_spans``, ``ucf_bin_table`` / ``ucf_bin_spans``) and the pool is scored
+from the bank (``scoring.resident_sequence_scores``) - no archive read, no upload and no sequence cut out per pass; the UCF bins of
+a pool come from one ``lstc_segment_mean`` launch.  Lists, masks, ``finish`` closures, thresholds, AUC and sharding are the same code.
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ import torch
 
 from . import scoring
 from .archive import FeatureArchive
-from .load_dataset import UBnormal_test, UCF_test, UCF_train, _ucf_line, shanghaitech_test
+from .load_dataset import UBnormal_test, UCF_test, UCF_train, _ucf_line, shanghaitech_test, test_list
 from .metrics import roc_auc
 
 
@@ -49,6 +54,117 @@ def _dev(a, device, n_patch=None):
     return t.to(device).contiguous()
 
 
+def _plain_key(key):
+    return key[:-4] if key.endswith(".npy") else key
+
+
+class ResidentSet:
+    """The videos of a test or label list in ONE ``[total_clips, P, d]`` float32 bank on the device: ``keys`` (list order, without
+    ``.npy``), ``lens`` (clips of every video) and ``offsets`` (first clip of a video in the bank; -1 where this rank holds none).
+    Built once, then handed to ``evaluate_auc`` / ``evaluate_train_auc`` / ``generate_pseudo_labels`` as ``resident=``: those passes
+    read no archive and upload nothing.  ``n_patch`` / ``view`` say how a stored array becomes clips, as the host-fed pass of the
+    same data does: ``view=False`` a 3-D array [n, P_stored, d] cut to its first ``n_patch`` patches (None: all - the STN label
+    generator), ``view=True`` any array viewed ``[-1, n_patch, d]`` (the UCF routes).  ``owns(i)``: upload only the videos this rank
+    scores (``i % world == rank``); the others keep their clip counts, which every rank needs."""
+
+    def __init__(self, bank, offsets, lens, keys):
+        self.bank, self.keys = bank, [_plain_key(k) for k in keys]
+        self.offsets, self.lens = np.asarray(offsets, dtype=np.int64), np.asarray(lens, dtype=np.int64)
+        self._at = {k: i for i, k in enumerate(self.keys)}
+
+    @staticmethod
+    def clip_shape(shape, n_patch=None, view=False):
+        """(clips, P, d) a stored array of ``shape`` contributes."""
+        shape = tuple(int(v) for v in shape)
+        if view or len(shape) != 3:
+            P = int(n_patch or 1)
+            return int(np.prod(shape)) // (P * shape[-1]), P, shape[-1]
+        return shape[0], (shape[1] if n_patch is None else min(int(n_patch), shape[1])), shape[2]
+
+    @staticmethod
+    def bytes(shapes, n_patch=None, view=False, owns=None) -> int:
+        """Bytes of the bank (fp32) of videos with the stored ``shapes`` (``archive_shapes``), from the shapes alone."""
+        return int(sum(4 * int(np.prod(ResidentSet.clip_shape(shp, n_patch, view)))
+                       for i, shp in enumerate(shapes) if owns is None or owns(i)))
+
+    @staticmethod
+    def archive_shapes(path, keys):
+        with FeatureArchive(path) as arc:
+            return [tuple(arc.shape(_plain_key(k) + ".npy")) for k in keys]
+
+    @classmethod
+    def _build(cls, shapes, fetch, keys, device, n_patch, view, owns):
+        cs = [cls.clip_shape(shp, n_patch, view) for shp in shapes]
+        if not cs:
+            raise ValueError("ResidentSet: no videos")
+        if any(c[1:] != cs[0][1:] for c in cs):
+            raise ValueError("ResidentSet: the videos do not share one clip shape [P, d]")
+        mine = [owns is None or bool(owns(i)) for i in range(len(cs))]
+        lens = [c[0] for c in cs]
+        offsets, tot = [], 0
+        for n, m in zip(lens, mine):
+            offsets.append(tot if m else -1)
+            tot += n if m else 0
+        _, P, d = cs[0]
+        bank = torch.empty((tot, P, d), dtype=torch.float32, device=device)
+        for i, (o, n, m) in enumerate(zip(offsets, lens, mine)):      # one staged copy per video: only the video in flight is on the host
+            if not m or n == 0:
+                continue
+            a = np.asarray(fetch(i))
+            a = a.reshape(-1, P, d) if (view or a.ndim != 3) else a[:, :P, :]
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if not a.flags.writeable:                 # a memory-mapped member of a directory archive: read it (torch wants writable memory)
+                a = a.copy()
+            bank[o:o + n].copy_(torch.from_numpy(a))
+        return cls(bank, offsets, lens, keys)
+
+    @classmethod
+    def from_arrays(cls, arrays, device, keys=None, n_patch=None, view=False, owns=None):
+        """From host arrays, one per video (``keys`` default to their positions)."""
+        arrays = list(arrays)
+        keys = [str(i) for i in range(len(arrays))] if keys is None else list(keys)
+        if len(keys) != len(arrays):
+            raise ValueError(f"ResidentSet: {len(keys)} keys for {len(arrays)} videos")
+        return cls._build([np.shape(a) for a in arrays], lambda i: arrays[i], keys, device, n_patch, view, owns)
+
+    @classmethod
+    def from_archive(cls, path, keys, device, n_patch=None, view=False, owns=None):
+        """From a feature archive: a shape pass, then one read and one staged copy per video."""
+        keys = [_plain_key(k) for k in keys]
+        with FeatureArchive(path) as arc:
+            shapes = [tuple(arc.shape(k + ".npy")) for k in keys]
+            return cls._build(shapes, lambda i: arc[keys[i] + ".npy"], keys, device, n_patch, view, owns)
+
+    @classmethod
+    def from_pairs(cls, pairs):
+        """Wrap the bank of a ``load_dataset.ResidentPairs`` - the training set already in HBM - without a copy: for
+        ``evaluate_train_auc``.  Single-crop banks only."""
+        if getattr(pairs, "crops", 1) != 1:
+            raise ValueError("ResidentSet.from_pairs: a ten-crop bank holds ten crops per clip; only single-crop banks are scored "
+                             "from HBM")
+        bank = pairs.bank if pairs.bank.dim() == 3 else pairs.bank.view(pairs.bank.shape[0], 1, -1)
+        offsets = np.asarray(pairs.offsets, dtype=np.int64)
+        return cls(bank, offsets[:-1], np.diff(offsets), list(pairs.ds.norm_keys) + list(pairs.ds.abnorm_keys))
+
+    def __len__(self):
+        return len(self.keys)
+
+    def n_clips(self, key):
+        return int(self.lens[self._at[_plain_key(key)]])
+
+    def first_clip(self, key):
+        """First clip of the video in the bank; ValueError where this rank did not upload it."""
+        o = int(self.offsets[self._at[_plain_key(key)]])
+        if o < 0:
+            raise ValueError(f"ResidentSet: video {key!r} was not uploaded on this rank (owns)")
+        return o
+
+    def patches(self, n_patch, what):
+        if self.bank.shape[1] != n_patch:
+            raise ValueError(f"{what}: the resident bank holds {self.bank.shape[1]} patches per clip, the pass scores n_patch = {n_patch}")
+        return int(n_patch)
+
+
 def _ranks(rank, world, group):
     """(rank, world) of a pass: explicit arguments, else the initialised process group, else a single rank."""
     if world is None:
@@ -65,8 +181,12 @@ class _ScoreBoard:
     rank``) also hands over the work (sequences to pool, or a closure that scores the clips).  ``results()`` scores what is
     owned, sums the zero-padded flat vector over the ranks and runs every video's ``finish`` on every rank."""
 
-    def __init__(self, enc, head, device, rank, world, group, pool_sequences, exchange=None, ragged=False):
+    def __init__(self, enc, head, device, rank, world, group, pool_sequences, exchange=None, ragged=False, resident=None,
+                 classifier_head=True, ucf=None):
+        # resident: the pool holds spans of resident.bank's rows (add_spans) or, with ``ucf`` = dict(part_len, rewindow, l2), the
+        # (first, count) bin tables of UCF videos (add_bins); classifier_head: the head's output of a pooled span (STN: a Regressor)
         self.enc, self.head, self.device, self.ragged = enc, head, device, ragged
+        self.resident, self.classifier_head, self.ucf = resident, classifier_head, ucf
         self.rank, self.world, self.group, self.exchange = rank, world, group, exchange
         self.pool_sequences = pool_sequences
         self.items, self.total = [], 0             # (offset, count, finish) in list order
@@ -93,6 +213,48 @@ class _ScoreBoard:
             if self.pooled >= self.pool_sequences:
                 self.flush()
 
+    def add_spans(self, i, count, make_spans, finish):
+        """A video of a resident set: ``make_spans() -> [(first_row, n_tokens)]`` of the bank, one per score."""
+        off = self._register(count, finish)
+        if self.owns(i):
+            spans = make_spans()
+            if len(spans) != count:
+                raise RuntimeError(f"video {i}: {len(spans)} spans, {count} announced")
+            self.pool.append((off, spans))
+            self.pooled += count
+            if self.pooled >= self.pool_sequences:
+                self.flush()
+
+    def add_bins(self, i, count, make_table, finish):
+        """A UCF video of a resident set: ``make_table() -> (first [32], count [32])``, its bins as runs of bank clips."""
+        off = self._register(count, finish)
+        if self.owns(i):
+            self.pool.append((off, make_table()))
+            self.pooled += count
+            if self.pooled >= self.pool_sequences:
+                self.flush()
+
+    def _flush_resident(self):
+        bank = self.resident.bank
+        if self.ucf is not None:
+            # the bins of every pooled video in one launch -> a bins bank [32 * videos, P, d], then spans of that bank
+            from . import functional as Fn
+            first = [v for _, (f, _c) in self.pool for v in f]
+            count = [v for _, (_f, c) in self.pool for v in c]
+            n_bins = len(self.pool[0][1][0])
+            bank = Fn.segment_mean(bank, first, count, l2=self.ucf["l2"])
+            per = [scoring.ucf_bin_spans(self.ucf["part_len"], self.ucf["rewindow"], bank.shape[1], v * n_bins, n_bins)
+                   for v in range(len(self.pool))]
+        else:
+            per = [spans for _, spans in self.pool]
+        sc = scoring.resident_sequence_scores(self.enc, self.head, bank, [q for spans in per for q in spans], ragged=self.ragged,
+                                              classifier_head=self.classifier_head)
+        o = 0
+        for (off, _), spans in zip(self.pool, per):
+            self.parts.append((off, sc[o:o + len(spans)]))
+            o += len(spans)
+        self.pool, self.pooled = [], 0
+
     def add_clips(self, i, count, score, finish):
         off = self._register(count, finish)
         if self.owns(i):
@@ -104,6 +266,8 @@ class _ScoreBoard:
     def flush(self):
         if not self.pool:
             return
+        if self.resident is not None:
+            return self._flush_resident()
         sc = scoring.ltn_sequence_scores(self.enc, self.head, [q for _, seqs in self.pool for q in seqs],
                                          **({"ragged": self.ragged} if self.ragged else {}))
         o = 0
@@ -136,14 +300,21 @@ def _threshold(scores_np, threshold):
 @torch.no_grad()
 def generate_pseudo_labels(enc, head, mode, dataset, dataset_path, training_txt, threshold, part_len=1, n_patch=16,
                            d_model=None, segment_len=16, classifier_head=False, out_path=None, pool_sequences=2048,
-                           rank=None, world=None, group=None, exchange=None, ragged=False):
+                           rank=None, world=None, group=None, exchange=None, ragged=False, resident=None):
     """mode 'STN' | 'LTN'; dataset 'SHT' | 'UCF' | 'UBnormal'.  Returns the dict (and writes it when ``out_path`` - on rank 0
     only under several ranks; every rank returns the complete dict).  ``ragged``: the pooled LTN parts of all lengths (the short
     tail parts of ``tail='short'``) share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: they share batches without
-    padding (parts of at most 127 patch tokens)."""
+    padding (parts of at most 127 patch tokens).  ``resident``: a ``ResidentSet`` of the list's videos (STN: every stored patch,
+    ``n_patch=None``; UCF: ``view=True``) - the archive is not opened and nothing is uploaded."""
     device = next(enc.parameters()).device
     d_model = d_model or enc.layer_norm.normalized_shape[0]
     rank, world = _ranks(rank, world, group)
+    if resident is not None:
+        return _generate_resident(enc, head, mode, dataset, training_txt, threshold, part_len, n_patch, segment_len, classifier_head,
+                                  out_path, _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged, resident,
+                                                        classifier_head=(mode != "STN" or classifier_head),
+                                                        ucf=dict(part_len=part_len, rewindow=False, l2=False)
+                                                        if (mode != "STN" and dataset == "UCF") else None))
     board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged)
     keys = []
 
@@ -177,6 +348,37 @@ def generate_pseudo_labels(enc, head, mode, dataset, dataset_path, training_txt,
     return out
 
 
+def _label_rows(ranges, threshold):
+    return lambda v: _threshold(np.concatenate([np.repeat(x, e - b) for x, (b, e) in zip(v, ranges)]), threshold)
+
+
+def _generate_resident(enc, head, mode, dataset, training_txt, threshold, part_len, n_patch, segment_len, classifier_head, out_path,
+                       board):
+    """``generate_pseudo_labels`` over a ResidentSet: the same list walk, every video registered as spans of the bank."""
+    rs, keys = board.resident, []
+    # the host-fed generators score every stored patch (no cut to n_patch); only the UCF route views the rows as [-1, n_patch, d]
+    P = rs.patches(n_patch, "generate_pseudo_labels") if (mode != "STN" and dataset == "UCF") else rs.bank.shape[1]
+    for i, (line, key) in enumerate(_train_keys(dataset, training_txt)):
+        keys.append(key + ".npy")
+        n = rs.n_clips(key)
+        if mode == "STN":
+            board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0],
+                            lambda v: _threshold(v, threshold))
+        elif dataset == "UCF":
+            ranges = scoring.ucf_bin_ranges(part_len, rewindow=False)
+            n_frames = _ucf_line(line)[1]
+            board.add_bins(i, len(ranges), lambda key=key, n=n, n_frames=n_frames: scoring.ucf_bin_table(
+                n_frames, segment_len, first_clip=rs.first_clip(key), n_clips=n), _label_rows(ranges, threshold))
+        else:
+            ranges = scoring.part_ranges(n, part_len)
+            board.add_spans(i, len(ranges), lambda key=key, n=n: scoring.part_spans(n, part_len, P, "short", rs.first_clip(key))[0],
+                            _label_rows(ranges, threshold))
+    out = dict(zip(keys, board.results()))
+    if out_path and board.rank == 0:
+        np.save(out_path, out)
+    return out
+
+
 def _auc_of(rows, return_frames):
     s, l = np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows])
     auc = roc_auc(s, l)
@@ -185,14 +387,21 @@ def _auc_of(rows, return_frames):
 
 @torch.no_grad()
 def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, part_len, n_patch, segment_len=16,
-                 return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, ragged=False):
+                 return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, ragged=False,
+                 resident=None):
     """``masks``: directory of ``<video>.npy`` frame masks (SHT / UBnormal, ``--test_mask_dir``) or the ground-truth
     archive (UCF, ``--test_mask_path``).  LTN only scores parts; STN scores clips (in-loop evaluation of the spatio
     scripts, Train/spatio_transformer_shanghaitech.py:118-150: every clip's score x segment_len).  ``ragged``: pooled LTN
-    parts of all lengths share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: batches without padding."""
+    parts of all lengths share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: batches without padding.
+    ``resident``: a ``ResidentSet`` of the list's videos, cut to ``n_patch`` (UCF: ``view=True``) - ``dataset_path`` is not opened,
+    nothing is uploaded, STN clips are pooled like LTN parts and the UCF bins of a pool are one ``lstc_segment_mean`` launch."""
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
-    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged)
+    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged, resident,
+                        classifier_head=(mode == "LTN"),
+                        ucf=dict(part_len=part_len, rewindow=True, l2=True) if (dataset == "UCF" and mode == "LTN") else None)
+    rs = resident
+    P = rs.patches(n_patch, "evaluate_auc") if rs is not None else n_patch
 
     def stn_finish(anno):
         def fin(v):
@@ -202,7 +411,7 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
 
     if dataset == "UCF":
         for i, line in enumerate(open(testing_txt, "r").readlines()):
-            if board.owns(i):
+            if rs is None and board.owns(i):
                 feats, anno, n_frames, _ = UCF_test(line, dataset_path, masks, segment_len, return_name=True)
             else:                                    # not ours: the list line and the ground truth say everything but the scores
                 key, n_frames, fields = _ucf_line(line)
@@ -212,6 +421,18 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
                 else:
                     with FeatureArchive(masks) as gt:
                         anno = np.asarray(gt[key + ".npy"])
+            if rs is not None:
+                n = rs.n_clips(key)
+                if mode != "LTN":
+                    board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0],
+                                    stn_finish(anno))
+                    continue
+                ranges = scoring.ucf_bin_ranges(part_len, rewindow=True)
+                r = scoring.ucf_bin_edges(n_frames, segment_len)
+                board.add_bins(i, len(ranges), lambda key=key, n=n, n_frames=n_frames: scoring.ucf_bin_table(
+                    n_frames, segment_len, first_clip=rs.first_clip(key), n_clips=n),
+                    lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len))
+                continue
             if mode != "LTN":
                 if feats is None:
                     with FeatureArchive(dataset_path) as arc:
@@ -234,6 +455,16 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
                                                      normalize=True, rewindow=True)[0]
             board.add_ltn(i, len(ranges), make,
                           lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len))
+    elif rs is not None:
+        keys, annos = test_list("sht" if dataset in ("SHT", "MT_SHT") else "ubnormal", testing_txt, masks)
+        for i, (key, anno) in enumerate(zip(keys, annos)):
+            n = rs.n_clips(key)
+            if mode != "LTN":
+                board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], stn_finish(anno))
+                continue
+            ranges = scoring.part_ranges(n, part_len)
+            board.add_spans(i, len(ranges), lambda key=key, n=n: scoring.part_spans(n, part_len, P, "rewindow", rs.first_clip(key))[0],
+                            lambda v, ranges=ranges, anno=anno: scoring.frame_scores_sht(v, ranges, anno, segment_len))
     else:
         loader = shanghaitech_test if dataset in ("SHT", "MT_SHT") else UBnormal_test
         feats_l, _, annos = loader(testing_txt, masks, dataset_path)
@@ -252,23 +483,27 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
 
 @torch.no_grad()
 def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, mask_dir, part_len, n_patch, segment_len=16,
-                       return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None):
+                       return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, resident=None):
     """Frame-level AUC over the TRAINING videos, the quantity the SHT / UBnormal train scripts select checkpoints on
     (Train/temporal_transformer_shanghaitech.py:186-229, Train/spatio_transformer_shanghaitech.py:145-172,
     Train/temporal_transformer_UBnormal.py:193-232): every training video is scored like a test video; a normal video's
     frames are labelled 0, an abnormal video's labels are the first frames of ``mask_dir + key + ".npy"`` (the upstream
     string concatenation - ``--test_mask_dir`` holds the masks of the training videos too).  Video class: second list
-    field (SHT ``name,label``) or the ``abnormal`` / ``normal`` name prefix (UBnormal)."""
+    field (SHT ``name,label``) or the ``abnormal`` / ``normal`` name prefix (UBnormal).  ``resident``: a ``ResidentSet`` of the
+    training videos - ``ResidentSet.from_pairs(feed)`` wraps the training bank already in HBM - instead of ``train_archive``."""
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
-    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange)
+    rs = resident
+    board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, False, rs, classifier_head=(mode == "LTN"))
+    P = rs.patches(n_patch, "evaluate_train_auc") if rs is not None else n_patch
 
     def frame_labels(abnormal, key, n):
         if not abnormal:
             return np.zeros(n)
         return np.asarray(np.load(mask_dir + key + ".npy", allow_pickle=True))[:n]
 
-    with FeatureArchive(train_archive) as arc:
+    import contextlib
+    with (FeatureArchive(train_archive) if rs is None else contextlib.nullcontext()) as arc:
         for i, line in enumerate(open(training_txt, "r").readlines()):
             fields = line.strip().split(",")
             key = fields[0]
@@ -281,11 +516,14 @@ def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, ma
                 # the published UBnormal list holds a FRAME COUNT there (train_video_names_frames.txt; upstream then looks for
                 # a mask of every video and stops) - the class of such a line comes from the file name
                 abnormal = not key.startswith("normal")
-            n = arc.shape(key + ".npy")[0]
+            n = arc.shape(key + ".npy")[0] if rs is None else rs.n_clips(key)
             if mode != "LTN":
                 def fin(v, abnormal=abnormal, key=key):
                     s = np.repeat(v, segment_len)
                     return s, frame_labels(abnormal, key, s.shape[0])
+                if rs is not None:
+                    board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], fin)
+                    continue
                 board.add_clips(i, n, lambda key=key: scoring.stn_clip_scores(enc, head, _dev(arc[key + ".npy"], device, n_patch)), fin)
                 continue
             ranges = scoring.part_ranges(n, part_len)
@@ -293,6 +531,10 @@ def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, ma
             def expand(v, ranges=ranges, abnormal=abnormal, key=key):
                 sfr = np.concatenate([np.full((e - b) * segment_len, float(x), np.float32) for x, (b, e) in zip(v, ranges)])
                 return sfr, frame_labels(abnormal, key, sfr.shape[0])
+            if rs is not None:
+                board.add_spans(i, len(ranges), lambda key=key, n=n: scoring.part_spans(n, part_len, P, "rewindow", rs.first_clip(key))[0],
+                                expand)
+                continue
             board.add_ltn(i, len(ranges),
                           lambda key=key: scoring.ltn_part_sequences(_dev(arc[key + ".npy"], device, n_patch), part_len, tail="rewindow")[0],
                           expand)

@@ -18,6 +18,9 @@ Recipes (all return per-part scores plus the ``(beg, end)`` clip ranges they sta
 * ``ltn_ucf_bin_scores``   - UCF: clips averaged into 32 bins (``np.linspace(0, n_frames // segment_len, 33)``), parts
                              of ``part_len`` bins, optional L2 normalisation (Test/evaluation_UCF.py:54-77 normalises,
                              Train/pseudo_labels_generator_temporal.py:73-99 does not).
+
+The same parts on an HBM-resident bank (``pipeline.ResidentSet``) are not cut out but described: ``part_spans``, ``ucf_bin_table`` and
+``ucf_bin_spans`` give every part as a span of bank rows (pure Python), ``resident_sequence_scores`` scores a pool of spans.
 """
 from __future__ import annotations
 
@@ -65,9 +68,16 @@ def unpadded_batches(seqs, max_batch=4096, max_rows=None):
         if s.shape[0] + 1 > 128:
             raise ValueError(f"ragged='unpadded': sequence {i} has {s.shape[0]} patch tokens, the unpadded route takes at most 127 "
                              "(128 tokens with the CLS token); use ragged=True for this pool")
+    batches = unpadded_chunks([int(s.shape[0]) for s in seqs], max_batch, max_rows)
+    return [(ids, torch.cat([seqs[i] for i in ids], 0), [int(seqs[i].shape[0]) for i in ids]) for ids in batches]
+
+
+def unpadded_chunks(lengths, max_batch, max_rows):
+    """The chunking rule of ``unpadded_batches`` on the lengths alone -> lists of consecutive positions: up to ``max_batch``
+    sequences and ``max_rows`` rows (CLS tokens counted) per chunk, a single sequence always fits.  Pure Python."""
     batches, ids, rows = [], [], 0
-    for i, s in enumerate(seqs):
-        r = int(s.shape[0]) + 1
+    for i, v in enumerate(lengths):
+        r = int(v) + 1
         if ids and (len(ids) >= max_batch or rows + r > max_rows):
             batches.append(ids)
             ids, rows = [], 0
@@ -75,7 +85,7 @@ def unpadded_batches(seqs, max_batch=4096, max_rows=None):
         rows += r
     if ids:
         batches.append(ids)
-    return [(ids, torch.cat([seqs[i] for i in ids], 0), [int(seqs[i].shape[0]) for i in ids]) for ids in batches]
+    return batches
 
 
 def ltn_sequence_scores(enc, head, seqs, max_batch=4096, ragged=False):
@@ -185,6 +195,98 @@ def ltn_ucf_bin_scores(enc, head, feats, n_frames, part_len, segment_len=16, nor
                        ragged=False):
     seqs, ranges, r = ltn_ucf_bin_sequences(feats, n_frames, part_len, segment_len, normalize, rewindow, max_clips)
     return ltn_sequence_scores(enc, head, seqs, ragged=ragged), ranges, r
+
+
+# -- spans of an HBM-resident bank: the same parts, described instead of cut out ---------------------------------------------------
+
+def part_spans(n, part_len, n_patch=1, tail="rewindow", first_clip=0):
+    """``ltn_part_sequences`` of a video of ``n`` clips that lies in a bank [clips, n_patch, d] from clip ``first_clip``, as spans
+    of the bank's ROWS -> ([(first_row, n_tokens)], [(beg, end)]): span k holds the rows ``ltn_part_sequences`` stacks into sequence
+    k.  ``tail='rewindow'`` moves a short tail part back with the slice semantics of the reference (``feats[end - part_len:end]``: a
+    video shorter than one part yields the clips its negative slice start selects).  ``part_len=1`` are the clips of an STN.  Pure
+    Python."""
+    ranges = part_ranges(n, part_len)
+    spans = []
+    for beg, end in ranges:
+        b, e = beg, end
+        if end - beg < part_len and tail == "rewindow":
+            b, e, _ = slice(end - part_len, end).indices(n)
+        spans.append(((first_clip + b) * n_patch, (e - b) * n_patch))
+    return spans, ranges
+
+
+def ucf_bin_table(n_frames, segment_len=16, max_clips=32, first_clip=0, n_clips=None):
+    """``ucf_bins`` as a table for ``functional.segment_mean`` -> (first [32], count [32]) in clips of the bank: bin i is the mean of
+    ``count[i]`` clips from ``first[i]``; an empty bin (``r[i] == r[i + 1]``) is clip ``r[i]`` alone, a count of 1.  ``n_clips``: the
+    clips the video really has - a bin ends there, as the host route's slices do.  Pure Python."""
+    r = ucf_bin_edges(n_frames, segment_len, max_clips)
+    first, count = [], []
+    for i in range(max_clips):
+        a, b = int(r[i]), int(r[i + 1])
+        if n_clips is not None:
+            if a >= n_clips:
+                raise ValueError(f"ucf_bin_table: bin {i} starts at clip {a}, the video has {n_clips}")
+            b = min(b, n_clips)
+        first.append(first_clip + a)
+        count.append(max(b - a, 1))
+    return first, count
+
+
+def ucf_bin_spans(part_len, rewindow=True, n_patch=1, first_bin=0, max_clips=32):
+    """The parts of ``ucf_bin_ranges`` as spans of the rows of a bins bank [bins, n_patch, d] in which the video's 32 bins lie from
+    bin ``first_bin`` -> [(first_row, n_tokens)].  Pure Python."""
+    return [((first_bin + b) * n_patch, (e - b) * n_patch) for b, e in ucf_bin_ranges(part_len, rewindow, max_clips)]
+
+
+def resident_sequence_scores(enc, head, bank, spans, max_batch=4096, ragged=False, classifier_head=True):
+    """``ltn_sequence_scores`` on sequences that are SPANS ``(first_row, n_tokens)`` of the rows of an HBM-resident ``bank``
+    ([clips, P, d] float32 on the device, or [rows, d]) -> tensor [len(spans)], input order.  No sequence is cut out or copied.
+    ``ragged=False``: spans of the same length share a batch of up to ``max_batch`` and go through the encoder's gather spec
+    (``enc.forward_cls((bank, clip_idx, N, Lc))``: the fixed-layout kernels; the spans must be whole clips of a 3-D bank); where
+    that entry refuses (d % 4, an input LayerNorm) the group is gathered (``functional.gather_rows``) and scored by ``forward_cls``.
+    ``ragged="unpadded"``: spans of all lengths share chunks (``unpadded_chunks``, the rule of ``unpadded_batches``) scored by
+    ``Encoder.forward_cls_spans``.  ``ragged=True`` (padded batches) does not exist on a bank.  ``classifier_head``: P(abnormal) is
+    column 1 of the head's two outputs (False: a Regressor's single output)."""
+    if ragged is True or (ragged and ragged != "unpadded"):
+        raise ValueError(f"ragged={ragged!r}: a resident bank is scored with ragged=False (same-length groups through the gather "
+                         "spec) or ragged='unpadded' (spans of all lengths, forward_cls_spans)")
+    spans = [(int(r), int(t)) for r, t in spans]
+    take = (lambda y: y.view(-1, 2)[:, 1]) if classifier_head else (lambda y: y.reshape(-1))
+    out = torch.empty(len(spans), device=bank.device, dtype=torch.float32)
+    if ragged == "unpadded":
+        for i, (_, t) in enumerate(spans):
+            if t + 1 > 128:
+                raise ValueError(f"ragged='unpadded': span {i} has {t} patch tokens, the unpadded route takes at most 127")
+        for ids in unpadded_chunks([t for _, t in spans], max_batch, UNPADDED_ROWS_PER_SEQUENCE * max_batch):
+            cls = enc.forward_cls_spans(bank, [spans[i][0] for i in ids], [spans[i][1] for i in ids])
+            out[ids[0]:ids[-1] + 1] = take(head(cls))
+        return out
+    if bank.dim() != 3:
+        raise ValueError(f"ragged=False scores whole clips of a bank [clips, P, d], got {tuple(bank.shape)}; use ragged='unpadded'")
+    clips, P, d = bank.shape
+    by_len = {}
+    for i, (r, t) in enumerate(spans):
+        if r % P or t % P or t < P or r < 0 or r + t > clips * P:
+            raise ValueError(f"ragged=False: span {i} = rows [{r}, {r + t}) is not a run of whole clips of the bank "
+                             f"[{clips}, {P}, {d}]; use ragged='unpadded'")
+        by_len.setdefault(t // P, []).append(i)
+    spec = d % 4 == 0 and not enc.input_layerNorm
+    if not spec and (P * d) % 4:
+        raise ValueError(f"ragged=False: clips of {P} x {d} floats fit neither the gather spec nor gather_rows; use ragged='unpadded'")
+    if not bank.is_cuda:
+        raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+    from . import functional as Fn
+    for Lc, ids in by_len.items():
+        for c in range(0, len(ids), max_batch):
+            chunk = ids[c:c + max_batch]
+            first = np.asarray([spans[i][0] // P for i in chunk], dtype=np.int64)
+            idx = torch.from_numpy((first[:, None] + np.arange(Lc, dtype=np.int64)[None, :]).reshape(-1)).to(bank.device)
+            if spec:
+                cls = enc.forward_cls((bank, idx, len(chunk), Lc))
+            else:
+                cls = enc.forward_cls(Fn.gather_rows(bank, idx).view(len(chunk), Lc * P, d))
+            out[torch.tensor(chunk, device=out.device)] = take(head(cls))
+    return out
 
 
 def frame_scores_sht(scores, ranges, anno, segment_len=16):

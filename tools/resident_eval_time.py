@@ -1,0 +1,191 @@
+"""Evaluation and label passes fed from the host (the default arguments of pipeline.evaluate_auc / generate_pseudo_labels: every
+video read from the archive, uploaded and cut into sequences per pass) against the same passes on a pipeline.ResidentSet
+(``resident=``: the set uploaded once, every part a span of the HBM bank), and lstc_segment_mean alone.  A measurement tool, not on
+the product path.
+
+Workloads (synthetic features, the reference's sizes):
+  SHT-shaped   ``--sht_videos`` (199) videos of ``--sht_clips`` (190 on average, 60 % .. 140 %) clips, P = 16, d = 2048, LTN part_len 3:
+               evaluate_auc (rewindowed tail) and generate_pseudo_labels (short tail)
+  UCF-shaped   ``--ucf_videos`` (290) videos of ``--ucf_clips`` (100 on average) clips, P = 9, d = 2048, 32 bins, part_len 2
+each in fp32 and in bf16 mode; the label passes run with threshold 0, so that their rows are the scores themselves and ``max |diff|``
+is a score difference in every row of the report.  The archives are directories of .npy files (memory-mapped reads: the host-fed arm runs from the page
+cache after the warm-up round, its best case).  The arms run interleaved, ``--repeats`` (5) rounds after ``--warmup`` (1); each time is
+a host clock around the pass and a device synchronise.  The upload of the resident set is timed once and reported apart.
+Run on an MI355X:  python tools/resident_eval_time.py --work /tmp/resident_eval [--out profiles/resident_eval.txt]"""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lstc_vad_amd import functional as Fn                            # noqa: E402
+from lstc_vad_amd import pipeline, scoring                           # noqa: E402
+from lstc_vad_amd.models import Classifier, Encoder                  # noqa: E402
+
+SEG, D = 16, 2048
+
+
+def _write(root, name, n_videos, mean_clips, P, ucf, seed):
+    """A directory archive, a test list, a train list and the masks of the abnormal half -> dict of paths, clip counts."""
+    rs, gen = np.random.RandomState(seed), np.random.default_rng(seed)
+    feats = os.path.join(root, name + "_feats")
+    masks = os.path.join(root, name + "_masks") + os.sep
+    os.makedirs(feats, exist_ok=True)
+    os.makedirs(masks, exist_ok=True)
+    counts = [max(4, int(mean_clips * (0.6 + 0.8 * rs.rand()))) for _ in range(n_videos)]
+    test, train = [], []
+    for i, n in enumerate(counts):
+        abnormal = i % 2 == 1
+        key = (("Abuse%03d_x264" if abnormal else "Normal_Videos%03d_x264") % i) if ucf else "%02d_%04d" % (1 + i % 13, i)
+        np.save(os.path.join(feats, key + ".npy"), 0.5 * np.maximum(gen.standard_normal((n, P, D), dtype=np.float32), 0))
+        n_frames = n * SEG + 7
+        if abnormal:
+            m = np.zeros(n_frames)
+            m[n_frames // 3: n_frames // 2] = 1.0
+            np.save(os.path.join(masks, key + ".npy"), m)
+        if ucf:
+            test.append(f"Dir/{key}.mp4 {n_frames} {'Abuse' if abnormal else 'Normal'} -1 -1 -1 -1 \n")
+            train.append(f"Dir/{key}.mp4 {n_frames} \n")
+        else:
+            test.append(f"{key},{int(abnormal)},{-1 if abnormal else n_frames}\n")
+            train.append(f"{key},{int(abnormal)}\n")
+    paths = {"feats": feats, "masks": masks.rstrip(os.sep) if ucf else masks, "test": os.path.join(root, name + "_test.txt"),
+             "train": os.path.join(root, name + "_train.txt")}
+    open(paths["test"], "w").write("".join(test))
+    open(paths["train"], "w").write("".join(train))
+    return paths, counts
+
+
+def _time_arms(arms, warmup, repeats):
+    times, last = {k: [] for k in arms}, {}
+    for r in range(warmup + repeats):
+        for name, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[name] = fn()
+            torch.cuda.synchronize()
+            if r >= warmup:
+                times[name].append(time.perf_counter() - t0)
+    return times, last
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--work", required=True, help="scratch directory for the synthetic archives (removed afterwards)")
+    ap.add_argument("--sht_videos", type=int, default=199)
+    ap.add_argument("--sht_clips", type=int, default=190)
+    ap.add_argument("--ucf_videos", type=int, default=290)
+    ap.add_argument("--ucf_clips", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise RuntimeError("resident_eval_time.py measures on the GPU: no device found")
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    os.makedirs(a.work, exist_ok=True)
+    lines, res = [], {"repeats": a.repeats, "rows": []}
+    try:
+        sht, sht_counts = _write(a.work, "sht", a.sht_videos, a.sht_clips, 16, False, 1)
+        ucf, ucf_counts = _write(a.work, "ucf", a.ucf_videos, a.ucf_clips, 9, True, 2)
+        head = Classifier(D).to(dev).eval()
+        encs = {"sht": Encoder(n_layers=3, n_head=8, d_k=256, d_v=256, d_model=D, d_inner=4096, MHA_layerNorm=True, FFN_layerNorm=True,
+                               relative_pe=True, window_size=4, window_depth=3, weight_init=False).to(dev).eval(),
+                "ucf": Encoder(n_layers=3, n_head=8, d_k=256, d_v=256, d_model=D, d_inner=4096, MHA_layerNorm=True, FFN_layerNorm=True,
+                               relative_pe=True, window_size=4, window_depth=2, weight_init=False).to(dev).eval()}
+        keys = lambda txt, is_ucf: [(l.split(" ")[0].split("/")[-1].split(".")[0] if is_ucf else l.split(",")[0])
+                                    for l in open(txt).read().splitlines()]
+        sets, upload = {}, {}
+        for tag, W, P, is_ucf, gen_patch in (("sht", sht, 16, False, None), ("ucf", ucf, 9, True, 9)):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            sets[tag, "ev"] = pipeline.ResidentSet.from_archive(W["feats"], keys(W["test"], is_ucf), dev, n_patch=P, view=is_ucf)
+            torch.cuda.synchronize(); upload[tag] = time.perf_counter() - t0
+            # the label pass walks the same videos: it shares the bank (SHT generators score every stored patch: the same P here)
+            sets[tag, "gen"] = sets[tag, "ev"]
+        lines.append(f"SHT-shaped: {a.sht_videos} videos, {sum(sht_counts)} clips, P = 16, d = {D}, LTN part_len 3 "
+                     f"({sets['sht', 'ev'].bank.numel() * 4 / 2**30:.2f} GiB, uploaded once in {upload['sht']:.2f} s); "
+                     f"UCF-shaped: {a.ucf_videos} videos, {sum(ucf_counts)} clips, P = 9, 32 bins, part_len 2 "
+                     f"({sets['ucf', 'ev'].bank.numel() * 4 / 2**30:.2f} GiB, uploaded once in {upload['ucf']:.2f} s)")
+        lines.append(f"medians of {a.repeats} interleaved runs after {a.warmup} warm-up round(s) (min .. max = the spread); clips/s = clips of "
+                     "the list / median")
+        for mode in ("fp32", "bf16"):
+            Fn.set_compute_dtype(mode)
+            try:
+                for tag, W, P, part_len, dataset, counts in (("sht", sht, 16, 3, "SHT", sht_counts), ("ucf", ucf, 9, 2, "UCF", ucf_counts)):
+                    enc = encs[tag]
+                    ev = lambda rs, ragged=False: pipeline.evaluate_auc(enc, head, "LTN", dataset, W["feats"], W["test"], W["masks"], part_len,
+                                                                        P, return_frames=True, resident=rs, ragged=ragged)
+                    gen = lambda rs, ragged=False: pipeline.generate_pseudo_labels(enc, head, "LTN", dataset, W["feats"], W["train"], 0.0,
+                                                                                   part_len=part_len, n_patch=P, d_model=D, resident=rs,
+                                                                                   ragged=ragged)
+                    passes = [("evaluate_auc", ev, sets[tag, "ev"], False)]
+                    passes.append(("generate_pseudo_labels", gen, sets[tag, "gen"], False))
+                    if tag == "sht":            # the short tail parts of the label pass: all lengths in shared chunks
+                        passes.append(("generate_pseudo_labels ragged='unpadded'", gen, sets[tag, "gen"], "unpadded"))
+                    for what, fn, rs, ragged in passes:
+                        arms = {"host-fed": lambda fn=fn, ragged=ragged: fn(None, ragged), "resident": lambda fn=fn, rs=rs, ragged=ragged: fn(rs, ragged)}
+                        times, last = _time_arms(arms, a.warmup, a.repeats)
+                        if what == "evaluate_auc":
+                            diff = float(np.abs(last["host-fed"][1] - last["resident"][1]).max())
+                        else:
+                            diff = max(float(np.abs(last["host-fed"][k] - last["resident"][k]).max()) for k in last["host-fed"])
+                        row = {"mode": mode, "set": tag, "pass": what, "clips": int(sum(counts)), "max_abs_diff": diff}
+                        for arm in arms:
+                            t = times[arm]
+                            row[arm] = {"median_s": statistics.median(t), "min_s": min(t), "max_s": max(t),
+                                        "clips_per_s": sum(counts) / statistics.median(t)}
+                        row["host_over_resident"] = row["host-fed"]["median_s"] / row["resident"]["median_s"]
+                        res["rows"].append(row)
+                        lines.append(f"  {mode:5s} {tag} {what:42s} host-fed {row['host-fed']['median_s'] * 1e3:9.1f} ms "
+                                     f"({row['host-fed']['min_s'] * 1e3:.1f} .. {row['host-fed']['max_s'] * 1e3:.1f}) = "
+                                     f"{row['host-fed']['clips_per_s'] / 1e3:7.1f} k clips/s | resident {row['resident']['median_s'] * 1e3:9.1f} ms "
+                                     f"({row['resident']['min_s'] * 1e3:.1f} .. {row['resident']['max_s'] * 1e3:.1f}) = "
+                                     f"{row['resident']['clips_per_s'] / 1e3:7.1f} k clips/s | host / resident {row['host_over_resident']:.2f} | "
+                                     f"max |diff| {diff:.1e}")
+            finally:
+                Fn.set_compute_dtype("fp32")
+        # lstc_segment_mean alone: the bins of every UCF-shaped video in one launch
+        rs = sets["ucf", "ev"]
+        first, count = [], []
+        for k, n in zip(rs.keys, ucf_counts):
+            f, c = scoring.ucf_bin_table(n * SEG + 7, first_clip=rs.first_clip(k), n_clips=n)
+            first += f
+            count += c
+        fd, cd = torch.tensor(first, dtype=torch.int64, device=dev), torch.tensor(count, dtype=torch.int32, device=dev)
+        moved = (sum(count) + len(count)) * 9 * D * 4
+        for l2 in (False, True):
+            out = Fn.segment_mean(rs.bank, fd, cd, l2=l2)
+            ts = []
+            for _ in range(3 + 9):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                Fn.segment_mean(rs.bank, fd, cd, l2=l2, out=out)
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1) * 1e-3)
+            t = statistics.median(ts[3:])
+            res["rows"].append({"kernel": "lstc_segment_mean", "l2": l2, "segments": len(count), "bytes": moved, "median_us": t * 1e6,
+                                "GB_per_s": moved / t / 1e9})
+            lines.append(f"  lstc_segment_mean{' + l2' if l2 else '     '}: {len(count)} bins x 9 patches, {moved / 1e6:.0f} MB read + written, "
+                         f"{t * 1e6:.1f} us = {moved / t / 1e9:.0f} GB/s (event-timed, median of 9; a launch this short is partly launch "
+                         f"latency; gather_rows: ~6000 GB/s on an 805 MB batch)")
+    finally:
+        shutil.rmtree(a.work, ignore_errors=True)
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
