@@ -190,7 +190,9 @@ typedef struct LstcAttnDesc {
                                        Q K^T, Pd V and of the four backward products are rounded to bf16 (RNE) in registers and
                                        contracted by v_mfma_f32_32x32x16_bf16 with f32 accumulation; Q, K, V, O, probs and the
                                        gradients stay f32 in memory, softmax / bias / dropout stay f32.  Taken by the staged
-                                       kernels (S <= 96, dk and dv multiples of 32, 16-B aligned operands, variant 0) and by the
+                                       kernels (S <= 96, dk and dv multiples of 32, 16-B aligned Q, K, V, dO and row strides that
+                                       are multiples of 4; forward: variant 0 or 2, backward: any variant but 1, and per-wave
+                                       bias tables that fit the LDS budget) and by the
                                        key-tiled kernels (128 < S <= 512: K and Q*scale rounded in the forward, every operand
                                        of the backward products likewise); every other case (S <= 128 outside the staged
                                        kernels) computes the exact-f32 products (the first-generation loops are latency-bound
@@ -218,12 +220,21 @@ typedef struct LstcAttnDesc {
                                        ceil(N/chunks) sequences, written (no atomics; the caller sums them - a
                                        fixed-order, bit-reproducible gradient) */
     int32_t dtable_chunks;
-    int32_t variant;                /* 0 = default kernels; 1 = first-generation kernels (operands straight from global in
-                                       MFMA lane layout) - kept for A/B measurements and as the fallback for shapes the
-                                       staged kernels do not take (d_k or d_v not a multiple of 32, unaligned operands, S > 96);
-                                       forward only: 2 = the second-generation (LDS-logit) kernel where the default is the
-                                       lane-=-query f32 kernel (LSTC_F32, S <= 32 or 64 < S <= 96, d_v a multiple of 64),
-                                       3 = that kernel also for 32 < S <= 64 (A/B measurements; same results to rounding).
+    int32_t variant;                /* S <= 96, row operands, no mask.  0 = default kernels; 1 = first-generation kernels
+                                       (operands straight from global in MFMA lane layout) - kept for A/B measurements and as the
+                                       fallback for what the staged kernels do not take (d_k or d_v not a multiple of 32, a Q, K,
+                                       V or dO base off a 16-B boundary, a row stride that is no multiple of 4, 96 < S <= 128):
+                                       there every value runs them.  Backward: every value but 1 runs the staged kernel where it
+                                       applies and its per-wave bias tables fit the LDS (else the first generation).  Forward,
+                                       d_k and d_v multiples of 32, T = ceil(S / 32):
+                                         LSTC_F32, d_v % 64 == 0 and O 16-B aligned: 0 = the lane-=-query f32 kernel at T = 1 and
+                                           3, the first generation at T = 2; 2 = the staged (LDS-logit) kernel at T = 1 and 3,
+                                           the first generation at T = 2; 3 = the lane-=-query kernel at every T;
+                                         LSTC_F32, any other d_v or an O base off a 16-B boundary (the lane-=-query kernel
+                                           writes O as 16-B groups): 0 and 2 = the staged kernel at T = 1 and 3, the first
+                                           generation at T = 2; 3 = the first generation;
+                                         LSTC_BF16: 0 and 2 = the staged kernel (bf16 products) at every T; 3 = as 1.
+                                       Same results to rounding throughout (A/B measurements).
                                        Packed-input forward only (in_pack_cols > 0): 100 + n = n sequences per workgroup
                                        (1 <= n <= 16; the default picks n from N * H), a measurement hook - results do not
                                        depend on it */

@@ -952,8 +952,9 @@ int attn_fwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
         dim3 grid3((p.N + npw - 1) / npw, p.H);
         return attn3_fwd_launch(p, T, (int)grid3.x, st);
     }
-    if (!mk && !bf && (d->variant == 3 || (d->variant == 0 && T != 2)) && d->O && T <= 3 && p.vec_qk && p.vec_v && p.dk % 32 == 0 && p.dv % 64 == 0) {
-        // third-generation structure on the exact-f32 MFMA (csrc/attention_pk.hip, attn_fwd3f_kernel).  Same box, N = 2048, H = 8,
+    if (!mk && !bf && (d->variant == 3 || (d->variant == 0 && T != 2)) && d->O && aligned16(d->O) && T <= 3 && p.vec_qk && p.vec_v && p.dk % 32 == 0 && p.dv % 64 == 0) {
+        // third-generation structure on the exact-f32 MFMA (csrc/attention_pk.hip, attn_fwd3f_kernel); it alone writes O rows as
+        // 16-B stores, so an O base off a 16-B boundary goes on to the arms below (4-B stores).  Same box, N = 2048, H = 8,
         // d_k = 256 (tools/attn3f_check.py): S = 81 2.85 -> 1.89 ms, S = 96 3.1 -> 2.1, S = 17 0.30 -> 0.27; S = 49 1.13 vs 1.17 and
         // S = 33 0.97 vs 1.1 (the padded 64-key tiles cost MFMA time the first generation skips): 32 < S <= 64 stays where it was
         int npw = (int)(((int64_t)p.N * p.H) / (T == 1 ? 8192 : 1024));

@@ -13,7 +13,7 @@ scaled by 0.4 and attention dropout 0.2; N * H stays small except in the one cas
 import pytest
 import torch
 
-from util import attn_reference, attn_rounded_probs
+from util import attn_layout as _layout, attn_reference, attn_rounded_probs
 
 pytestmark = pytest.mark.gpu
 
@@ -144,25 +144,6 @@ def test_head_width_matrix(S, dk, dv):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. strides, alignment
-
-def _layout(kind, ts):
-    """Views holding the values of the contiguous [M, cols] tensors ``ts`` (Q, K, V, dO) in the layout ``kind``:
-    "odd_ld": Q | K | V column blocks of one buffer whose row length is odd, dO in its own odd-length rows;
-    "offset": every base one float past a 16-B boundary; "strides": four buffers, four different row strides."""
-    M = ts[0].shape[0]
-    cols = [t.shape[1] for t in ts]
-    if kind == "odd_ld":
-        buf = torch.zeros(M, sum(cols[:3]) + 1, device=DEV)
-        c0 = [0, cols[0], cols[0] + cols[1]]
-        views = [buf[:, c: c + n] for c, n in zip(c0, cols[:3])] + [torch.zeros(M, cols[3] + 1, device=DEV)[:, : cols[3]]]
-    elif kind == "offset":
-        views = [torch.zeros(t.numel() + 4, device=DEV)[1: 1 + t.numel()].view(t.shape) for t in ts]
-    else:
-        views = [torch.zeros(M, n + extra, device=DEV)[:, :n] for n, extra in zip(cols, (1, 2, 3, 5))]
-    for dst, src in zip(views, ts):
-        dst.copy_(src)
-    return views
-
 
 @pytest.mark.parametrize("kind", ["odd_ld", "offset", "strides"])
 @pytest.mark.parametrize("d", [64, 80])

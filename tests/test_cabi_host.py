@@ -161,6 +161,27 @@ def test_host_side_validation_error_codes(lib):
     assert b"NULL" in lib.lstc_strerror(-1) and lib.lstc_strerror(0) == b"ok"
 
 
+def test_attention_backward_refuses_a_table_past_the_lds_budget(lib):
+    """S = 81: the first-generation backward holds two 96 x 97 f32 images and four per-wave tables of table_rows floats in LDS
+    (74496 + 16 table_rows bytes).  The staged kernel's larger footprint only sends the call back to the first generation
+    (tests/test_attention_short_gpu.py); a table that pushes the first generation's own past 160 KB is LSTC_E_RANGE before any
+    launch, with partial tables and with atomics, under either variant."""
+    from lstc_vad_amd._lib import AttnDesc
+    a = AttnDesc()
+    a.Q = a.K = a.V = a.probs = a.dO = a.dQ = a.dK = a.dV = a.table = a.index = a.dtable = 4096
+    a.N, a.S, a.H, a.dk, a.dv, a.scale = 1, 81, 1, 64, 64, 0.125
+    a.ldq = a.ldk = a.ldv = a.ldo = 64
+    a.index_ld = 80
+    a.table_rows = (160 * 1024 - 74496) // 16 + 1
+    assert 74496 + 16 * a.table_rows > 160 * 1024 >= 74496 + 16 * (a.table_rows - 1)
+    for chunks in (1, 0):
+        for variant in (0, 1):
+            a.dtable_chunks, a.variant = chunks, variant
+            assert lib.lstc_attn_bwd(C.byref(a), None) == -5, (chunks, variant)
+    a.table_rows = 0
+    assert lib.lstc_attn_bwd(C.byref(a), None) == -2          # a table gradient needs the table's row count
+
+
 def test_model_mirror_keeps_reference_surface():
     from lstc_vad_amd.models import Encoder, Classifier, Regressor
     z = np.load(os.path.join(ROOT, "tests", "golden", "misc.npz"), allow_pickle=False)

@@ -2681,8 +2681,9 @@ def test_packed_input_attention_sequence_length_sweep(S):
 def test_f32_lane_query_attention_forward_matches_the_first_generation(S, dk, H):
     """fp32 mode: attn_fwd3f_kernel (lane = query, exact-f32 MFMA, producer-wave ring; the default for S <= 32 and 64 < S <= 96,
     LstcAttnDesc.variant = 3 elsewhere) against the first-generation kernel (variant 1): probabilities and O to f32 summation
-    order, with relative bias (read through the top-left of a larger index), dropout, partial last workgroup chunk (N = 300 is
-    not a multiple of the sequences per workgroup)."""
+    order, with relative bias (read through the top-left of a larger index), dropout.  N = 300 gives N H / 1024 = 1 sequence
+    per workgroup at H = 2 and 4 and 2 (150 whole chunks) at H = 8: no workgroup here has a partial last chunk - those are in
+    tests/test_attention_short_gpu.py (test_lane_query_forward_with_several_sequences_per_workgroup)."""
     from lstc_vad_amd import functional as Fn
     N = 300
     M = N * S

@@ -105,6 +105,31 @@ def attn_rounded_probs(q, k, N, S, H, dk, table, index):
     return torch.softmax(a, -1)
 
 
+def attn_layout(kind, ts):
+    """Views holding the values of the contiguous [M, cols] tensors ``ts`` (Q, K, V, dO) in the layout ``kind``:
+    "odd_ld": Q | K | V column blocks of one buffer whose row length is odd, dO in its own odd-length rows;
+    "offset": every base one float past a 16-B boundary; "strides": four buffers, four different row strides;
+    "fused": Q | K | V column blocks of one [M, cols(Q) + cols(K) + cols(V)] matrix (the fused projection's output: every
+    base 16-B aligned when the widths are multiples of 4, row stride the sum of the three), dO contiguous."""
+    dev = ts[0].device
+    M = ts[0].shape[0]
+    cols = [t.shape[1] for t in ts]
+    if kind in ("odd_ld", "fused"):
+        pad = 1 if kind == "odd_ld" else 0
+        buf = torch.zeros(M, sum(cols[:3]) + pad, device=dev)
+        c0 = [0, cols[0], cols[0] + cols[1]]
+        views = [buf[:, c: c + n] for c, n in zip(c0, cols[:3])] + [torch.zeros(M, cols[3] + pad, device=dev)[:, : cols[3]]]
+    elif kind == "offset":
+        views = [torch.zeros(t.numel() + 4, device=dev)[1: 1 + t.numel()].view(t.shape) for t in ts]
+    elif kind == "strides":
+        views = [torch.zeros(M, n + extra, device=dev)[:, :n] for n, extra in zip(cols, (1, 2, 3, 5))]
+    else:
+        raise ValueError(kind)
+    for dst, src in zip(views, ts):
+        dst.copy_(src)
+    return views
+
+
 _BATCH_CACHE = {}
 
 
