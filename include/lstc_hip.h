@@ -434,7 +434,12 @@ int lstc_cls_outer_pack(const float* W1, const float* U1, const float* W2, const
  * models/Encoder.py:31,48-49.  Saves mean / rstd per row for the backward. */
 int lstc_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
                        float* mean, float* rstd, int64_t rows, int32_t d, float eps, void* stream);
-/* dx, and per-workgroup partial dgamma/dbeta in `partial` [2, n_partial, d] (reduce with lstc_colsum). */
+/* dx, and per-workgroup partial dgamma/dbeta in `partial` [2, n_partial, d] (reduce with lstc_colsum).
+ * d % 4 == 0, d <= 2048 and 16-B aligned dy, x, gamma, dx, partial: the register-resident kernel of csrc/rowops.hip (ln_bwd_pair,
+ * two waves per row; workgroup w takes rows 2w and 2w + 1, then every 2 n_partial further) - the one kernel text behind
+ * lstc_layernorm_bwd_drop and lstc_layernorm_bwd_drop_pack too, so the three give the same dx bit for bit, and at the same
+ * n_partial the same dgamma / dbeta planes.  Any other d or alignment: a scalar kernel (2 d floats of LDS: LSTC_E_RANGE beyond
+ * 64 KiB). */
 int lstc_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                        float* dx, float* partial, int32_t n_partial, int64_t rows, int32_t d, void* stream);
 /* bf16 mode: the same two kernels also emit the packed bf16 operand (lstc_pack1 layout, [rows, d]) of the GEMMs that read
@@ -447,12 +452,14 @@ int lstc_layernorm_bwd(const float* dy, const float* x, const float* gamma, cons
  *                                 weight gradient and the input gradient of the Linear in front of the dropout
  *                                 (fc: MultiHeadAttention.py:123, w_2: FFN.py:17-18); `partial` is [3, n_partial, d], the
  *                                 third plane = column sums of df (that Linear's bias gradient).  dx stays f32 (residual).
+ *                                 At every accepted width the kernel is lstc_layernorm_bwd's, with the replay compiled in.
  * Both need rows % 256 == 0, d % 64 == 0, d <= 2048 (the rows fill the pack's even tile grid exactly; LSTC_E_UNSUPPORTED
  * otherwise - the caller then packs with lstc_pack1) and `packed` of lstc_pack1_bytes(rows, d) bytes. */
 int lstc_layernorm_fwd_pack(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                             int64_t rows, int32_t d, float eps, void* packed, void* stream);
 /* The same fusion with an f32 result (fp32 / f32x3 modes): df = lstc_dropout_apply(dx, p, seed) written next to dx, `partial`
- * [3, n_partial, d] with the column sums of df as third plane.  d = 512, 1024 or 2048 (LSTC_E_UNSUPPORTED otherwise). */
+ * [3, n_partial, d] with the column sums of df as third plane.  d = 512, 1024 or 2048, the widths of the models and of its only
+ * callers (LSTC_E_UNSUPPORTED otherwise, although the kernel behind it serves every d % 4 == 0 up to 2048). */
 int lstc_layernorm_bwd_drop(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                             float* dx, float* df, float* partial, int32_t n_partial, int64_t rows, int32_t d, float dropout_p,
                             uint64_t dropout_seed, void* stream);
@@ -471,6 +478,7 @@ int lstc_layernorm_bwd_drop_pack(const float* dy, const float* x, const float* g
  *   lstc_layernorm_bwd_act: x_pack = the forward's input pack; the incoming gradient is dy (f32) or dy_pack; dx_pack (may be
  *                           NULL: nobody reads layer 0's) = gradient of the residual sum, df_pack = dropout-replay(dx) exactly
  *                           as lstc_layernorm_bwd_drop_pack, partial [3, n_partial, d] = dgamma, dbeta, column sums of df.
+ *                           A kernel of its own (ln_bwd_act): it sums a row in another order than the f32-row kernel.
  * rows % 256 == 0 and d = 1024 or 2048 (LSTC_E_UNSUPPORTED otherwise); every pack lstc_pack1_bytes(rows, d) bytes, 16-B aligned. */
 int lstc_layernorm_fwd_act(const float* x, const void* x_pack, const float* gamma, const float* beta, float* y, void* y_pack,
                            float* mean, float* rstd, int64_t rows, int32_t d, float eps, void* stream);

@@ -934,17 +934,25 @@ def layernorm_fwd(x2: torch.Tensor, gamma, beta, eps=1e-6, pack=False):
     return y, mean, rstd
 
 
+def _ln_bwd_rows(name, dz2, y, gamma, mean, rstd, outs, drop=(), n_sums=2):
+    """One f32-row LayerNorm backward (csrc/rowops.hip, ln_bwd_pair): ``name(dz2, y, gamma, mean, rstd, *outs, partial, n_partial,
+    rows, d, *drop, stream)``, then the column sums of the first ``n_sums`` partial planes (dgamma, dbeta(, dbias): one batched
+    two-pass sum).  ``drop``: the dropout-replay arguments of the fused entry points, which write a third plane.  One partial row
+    per workgroup: at d = 2048 the kernel's registers allow 4 workgroups per CU without the replay (1024 = 4 x 256 CUs) and 3 with
+    it (768); the narrower instantiations would hold more and keep these caps, so the summation order follows one rule."""
+    rows, d = y.shape
+    dz2 = dz2.contiguous()
+    planes, cap = (3, 768) if drop else (2, 1024)
+    n_partial = int(min(max(rows // 4, 1), cap))
+    partial = torch.empty((planes, n_partial, d), device=y.device, dtype=torch.float32)
+    check(getattr(_lib.load(), name)(dev_ptr(dz2), dev_ptr(y), dev_ptr(gamma), dev_ptr(mean), dev_ptr(rstd),
+                                     *(dev_ptr(t) for t in outs), dev_ptr(partial), n_partial, rows, d, *drop, stream_ptr()), name)
+    return colsum_planes(partial, n_sums)
+
+
 def layernorm_bwd(dy2, x2, gamma, mean, rstd):
-    rows, d = x2.shape
-    dy2 = dy2.contiguous()
     dx = torch.empty_like(x2)
-    # one partial row per workgroup: 4 resident workgroups per CU at the model widths (two waves per row, csrc/rowops.hip), 2 else
-    n_partial = int(min(max(rows // 4, 1), 1024 if d in (512, 1024, 2048) else 512))
-    partial = torch.empty((2, n_partial, d), device=x2.device, dtype=torch.float32)
-    check(_lib.load().lstc_layernorm_bwd(dev_ptr(dy2), dev_ptr(x2), dev_ptr(gamma), dev_ptr(mean), dev_ptr(rstd),
-                                         dev_ptr(dx), dev_ptr(partial), n_partial, rows, d, stream_ptr()),
-          "lstc_layernorm_bwd")
-    sums = colsum_planes(partial)
+    sums = _ln_bwd_rows("lstc_layernorm_bwd", dy2, x2, gamma, mean, rstd, (dx,))
     return dx, sums[0], sums[1]
 
 
@@ -957,29 +965,17 @@ def layernorm_bwd_branch(dz2, y, gamma, mean, rstd, p: float, seed: int, layer_n
     lstc_dropout_apply (+ lstc_colsum)."""
     rows, d = dz2.shape
     if layer_norm and _fused_pack_shape(rows, d) and rows * d <= 0xffffffff:
-        lib = _lib.load()
-        dz2 = dz2.contiguous()
         dy = torch.empty_like(y)
-        n_partial = int(min(max(rows // 4, 1), 768))        # 3 workgroups per CU resident (csrc/rowops.hip, ln_bwd_pack2)
-        partial = torch.empty((3, n_partial, d), device=y.device, dtype=torch.float32)
-        buf = torch.empty((int(lib.lstc_pack1_bytes(rows, d)),), device=y.device, dtype=torch.uint8)
-        check(lib.lstc_layernorm_bwd_drop_pack(dev_ptr(dz2), dev_ptr(y), dev_ptr(gamma), dev_ptr(mean), dev_ptr(rstd),
-                                               dev_ptr(dy), dev_ptr(partial), n_partial, rows, d, float(p), int(seed),
-                                               dev_ptr(buf), stream_ptr()), "lstc_layernorm_bwd_drop_pack")
-        sums = colsum_planes(partial, 3 if want_bias else 2)        # dgamma, dbeta(, dbias): one batched two-pass sum
+        buf = torch.empty((int(_lib.load().lstc_pack1_bytes(rows, d)),), device=y.device, dtype=torch.uint8)
+        sums = _ln_bwd_rows("lstc_layernorm_bwd_drop_pack", dz2, y, gamma, mean, rstd, (dy,), (float(p), int(seed), dev_ptr(buf)),
+                            3 if want_bias else 2)
         return dy, Packed(buf, rows, d, _lib.BF16P), sums[0], sums[1], (sums[2] if want_bias else None)
     if layer_norm and p > 0 and _FUSE_PACKS and d in (512, 1024, 2048) and rows * d <= 0xffffffff:
         # f32 modes: the same kernel writes the dropped gradient as a second f32 result (no lstc_dropout_apply pass, and the
         # bias gradient's column sums come out of the same pass)
-        lib = _lib.load()
-        dz2 = dz2.contiguous()
         dy, df = torch.empty_like(y), torch.empty_like(y)
-        n_partial = int(min(max(rows // 4, 1), 768))
-        partial = torch.empty((3, n_partial, d), device=y.device, dtype=torch.float32)
-        check(lib.lstc_layernorm_bwd_drop(dev_ptr(dz2), dev_ptr(y), dev_ptr(gamma), dev_ptr(mean), dev_ptr(rstd), dev_ptr(dy),
-                                          dev_ptr(df), dev_ptr(partial), n_partial, rows, d, float(p), int(seed), stream_ptr()),
-              "lstc_layernorm_bwd_drop")
-        sums = colsum_planes(partial, 3 if want_bias else 2)
+        sums = _ln_bwd_rows("lstc_layernorm_bwd_drop", dz2, y, gamma, mean, rstd, (dy, df), (float(p), int(seed)),
+                            3 if want_bias else 2)
         return dy, df, sums[0], sums[1], (sums[2] if want_bias else None)
     dgamma = dbeta = None
     if layer_norm:

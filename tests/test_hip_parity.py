@@ -2207,7 +2207,8 @@ def test_bf16_gradient_allreduce_wire_format_single_rank():
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("rows,d,p", [(256, 64, 0.0), (512, 2048, 0.2), (768, 1024, 0.1), (1280, 320, 0.3)])
+@pytest.mark.parametrize("rows,d,p", [(256, 64, 0.0), (512, 2048, 0.2), (768, 1024, 0.1), (1280, 320, 0.3), (256, 576, 0.2),
+                                      (256, 1088, 0.1)])
 def test_layernorm_kernels_emit_the_packs_the_separate_passes_would(rows, d, p):
     """lstc_layernorm_fwd_pack / lstc_layernorm_bwd_drop_pack against lstc_layernorm_fwd / _bwd + lstc_dropout_apply +
     lstc_pack1: f32 results and the packed bf16 bytes are IDENTICAL (same registers, same rounding); the third partial plane
