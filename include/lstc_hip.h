@@ -736,6 +736,35 @@ int lstc_segment_mean(const float* bank, int64_t bank_clips, const int64_t* firs
 int lstc_expand_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
                      const int32_t* map, int64_t rows, int32_t cols, void* stream);
 
+/* --------------------------------------------------------------------------- metrics
+ * Frame-level ROC-AUC of a pass without its host tail (replaces utils/eval_utils.py:21-24,139-143 - sklearn roc_curve + auc over
+ * the frame scores - for passes whose frame scores only repeat row scores).  Row i has score scores[i] and covers pos[i] frames
+ * labelled 1 and neg[i] frames labelled 0; the tie-aware trapezoid AUC of the expanded frames is the weighted pair count
+ *     u2 = sum_i sum_j pos[i] neg[j] (2 [scores[i] > scores[j]] + [scores[i] == scores[j]]),   auc = u2 / (2 P N),
+ * P = sum pos, N = sum neg.  The floats are compared with > and ==: +0.0 and -0.0 tie, denormals order as on the host.
+ *   - a row with pos == neg == 0 does not exist: its score is never looked at, NaN included;
+ *   - u2, pos (= P) and neg (= N) are exact integers, whatever the launch shape (integer partials, no atomics);
+ *   - auc = (double)u2 / (2.0 * P * N), one IEEE division; NaN when P == 0 or N == 0;
+ *   - flags & LSTC_AUC_NAN_SCORE: a row with non-zero weight has a NaN score; auc is NaN;
+ *   - flags & LSTC_AUC_TOO_MANY_FRAMES: P + N > 2^26 (the bound keeps the per-thread 32-bit counts and 2 P N < 2^53 safe); auc
+ *     is NaN and u2 is not meaningful.
+ * All buffers are device memory owned by the caller; `workspace` holds at least lstc_auc_workspace_bytes(n) bytes at any
+ * alignment (its content before and after the call is unspecified), `out` is 8-byte aligned (else LSTC_E_ALIGN).  Two launches on
+ * `stream`, no allocation, no synchronisation: the call can be captured in a graph.  Checked before any launch: a NULL pointer
+ * LSTC_E_NULL; n <= 0 LSTC_E_SHAPE; n > 2^24 LSTC_E_RANGE; workspace_bytes too small LSTC_E_SHAPE.
+ * lstc_auc_workspace_bytes is positive and monotone in n (n is clamped into 1..2^24). */
+typedef struct {
+    uint64_t u2, pos, neg;
+    double auc;
+    uint32_t flags;
+    uint32_t reserved;
+} LstcAucOut;                           /* 40 bytes */
+#define LSTC_AUC_NAN_SCORE 1u
+#define LSTC_AUC_TOO_MANY_FRAMES 2u
+int64_t lstc_auc_workspace_bytes(int64_t n);
+int lstc_auc_weighted(const float* scores, const uint32_t* pos, const uint32_t* neg, int64_t n, void* workspace,
+                      int64_t workspace_bytes, LstcAucOut* out, void* stream);
+
 /* ------------------------------------------------------------------------------ misc */
 int lstc_version(void);
 const char* lstc_strerror(int code);

@@ -135,6 +135,11 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                         "(pipeline.ResidentSet), the train-AUC pass reads the training bank already there, and every pass describes "
                         "its sequences as spans of the bank instead of re-reading and re-uploading every video.  A set beyond 60 %% "
                         "of the free HBM stays host-fed")
+    p.add_argument("--device_auc", action="store_true",
+                   help="frame-level AUC of the evaluation passes on the device: the per-row frame counts of the test and the train "
+                        "list are built once (pipeline.AucWeights), every evaluation is then one exact weighted pair count over the "
+                        "flat score vector (lstc_auc_weighted) and only its 40-byte record comes to the host.  With or without "
+                        "--resident_eval")
     return p
 
 
@@ -580,17 +585,23 @@ def _real_data(script, args, mode, part_len, pseudo_path, dev, rank, world, enc,
                 data.bank.shape[1] == args.n_patch and os.path.abspath(train_arc) == os.path.abspath(args.dataset_path):
             from .pipeline import ResidentSet
             train_set = ResidentSet.from_pairs(data)
+    # --device_auc: one AucWeights per pass, filled by the first evaluation and reused by every later one
+    test_w = train_w = None
+    if getattr(args, "device_auc", False):
+        from .pipeline import AucWeights
+        test_w, train_w = AucWeights(), AucWeights()
 
     def eval_fn():
         """(test AUC, train AUC) as the script's in-loop evaluation computes them (0 where it does not)."""
         auc_test = auc_train = 0.0
         if getattr(args, "testing_txt", ""):
             auc_test = evaluate_auc(enc.eval(), head.eval(), kind, dataset, test_arc, args.testing_txt, masks, part_len,
-                                    args.n_patch, args.segment_len, rank=rank, world=world, resident=test_set)
+                                    args.n_patch, args.segment_len, rank=rank, world=world, resident=test_set,
+                                    device_auc=test_w)
         if train_arc and dataset != "UCF":
             auc_train = evaluate_train_auc(enc.eval(), head.eval(), kind, dataset, train_arc, args.training_txt,
                                            getattr(args, "test_mask_dir", ""), part_len, args.n_patch, args.segment_len,
-                                           rank=rank, world=world, resident=train_set)
+                                           rank=rank, world=world, resident=train_set, device_auc=train_w)
         return auc_test, auc_train
     return data, eval_fn
 
@@ -751,11 +762,19 @@ def evaluate_cli(script: str, argv=None, args=None):
         test_set = _resident_set(args, dev, args.dataset_path, _list_keys("UCF" if ucf else args.dataset, args.testing_txt),
                                  args.n_patch, ucf)
         torch.cuda.synchronize(); t0 = _time.perf_counter()
-        auc, fs, _ = evaluate_auc(enc, head, "LTN", "UCF" if ucf else args.dataset, args.dataset_path, args.testing_txt, masks,
-                                  part_len, args.n_patch, seg, return_frames=True, resident=test_set)
+        if getattr(args, "device_auc", False):
+            from .pipeline import AucWeights
+            weights = AucWeights()
+            auc = evaluate_auc(enc, head, "LTN", "UCF" if ucf else args.dataset, args.dataset_path, args.testing_txt, masks,
+                               part_len, args.n_patch, seg, resident=test_set, device_auc=weights)
+            n_frames = weights.frames
+        else:
+            auc, fs, _ = evaluate_auc(enc, head, "LTN", "UCF" if ucf else args.dataset, args.dataset_path, args.testing_txt, masks,
+                                      part_len, args.n_patch, seg, return_frames=True, resident=test_set)
+            n_frames = int(fs.shape[0])
         torch.cuda.synchronize()
         LAST_RUN.clear()
-        LAST_RUN.update(script=script, clips=int(fs.shape[0]) // seg, score_s=_time.perf_counter() - t0, world=1)
+        LAST_RUN.update(script=script, clips=n_frames // seg, score_s=_time.perf_counter() - t0, world=1)
         print("auc = ", auc)
         return auc
     data = SyntheticVideos(2, 1, 1, part_len, args.n_patch, args.d_model, dev, seed=0)

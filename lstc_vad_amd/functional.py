@@ -2646,6 +2646,45 @@ def segment_mean(bank: torch.Tensor, first, count, l2: bool = False, out: Option
     return out
 
 
+_auc_workspaces = {}        # (device index, rows) -> uint8 workspace of lstc_auc_weighted
+
+
+def weighted_auc(scores: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frame-level ROC-AUC from row scores and per-row frame counts (``lstc_auc_weighted``; ``metrics.roc_auc_weighted`` is the
+    host statement of the same contract): ``scores`` float32 [n], ``pos`` / ``neg`` int32 or uint32 [n] (frames labelled 1 / 0 that
+    row covers), all contiguous on one HIP device.  Returns the 40-byte ``LstcAucOut`` record as an int64 [5] device tensor (``out``
+    when given) without synchronising; ``read_auc`` copies it to the host.  The workspace is cached per device and n."""
+    if scores.dim() != 1 or scores.dtype != torch.float32 or scores.numel() == 0:
+        raise TypeError(f"weighted_auc: scores must be float32 [n], n >= 1, got {tuple(scores.shape)} {scores.dtype}")
+    counts = (torch.int32, torch.uint32)
+    if pos.dtype not in counts or neg.dtype not in counts or pos.shape != scores.shape or neg.shape != scores.shape:
+        raise TypeError("weighted_auc: pos and neg must be int32 or uint32 [n], one count per score")
+    if not (scores.is_contiguous() and pos.is_contiguous() and neg.is_contiguous()):
+        raise TypeError("weighted_auc: scores, pos and neg must be contiguous")
+    if not (scores.is_cuda and pos.is_cuda and neg.is_cuda):
+        raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+    if pos.device != scores.device or neg.device != scores.device:
+        raise ValueError("weighted_auc: scores, pos and neg lie on different devices")
+    n = scores.numel()
+    lib = _lib.load()
+    key = (scores.device.index, n)
+    ws = _auc_workspaces.get(key)
+    if ws is None:
+        ws = _auc_workspaces[key] = torch.empty((int(lib.lstc_auc_workspace_bytes(n)),), dtype=torch.uint8, device=scores.device)
+    if out is None:
+        out = torch.empty((5,), dtype=torch.int64, device=scores.device)
+    elif out.dtype != torch.int64 or out.numel() != 5 or not out.is_contiguous() or out.device != scores.device:
+        raise TypeError("weighted_auc: out must be a contiguous int64 [5] tensor on the scores' device")
+    check(lib.lstc_auc_weighted(dev_ptr(scores), dev_ptr(pos), dev_ptr(neg), n, dev_ptr(ws), ws.numel(), dev_ptr(out), stream_ptr()),
+          "lstc_auc_weighted")
+    return out
+
+
+def read_auc(record: torch.Tensor):
+    """The record ``weighted_auc`` returned, on the host (one 40-byte copy, which waits for the launch) -> ``_lib.AucOut``."""
+    return _lib.AucOut.from_buffer_copy(record.cpu().numpy().tobytes())
+
+
 def lengths_arg(lengths, N, S, device):
     """Normalise the ``lengths`` of a padded batch of N sequences with S - 1 token slots: a Python sequence or a CPU tensor is
     range-checked here (ValueError; 1 <= L <= S - 1) and copied to ``device``; a device tensor is taken as it is, without a host

@@ -27,6 +27,11 @@ GPUs idle.
 part of every video as a SPAN of bank rows (``scoring.part_spans``, ``ucf_bin_table`` / ``ucf_bin_spans``) and the pool is scored
 from the bank (``scoring.resident_sequence_scores``) - no archive read, no upload and no sequence cut out per pass; the UCF bins of
 a pool come from one ``lstc_segment_mean`` launch.  Lists, masks, ``finish`` closures, thresholds, AUC and sharding are the same code.
+
+**AUC on the device.**  ``device_auc=`` on the two AUC passes: every frame's score is one flat row's score, so the frame-level AUC is
+a weighted pair count over the rows (``metrics.roc_auc_weighted``).  ``AucWeights`` turns the ``finish`` closures of a pass into the
+per-row counts of label-1 / label-0 frames once; an evaluation is then ``lstc_auc_weighted`` on the flat device vector and 40 bytes
+come back instead of the scores.
 """
 from __future__ import annotations
 
@@ -190,20 +195,22 @@ class _ScoreBoard:
         self.rank, self.world, self.group, self.exchange = rank, world, group, exchange
         self.pool_sequences = pool_sequences
         self.items, self.total = [], 0             # (offset, count, finish) in list order
+        self.names = []                            # the videos of ``items`` (error messages of AucWeights)
         self.pool, self.pooled = [], 0             # own LTN work waiting for a launch: (offset, sequences)
         self.parts = []                            # (offset, device tensor) scored segments of this rank
 
     def owns(self, i):
         return i % self.world == self.rank
 
-    def _register(self, count, finish):
+    def _register(self, count, finish, name=None):
         off = self.total
         self.items.append((off, int(count), finish))
+        self.names.append(name if name is not None else f"#{len(self.names)}")
         self.total += int(count)
         return off
 
-    def add_ltn(self, i, count, make_sequences, finish):
-        off = self._register(count, finish)
+    def add_ltn(self, i, count, make_sequences, finish, name=None):
+        off = self._register(count, finish, name)
         if self.owns(i):
             seqs = make_sequences()
             if len(seqs) != count:
@@ -213,9 +220,9 @@ class _ScoreBoard:
             if self.pooled >= self.pool_sequences:
                 self.flush()
 
-    def add_spans(self, i, count, make_spans, finish):
+    def add_spans(self, i, count, make_spans, finish, name=None):
         """A video of a resident set: ``make_spans() -> [(first_row, n_tokens)]`` of the bank, one per score."""
-        off = self._register(count, finish)
+        off = self._register(count, finish, name)
         if self.owns(i):
             spans = make_spans()
             if len(spans) != count:
@@ -225,9 +232,9 @@ class _ScoreBoard:
             if self.pooled >= self.pool_sequences:
                 self.flush()
 
-    def add_bins(self, i, count, make_table, finish):
+    def add_bins(self, i, count, make_table, finish, name=None):
         """A UCF video of a resident set: ``make_table() -> (first [32], count [32])``, its bins as runs of bank clips."""
-        off = self._register(count, finish)
+        off = self._register(count, finish, name)
         if self.owns(i):
             self.pool.append((off, make_table()))
             self.pooled += count
@@ -255,8 +262,8 @@ class _ScoreBoard:
             o += len(spans)
         self.pool, self.pooled = [], 0
 
-    def add_clips(self, i, count, score, finish):
-        off = self._register(count, finish)
+    def add_clips(self, i, count, score, finish, name=None):
+        off = self._register(count, finish, name)
         if self.owns(i):
             sc = score().reshape(-1).float()
             if sc.numel() != count:
@@ -276,7 +283,8 @@ class _ScoreBoard:
             o += len(seqs)
         self.pool, self.pooled = [], 0
 
-    def results(self):
+    def flat_scores(self):
+        """The complete flat score vector of the pass on the device: own scores, then the sum over the ranks."""
         self.flush()
         flat = torch.zeros((self.total,), device=self.device, dtype=torch.float32)
         for off, sc in self.parts:
@@ -288,7 +296,10 @@ class _ScoreBoard:
                 import torch.distributed as dist
                 from .dist import all_reduce_sum
                 all_reduce_sum(flat, self.group)
-        host = flat.cpu().numpy()
+        return flat
+
+    def results(self):
+        host = self.flat_scores().cpu().numpy()
         return [finish(host[off:off + n]) for off, n, finish in self.items]
 
 
@@ -379,6 +390,90 @@ def _generate_resident(enc, head, mode, dataset, training_txt, threshold, part_l
     return out
 
 
+class AucWeights:
+    """The per-row frame counts of ONE pass - one (list, masks, mode, part_len, segment_len): ``pos[i]`` / ``neg[i]`` frames labelled
+    1 / 0 repeat the score of flat row i (int32 device tensors once filled; ``pos_host`` / ``neg_host`` the same counts as int64
+    numpy arrays), ``total`` rows, ``frames`` frames.  Created empty, filled by the first ``evaluate_auc`` / ``evaluate_train_auc``
+    call that gets it as ``device_auc=`` and reused by the later ones: the labels of a list do not change between evaluations.
+
+    ``fill`` derives the counts from the ``finish`` closures the pass registered, so the tail rules (re-windowed tail, negative
+    slice, UCF bin edges, ``anno[:n]``) exist once: every closure runs on its own flat row numbers instead of scores, what comes back
+    as frame "scores" are the frames' row ids (exact through float32 below 2^24 - hence the row limit) beside their labels."""
+    MAX_ROWS, MAX_FRAMES = 1 << 24, 1 << 26          # the limits of lstc_auc_weighted (include/lstc_hip.h)
+
+    def __init__(self):
+        self.pos = self.neg = self.pos_host = self.neg_host = None
+        self.total, self.frames = None, 0
+
+    @property
+    def filled(self):
+        return self.total is not None
+
+    def fill(self, board):
+        """From the registered videos of ``board`` (a ``_ScoreBoard`` after its list walk), onto the board's device.  Every refusal
+        is a ValueError raised before anything is launched."""
+        total = int(board.total)
+        if total > self.MAX_ROWS:
+            raise ValueError(f"AucWeights: {total} score rows, lstc_auc_weighted takes at most 2^24")
+        if total <= 0:
+            raise ValueError("AucWeights: the pass registered no scores")
+        ids, labels, frames = [], [], 0
+        for (off, n, finish), name in zip(board.items, board.names):
+            s, l = finish(np.arange(off, off + n, dtype=np.float32))
+            s, l = np.asarray(s), np.asarray(l)
+            if s.size != l.size:
+                raise ValueError(f"AucWeights: video {name!r} has {s.size} frame scores and {l.size} frame labels")
+            frames += s.size
+            if frames > self.MAX_FRAMES:
+                raise ValueError(f"AucWeights: more than 2^26 frames (at video {name!r})")
+            if not np.all((l == 0) | (l == 1)):
+                raise ValueError(f"AucWeights: video {name!r} has a frame label other than 0 / 1")
+            ids.append(s.ravel().astype(np.int64))
+            labels.append(l.ravel().astype(np.float64))
+        ids, labels = np.concatenate(ids), np.concatenate(labels)
+        if ids.size and (ids.min() < 0 or ids.max() >= total):
+            raise ValueError("AucWeights: a finish closure returned something other than its own scores")
+        pos = np.bincount(ids, weights=labels, minlength=total).astype(np.int64)
+        neg = np.bincount(ids, minlength=total).astype(np.int64) - pos
+        self.pos_host, self.neg_host = pos, neg
+        self.pos = torch.from_numpy(pos.astype(np.int32)).to(board.device)
+        self.neg = torch.from_numpy(neg.astype(np.int32)).to(board.device)
+        self.total, self.frames = total, int(frames)
+        return self
+
+    def auc(self, flat):
+        """AUC of the flat device score vector of the pass: two launches, then the pass's only device-to-host copy (40 bytes)."""
+        from . import functional as Fn
+        if flat.numel() != self.total:
+            raise ValueError(f"AucWeights: built for {self.total} score rows, got {flat.numel()}")
+        return float(Fn.read_auc(Fn.weighted_auc(flat.contiguous(), self.pos, self.neg)).auc)
+
+
+def _device_auc_arg(device_auc, return_frames, what):
+    """None (the host AUC), or the AucWeights of the pass: a fresh one for ``True``."""
+    if device_auc is None or device_auc is False:
+        return None
+    if return_frames:
+        raise ValueError(f"{what}: device_auc returns the AUC alone; return_frames=True stays on the host route")
+    if device_auc is True:
+        return AucWeights()
+    if not isinstance(device_auc, AucWeights):
+        raise TypeError(f"{what}: device_auc takes True or a pipeline.AucWeights, got {type(device_auc).__name__}")
+    return device_auc
+
+
+def _finish_pass(board, weights, return_frames, what):
+    """The AUC of a walked list: on the host from every video's frames, or (``weights``) on the device from the flat vector."""
+    if weights is None:
+        return _auc_of(board.results(), return_frames)
+    if not weights.filled:
+        weights.fill(board)
+    elif weights.total != board.total:
+        raise ValueError(f"{what}: the AucWeights hold {weights.total} score rows, this pass has {board.total} - one AucWeights per "
+                         "(list, masks, mode, part_len, segment_len)")
+    return weights.auc(board.flat_scores())
+
+
 def _auc_of(rows, return_frames):
     s, l = np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows])
     auc = roc_auc(s, l)
@@ -388,15 +483,21 @@ def _auc_of(rows, return_frames):
 @torch.no_grad()
 def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, part_len, n_patch, segment_len=16,
                  return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, ragged=False,
-                 resident=None):
+                 resident=None, device_auc=None):
     """``masks``: directory of ``<video>.npy`` frame masks (SHT / UBnormal, ``--test_mask_dir``) or the ground-truth
     archive (UCF, ``--test_mask_path``).  LTN only scores parts; STN scores clips (in-loop evaluation of the spatio
     scripts, Train/spatio_transformer_shanghaitech.py:118-150: every clip's score x segment_len).  ``ragged``: pooled LTN
     parts of all lengths share padded batches (scoring.ltn_sequence_scores); ``"unpadded"``: batches without padding.
     ``resident``: a ``ResidentSet`` of the list's videos, cut to ``n_patch`` (UCF: ``view=True``) - ``dataset_path`` is not opened,
-    nothing is uploaded, STN clips are pooled like LTN parts and the UCF bins of a pool are one ``lstc_segment_mean`` launch."""
+    nothing is uploaded, STN clips are pooled like LTN parts and the UCF bins of a pool are one ``lstc_segment_mean`` launch.
+    ``device_auc``: ``True`` or an ``AucWeights`` (filled by the first call, reused by the later ones; ValueError when it was built
+    for another row count) - the AUC is computed on the device from the flat score vector (``lstc_auc_weighted``) and the float read
+    from its record is returned: no score comes to the host.  With ``resident`` and filled weights no mask file and no ground-truth
+    archive is opened either.  Not with ``return_frames`` (ValueError)."""
+    weights = _device_auc_arg(device_auc, return_frames, "evaluate_auc")
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
+    labels_known = weights is not None and weights.filled      # the finish closures will not run: their labels are not read
     board = _ScoreBoard(enc, head, device, rank, world, group, pool_sequences, exchange, ragged, resident,
                         classifier_head=(mode == "LTN"),
                         ucf=dict(part_len=part_len, rewindow=True, l2=True) if (dataset == "UCF" and mode == "LTN") else None)
@@ -411,12 +512,15 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
 
     if dataset == "UCF":
         for i, line in enumerate(open(testing_txt, "r").readlines()):
+            name = _ucf_line(line)[0]
             if rs is None and board.owns(i):
                 feats, anno, n_frames, _ = UCF_test(line, dataset_path, masks, segment_len, return_name=True)
             else:                                    # not ours: the list line and the ground truth say everything but the scores
                 key, n_frames, fields = _ucf_line(line)
                 feats = None
-                if fields[2] == "Normal":
+                if labels_known and rs is not None:
+                    anno = None
+                elif fields[2] == "Normal":
                     anno = np.zeros(n_frames)
                 else:
                     with FeatureArchive(masks) as gt:
@@ -425,13 +529,13 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
                 n = rs.n_clips(key)
                 if mode != "LTN":
                     board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0],
-                                    stn_finish(anno))
+                                    stn_finish(anno), name)
                     continue
                 ranges = scoring.ucf_bin_ranges(part_len, rewindow=True)
                 r = scoring.ucf_bin_edges(n_frames, segment_len)
                 board.add_bins(i, len(ranges), lambda key=key, n=n, n_frames=n_frames: scoring.ucf_bin_table(
                     n_frames, segment_len, first_clip=rs.first_clip(key), n_clips=n),
-                    lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len))
+                    lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len), name)
                 continue
             if mode != "LTN":
                 if feats is None:
@@ -444,7 +548,7 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
                 def score(feats=feats):
                     f = _dev(feats, device)
                     return scoring.stn_clip_scores(enc, head, f.view(-1, n_patch, f.shape[-1]))
-                board.add_clips(i, n_clips, score, stn_finish(anno))
+                board.add_clips(i, n_clips, score, stn_finish(anno), name)
                 continue
             ranges = scoring.ucf_bin_ranges(part_len, rewindow=True)
             r = scoring.ucf_bin_edges(n_frames, segment_len)
@@ -454,43 +558,53 @@ def evaluate_auc(enc, head, mode, dataset, dataset_path, testing_txt, masks, par
                 return scoring.ltn_ucf_bin_sequences(f.view(-1, n_patch, f.shape[-1]), n_frames, part_len, segment_len,
                                                      normalize=True, rewindow=True)[0]
             board.add_ltn(i, len(ranges), make,
-                          lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len))
+                          lambda v, ranges=ranges, r=r, anno=anno: scoring.frame_scores_ucf(v, ranges, r, anno, segment_len), name)
     elif rs is not None:
-        keys, annos = test_list("sht" if dataset in ("SHT", "MT_SHT") else "ubnormal", testing_txt, masks)
+        if labels_known:
+            keys = [line.strip().split(",")[0] for line in open(testing_txt, "r").readlines()]
+            annos = [None] * len(keys)
+        else:
+            keys, annos = test_list("sht" if dataset in ("SHT", "MT_SHT") else "ubnormal", testing_txt, masks)
         for i, (key, anno) in enumerate(zip(keys, annos)):
             n = rs.n_clips(key)
             if mode != "LTN":
-                board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], stn_finish(anno))
+                board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], stn_finish(anno),
+                                key)
                 continue
             ranges = scoring.part_ranges(n, part_len)
             board.add_spans(i, len(ranges), lambda key=key, n=n: scoring.part_spans(n, part_len, P, "rewindow", rs.first_clip(key))[0],
-                            lambda v, ranges=ranges, anno=anno: scoring.frame_scores_sht(v, ranges, anno, segment_len))
+                            lambda v, ranges=ranges, anno=anno: scoring.frame_scores_sht(v, ranges, anno, segment_len), key)
     else:
         loader = shanghaitech_test if dataset in ("SHT", "MT_SHT") else UBnormal_test
         feats_l, _, annos = loader(testing_txt, masks, dataset_path)
+        names = [line.strip().split(",")[0] for line in open(testing_txt, "r").readlines()] if weights is not None else None
         for i, (feats, anno) in enumerate(zip(feats_l, annos)):
+            name = names[i] if names else None
             n = feats.shape[0]
             if mode != "LTN":
                 board.add_clips(i, n, lambda feats=feats: scoring.stn_clip_scores(enc, head, _dev(feats, device, n_patch)),
-                                stn_finish(anno))
+                                stn_finish(anno), name)
                 continue
             ranges = scoring.part_ranges(n, part_len)
             board.add_ltn(i, len(ranges),
                           lambda feats=feats: scoring.ltn_part_sequences(_dev(feats, device, n_patch), part_len, tail="rewindow")[0],
-                          lambda v, ranges=ranges, anno=anno: scoring.frame_scores_sht(v, ranges, anno, segment_len))
-    return _auc_of(board.results(), return_frames)
+                          lambda v, ranges=ranges, anno=anno: scoring.frame_scores_sht(v, ranges, anno, segment_len), name)
+    return _finish_pass(board, weights, return_frames, "evaluate_auc")
 
 
 @torch.no_grad()
 def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, mask_dir, part_len, n_patch, segment_len=16,
-                       return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, resident=None):
+                       return_frames=False, pool_sequences=2048, rank=None, world=None, group=None, exchange=None, resident=None,
+                       device_auc=None):
     """Frame-level AUC over the TRAINING videos, the quantity the SHT / UBnormal train scripts select checkpoints on
     (Train/temporal_transformer_shanghaitech.py:186-229, Train/spatio_transformer_shanghaitech.py:145-172,
     Train/temporal_transformer_UBnormal.py:193-232): every training video is scored like a test video; a normal video's
     frames are labelled 0, an abnormal video's labels are the first frames of ``mask_dir + key + ".npy"`` (the upstream
     string concatenation - ``--test_mask_dir`` holds the masks of the training videos too).  Video class: second list
     field (SHT ``name,label``) or the ``abnormal`` / ``normal`` name prefix (UBnormal).  ``resident``: a ``ResidentSet`` of the
-    training videos - ``ResidentSet.from_pairs(feed)`` wraps the training bank already in HBM - instead of ``train_archive``."""
+    training videos - ``ResidentSet.from_pairs(feed)`` wraps the training bank already in HBM - instead of ``train_archive``.
+    ``device_auc``: as in ``evaluate_auc`` (the masks are read when the weights are filled, and never after)."""
+    weights = _device_auc_arg(device_auc, return_frames, "evaluate_train_auc")
     device = next(enc.parameters()).device
     rank, world = _ranks(rank, world, group)
     rs = resident
@@ -522,9 +636,10 @@ def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, ma
                     s = np.repeat(v, segment_len)
                     return s, frame_labels(abnormal, key, s.shape[0])
                 if rs is not None:
-                    board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], fin)
+                    board.add_spans(i, n, lambda key=key, n=n: scoring.part_spans(n, 1, P, first_clip=rs.first_clip(key))[0], fin, key)
                     continue
-                board.add_clips(i, n, lambda key=key: scoring.stn_clip_scores(enc, head, _dev(arc[key + ".npy"], device, n_patch)), fin)
+                board.add_clips(i, n, lambda key=key: scoring.stn_clip_scores(enc, head, _dev(arc[key + ".npy"], device, n_patch)), fin,
+                                key)
                 continue
             ranges = scoring.part_ranges(n, part_len)
 
@@ -533,10 +648,9 @@ def evaluate_train_auc(enc, head, mode, dataset, train_archive, training_txt, ma
                 return sfr, frame_labels(abnormal, key, sfr.shape[0])
             if rs is not None:
                 board.add_spans(i, len(ranges), lambda key=key, n=n: scoring.part_spans(n, part_len, P, "rewindow", rs.first_clip(key))[0],
-                                expand)
+                                expand, key)
                 continue
             board.add_ltn(i, len(ranges),
                           lambda key=key: scoring.ltn_part_sequences(_dev(arc[key + ".npy"], device, n_patch), part_len, tail="rewindow")[0],
-                          expand)
-        rows = board.results()
-    return _auc_of(rows, return_frames)
+                          expand, key)
+        return _finish_pass(board, weights, return_frames, "evaluate_train_auc")

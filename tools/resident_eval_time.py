@@ -11,7 +11,12 @@ each in fp32 and in bf16 mode; the label passes run with threshold 0, so that th
 is a score difference in every row of the report.  The archives are directories of .npy files (memory-mapped reads: the host-fed arm runs from the page
 cache after the warm-up round, its best case).  The arms run interleaved, ``--repeats`` (5) rounds after ``--warmup`` (1); each time is
 a host clock around the pass and a device synchronise.  The upload of the resident set is timed once and reported apart.
-Run on an MI355X:  python tools/resident_eval_time.py --work /tmp/resident_eval [--out profiles/resident_eval.txt]"""
+Run on an MI355X:  python tools/resident_eval_time.py --work /tmp/resident_eval [--out profiles/resident_eval.txt]
+
+``--device_auc`` measures the device AUC instead (profiles/device_auc.txt): evaluate_auc over the same resident sets with and
+without ``device_auc=`` (one filled pipeline.AucWeights per pass), interleaved; the host tail the flag replaces (the ``.cpu()`` copy
+of the flat score vector, every ``finish`` closure and metrics.roc_auc - the code of ``_ScoreBoard.results`` and ``_auc_of``), timed
+on the same flat vector in the same process; and the event-timed kernel pair of lstc_auc_weighted on the passes' own weights."""
 import argparse
 import json
 import os
@@ -75,6 +80,95 @@ def _time_arms(arms, warmup, repeats):
     return times, last
 
 
+def _device_auc_report(a, dev, lines, res):
+    """The --device_auc report (see the module docstring)."""
+    from lstc_vad_amd.models import Regressor
+    sht, sht_counts = _write(a.work, "sht", a.sht_videos, a.sht_clips, 16, False, 1)
+    ucf, ucf_counts = _write(a.work, "ucf", a.ucf_videos, a.ucf_clips, 9, True, 2)
+    wide = dict(n_layers=3, n_head=8, d_k=256, d_v=256, d_model=D, d_inner=4096, FFN_layerNorm=True, weight_init=False)
+    ltn = lambda depth: Encoder(MHA_layerNorm=True, relative_pe=True, window_size=4, window_depth=depth, **wide).to(dev).eval()
+    models = {("sht", "LTN"): (ltn(3), Classifier(D).to(dev).eval()), ("ucf", "LTN"): (ltn(2), Classifier(D).to(dev).eval()),
+              ("sht", "STN"): (Encoder(**wide).to(dev).eval(), Regressor(D).to(dev).eval())}
+    keys = lambda txt, is_ucf: [(l.split(" ")[0].split("/")[-1].split(".")[0] if is_ucf else l.split(",")[0])
+                                for l in open(txt).read().splitlines()]
+    sets = {"sht": pipeline.ResidentSet.from_archive(sht["feats"], keys(sht["test"], False), dev, n_patch=16),
+            "ucf": pipeline.ResidentSet.from_archive(ucf["feats"], keys(ucf["test"], True), dev, n_patch=9, view=True)}
+    lines.append(f"SHT-shaped: {a.sht_videos} videos, {sum(sht_counts)} clips, P = 16, d = {D}, part_len 3; UCF-shaped: {a.ucf_videos} "
+                 f"videos, {sum(ucf_counts)} clips, P = 9, 32 bins, part_len 2; both resident (pipeline.ResidentSet)")
+    lines.append(f"evaluate_auc, medians of {a.repeats} interleaved runs after {a.warmup} warm-up round(s) (min .. max): resident = "
+                 "evaluate_auc(resident=) as it stands, + device_auc = the same call with a filled AucWeights; host tail = .cpu() of the "
+                 "flat vector + every finish closure + metrics.roc_auc, on the pass's own flat vector, same process")
+    weights = {}
+    for mode, tag, kind in (("fp32", "sht", "LTN"), ("fp32", "ucf", "LTN"), ("bf16", "sht", "LTN"), ("bf16", "ucf", "LTN"),
+                            ("fp32", "sht", "STN")):
+        W, P, part_len, dataset = (sht, 16, 3, "SHT") if tag == "sht" else (ucf, 9, 2, "UCF")
+        enc, head = models[tag, kind]
+        w = weights.setdefault((tag, kind), pipeline.AucWeights())
+        Fn.set_compute_dtype(mode)
+        try:
+            ev = lambda **kw: pipeline.evaluate_auc(enc, head, kind, dataset, W["feats"], W["test"], W["masks"], part_len, P,
+                                                    resident=sets[tag], **kw)
+            ev(device_auc=w)                                        # fills the weights: built once, outside the timed runs
+            arms = {"resident": lambda: ev(), "+ device_auc": lambda: ev(device_auc=w)}
+            times, last = _time_arms(arms, a.warmup, a.repeats)
+            # the host tail on this pass's flat vector: what _ScoreBoard.results and _auc_of do behind the all-reduce
+            seen = {}
+            orig = pipeline._ScoreBoard.flat_scores
+
+            def spy(board):
+                seen["board"], seen["flat"] = board, orig(board)
+                return seen["flat"]
+            pipeline._ScoreBoard.flat_scores = spy
+            try:
+                ev()
+            finally:
+                pipeline._ScoreBoard.flat_scores = orig
+            board, flat = seen["board"], seen["flat"]
+
+            def tail():
+                host = flat.cpu().numpy()
+                return pipeline._auc_of([finish(host[off:off + n]) for off, n, finish in board.items], False)
+            t_tail, _ = _time_arms({"tail": tail}, a.warmup, a.repeats)
+        finally:
+            Fn.set_compute_dtype("fp32")
+        row = {"mode": mode, "set": tag, "net": kind, "rows": w.total, "frames": w.frames,
+               "auc_diff": abs(last["resident"] - last["+ device_auc"])}
+        for arm, t in (("resident", times["resident"]), ("device_auc", times["+ device_auc"]), ("host_tail", t_tail["tail"])):
+            row[arm] = {"median_s": statistics.median(t), "min_s": min(t), "max_s": max(t)}
+        row["resident_over_device_auc"] = row["resident"]["median_s"] / row["device_auc"]["median_s"]
+        res["rows"].append(row)
+        ms = lambda r: f"{r['median_s'] * 1e3:8.2f} ms ({r['min_s'] * 1e3:.2f} .. {r['max_s'] * 1e3:.2f})"
+        lines.append(f"  {mode:5s} {tag} {kind} evaluate_auc  {w.total:6d} rows {w.frames:7d} frames | resident {ms(row['resident'])} | "
+                     f"+ device_auc {ms(row['device_auc'])} | resident / device_auc {row['resident_over_device_auc']:.3f} | host tail "
+                     f"{ms(row['host_tail'])} | |AUC diff| {row['auc_diff']:.1e}")
+    # the kernel pair alone, event-timed, on the passes' own weights; 9 280 rows: the UCF pass's rows split into their two bins
+    wu, wl, ws = weights["ucf", "LTN"], weights["sht", "LTN"], weights["sht", "STN"]
+    half = lambda v: np.stack([v // 2, v - v // 2], 1).reshape(-1)
+    shaped = [("UCF bins", half(wu.pos_host), half(wu.neg_host)), ("SHT parts", wl.pos_host, wl.neg_host),
+              ("SHT clips", ws.pos_host, ws.neg_host)]
+    gen = torch.Generator().manual_seed(5)
+    for what, pos, neg in shaped:
+        n = int(pos.shape[0])
+        sc = torch.rand(n, generator=gen).to(dev)
+        dp, dn = torch.from_numpy(pos.astype(np.int32)).to(dev), torch.from_numpy(neg.astype(np.int32)).to(dev)
+        out = Fn.weighted_auc(sc, dp, dn)
+        ts = []
+        for _ in range(3 + 9):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            Fn.weighted_auc(sc, dp, dn, out=out)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e-3)
+        t = statistics.median(ts[3:])
+        rec = Fn.read_auc(out)
+        busy = int((np.add.reduceat(pos, np.arange(0, n, 256)) > 0).sum())
+        res["rows"].append({"kernel": "lstc_auc_weighted", "shape": what, "n": n, "median_us": t * 1e6, "pos": rec.pos, "neg": rec.neg,
+                            "row_blocks_with_positives": busy})
+        lines.append(f"  lstc_auc_weighted, {what:9s}: n = {n:6d}, P = {rec.pos}, N = {rec.neg}, {busy} of {(n + 255) // 256} blocks of 256 rows "
+                     f"hold a positive frame: {t * 1e6:.1f} us for the two launches (event-timed, median of 9)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--work", required=True, help="scratch directory for the synthetic archives (removed afterwards)")
@@ -85,6 +179,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--device_auc", action="store_true", help="the device-AUC report instead (profiles/device_auc.txt)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("resident_eval_time.py measures on the GPU: no device found")
@@ -93,6 +188,9 @@ def main():
     os.makedirs(a.work, exist_ok=True)
     lines, res = [], {"repeats": a.repeats, "rows": []}
     try:
+        if a.device_auc:
+            _device_auc_report(a, dev, lines, res)
+            return _finish(a, lines, res)
         sht, sht_counts = _write(a.work, "sht", a.sht_videos, a.sht_clips, 16, False, 1)
         ucf, ucf_counts = _write(a.work, "ucf", a.ucf_videos, a.ucf_clips, 9, True, 2)
         head = Classifier(D).to(dev).eval()
@@ -178,6 +276,10 @@ def main():
                          f"latency; gather_rows: ~6000 GB/s on an 805 MB batch)")
     finally:
         shutil.rmtree(a.work, ignore_errors=True)
+    _finish(a, lines, res)
+
+
+def _finish(a, lines, res):
     text = "\n".join(lines)
     print(text)
     print(json.dumps(res))
