@@ -956,6 +956,20 @@ def layernorm_bwd(dy2, x2, gamma, mean, rstd):
     return dx, sums[0], sums[1]
 
 
+def layernorm_bwd_rows(dz2, y, gamma, mean, rstd, p: float, seed: int, layer_norm: bool):
+    """Backward of ``z = [LayerNorm](dropout(f) + x)`` on f32 rows in separate passes: lstc_layernorm_bwd, then lstc_dropout_apply
+    -> (dy, df, dgamma, dbeta).  The route of the CLS-only nodes at every width (their [sequences, d] rows must not take the
+    fused kernels of ``layernorm_bwd_branch``: other launches, another summation order of dgamma / dbeta) and the plain arm of
+    ``layernorm_bwd_branch``."""
+    dgamma = dbeta = None
+    if layer_norm:
+        dy, dgamma, dbeta = layernorm_bwd(dz2, y, gamma, mean, rstd)
+    else:
+        dy = dz2
+    df = dropout_apply(dy, p, seed) if p > 0 else dy
+    return dy, df, dgamma, dbeta
+
+
 def layernorm_bwd_branch(dz2, y, gamma, mean, rstd, p: float, seed: int, layer_norm: bool, want_bias: bool):
     """Backward of ``z = [LayerNorm](dropout(f) + x)`` up to the two things its callers consume: ``dy`` (gradient of the
     residual sum, f32: it flows on into x) and ``df`` (gradient of the dropout's input f: operand of the weight / input
@@ -977,12 +991,7 @@ def layernorm_bwd_branch(dz2, y, gamma, mean, rstd, p: float, seed: int, layer_n
         sums = _ln_bwd_rows("lstc_layernorm_bwd_drop", dz2, y, gamma, mean, rstd, (dy, df), (float(p), int(seed)),
                             3 if want_bias else 2)
         return dy, df, sums[0], sums[1], (sums[2] if want_bias else None)
-    dgamma = dbeta = None
-    if layer_norm:
-        dy, dgamma, dbeta = layernorm_bwd(dz2, y, gamma, mean, rstd)
-    else:
-        dy = dz2
-    df = dropout_apply(dy, p, seed) if p > 0 else dy
+    dy, df, dgamma, dbeta = layernorm_bwd_rows(dz2, y, gamma, mean, rstd, p, seed, layer_norm)
     return dy, df, dgamma, dbeta, (colsum(df) if want_bias else None)
 
 
@@ -1052,6 +1061,38 @@ def _qkv_pack_desc(d, qkv: "Packed", H, dk, dv):
     d.Q = d.K = d.V = dev_ptr(qkv.buf)
 
 
+def _attn_desc(N, S, H, dk, dv, q, k, v, dtype, table=None, index=None, p_drop=0.0, seed=0):
+    """LstcAttnDesc with what every attention call fills the same way: shape, element type, bias table and index, scale, dropout
+    and the Q / K / V operands - row operands with their leading dims, or ``q`` the ``Packed`` fused Q | K | V projection
+    (``k``, ``v`` None).  The caller adds what is its own (O / O_pack, dO, gradients, probs, variant, dtable); a field nobody sets
+    stays zero."""
+    d = AttnDesc()
+    d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
+    d.dtype = dtype
+    if table is not None:
+        d.index_ld, d.table_rows = index.shape[1], table.shape[0]
+        d.table, d.index = dev_ptr(table), dev_ptr(index)
+    d.scale = 1.0 / (dk ** 0.5)
+    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
+    if isinstance(q, Packed):
+        _qkv_pack_desc(d, q, H, dk, dv)
+    else:
+        d.ldq, d.ldk, d.ldv = q.stride(0), k.stride(0), v.stride(0)
+        d.Q, d.K, d.V = dev_ptr(q), dev_ptr(k), dev_ptr(v)
+    return d
+
+
+def _dtable_chunks(n, H, npw=None):
+    """Partial bias-table gradients of an attention backward over ``n`` sequences: ``npw`` sequences per workgroup (default: by
+    the launch's size), one partial per workgroup, re-balanced so that no chunk is empty - the count the C launcher derives
+    from ``dtable_chunks`` (it returns LSTC_E_SHAPE on any other)."""
+    if npw is None:
+        npw = min(8, max(1, (n * H + 4095) // 4096))
+    chunks = (n + npw - 1) // npw
+    per = (n + chunks - 1) // chunks
+    return (n + per - 1) // per
+
+
 def attn_packed_inputs(N, S, H, dk, dv) -> bool:
     """bf16 mode: the attention core can read Q | K | V (and dO) as packed bf16 operands (include/lstc_hip.h, in_pack_cols)."""
     return (attn_fwd_pack(N, S, H, dv) and attn_bwd_packs(N, S, H, dk, dv) and _ATTN_PACKED_IN and S <= 96 and
@@ -1107,29 +1148,13 @@ def attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_drop, seed, packed=False,
         probs = torch.empty((N, H, S, (S + 3) // 4 * 4), device=dev, dtype=torch.float32)[..., :S]
     else:
         probs = torch.empty((N, H, S, S), device=dev, dtype=torch.float32)
-    d = AttnDesc()
-    d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
-    d.probs_ld = probs.stride(2)
-    if in_pack:
-        d.ldo = H * dv
-    else:
-        d.ldq, d.ldk, d.ldv, d.ldo = q.stride(0), k.stride(0), v.stride(0), (H * dv if packed else o.stride(0))
-    d.dtype = _attn_dtype()
-    if table is not None:
-        d.index_ld, d.table_rows = index.shape[1], table.shape[0]
-        d.table, d.index = dev_ptr(table), dev_ptr(index)
-    d.scale = 1.0 / (dk ** 0.5)
-    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
+    d = _attn_desc(N, S, H, dk, dv, q, k, v, _attn_dtype(), table, index, p_drop, seed)
     d.variant = _ATTN_VARIANT
-    d.probs = dev_ptr(probs)
-    if in_pack:
-        _qkv_pack_desc(d, q, H, dk, dv)
-    else:
-        d.Q, d.K, d.V = dev_ptr(q), dev_ptr(k), dev_ptr(v)
+    d.probs, d.probs_ld = dev_ptr(probs), probs.stride(2)
     if packed:
-        d.O_pack = dev_ptr(obuf)
+        d.O_pack, d.ldo = dev_ptr(obuf), H * dv
     else:
-        d.O = dev_ptr(o)
+        d.O, d.ldo = dev_ptr(o), o.stride(0)
     if mask is not None:
         check(_lib.load().lstc_attn_fwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_fwd_masked")
         return o, probs
@@ -1172,36 +1197,25 @@ def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, ou
         dq = dk_ = dv_ = None
     else:
         dq, dk_, dv_ = out if out is not None else (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
-    d = AttnDesc()
-    d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
-    if not in_pack:
-        d.ldq, d.ldk, d.ldv, d.ldo = q.stride(0), k.stride(0), v.stride(0), do.stride(0)
     if not packed and not (dq.stride(0) == q.stride(0) and dk_.stride(0) == k.stride(0) and dv_.stride(0) == v.stride(0)):
         raise RuntimeError("attn_bwd: dQ / dK / dV must have the row strides of Q / K / V")
-    d.dtype = _attn_dtype()
+    if not (probs.stride(3) == 1 and probs.stride(1) == S * probs.stride(2) and probs.stride(0) == H * S * probs.stride(2)):
+        raise RuntimeError(f"attn_bwd: probs must be [N, H, S, S] rows of one pitch (strides {probs.stride()})")
+    d = _attn_desc(N, S, H, dk, dv, q, k, v, _attn_dtype(), table, index, p_drop, seed)
     dtable = parts = None
     if table is not None:
         # one partial table per chunk of sequences, summed in a fixed order afterwards: no float atomics anywhere
-        npw = min(8, max(1, (N * H + 4095) // 4096))
+        npw = None
         if in_pack:        # the packed-input kernel's ring runs across a workgroup's sequences: fewer, longer workgroups (csrc/attention_pk.hip)
             npw = min(16, max(1, (N * H) // (8192 if S <= 32 else 1024)))
-        if _BWD_NPW:
-            npw = _BWD_NPW
-        chunks = (N + npw - 1) // npw
-        chunks = (N + ((N + chunks - 1) // chunks) - 1) // ((N + chunks - 1) // chunks)
+        chunks = _dtable_chunks(N, H, _BWD_NPW or npw)
         parts = torch.empty((chunks, table.shape[0] * H), device=probs.device, dtype=torch.float32)
-        d.index_ld, d.table_rows, d.dtable_chunks = index.shape[1], table.shape[0], chunks
-        d.table, d.index, d.dtable = dev_ptr(table), dev_ptr(index), dev_ptr(parts)
-    d.scale = 1.0 / (dk ** 0.5)
-    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
+        d.dtable, d.dtable_chunks = dev_ptr(parts), chunks
     d.probs, d.probs_ld = dev_ptr(probs), probs.stride(2)
-    if not (probs.stride(3) == 1 and probs.stride(1) == S * probs.stride(2) and probs.stride(0) == H * S * probs.stride(2)):
-        raise RuntimeError(f"attn_bwd: probs must be [N, H, S, S] rows of one pitch (strides {probs.stride()})")
     if in_pack:
-        _qkv_pack_desc(d, q, H, dk, dv)
         d.dO, d.dO_pack_cols, d.dO_col0 = dev_ptr(do.buf), do.K, 0
     else:
-        d.Q, d.K, d.V, d.dO = dev_ptr(q), dev_ptr(k), dev_ptr(v), dev_ptr(do)
+        d.dO, d.ldo = dev_ptr(do), do.stride(0)
     if packed:
         d.dQ_pack, d.dK_pack, d.dV_pack = (dev_ptr(b) for b in bufs)
         if packed == "fused":
@@ -1312,17 +1326,8 @@ def unpadded_layout(lengths, max_tokens=UNPADDED_MAX_TOKENS):
 
 
 def _attn_var_desc(q, k, v, H, dk, dv, table, index, p_drop, seed):
-    d = AttnDesc()
-    d.N, d.H, d.dk, d.dv = 1, H, dk, dv
-    d.ldq, d.ldk, d.ldv = q.stride(0), k.stride(0), v.stride(0)
-    d.dtype = F32                   # exact-f32 products in every compute mode
-    if table is not None:
-        d.index_ld, d.table_rows = index.shape[1], table.shape[0]
-        d.table, d.index = dev_ptr(table), dev_ptr(index)
-    d.scale = 1.0 / (dk ** 0.5)
-    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
-    d.Q, d.K, d.V = dev_ptr(q), dev_ptr(k), dev_ptr(v)
-    return d
+    """N = 1 and no S: the launch loop sets each launch's S; exact-f32 products in every compute mode."""
+    return _attn_desc(1, 0, H, dk, dv, q, k, v, F32, table, index, p_drop, seed)
 
 
 def attn_var_fwd(q, k, v, lay: SeqLayout, H, dk, dv, table, index, p_drop, seed, out=None, probs=None):
@@ -1356,10 +1361,7 @@ def attn_var_bwd(do, q, k, v, probs, lay: SeqLayout, H, dk, dv, table, index, p_
     d.dQ, d.dK, d.dV = dev_ptr(dq), dev_ptr(dk_), dev_ptr(dv_)
     chunks, parts = [], None
     if table is not None:
-        for _, _, n_ids in t["launches"]:
-            npw = min(8, max(1, (n_ids * H + 4095) // 4096))
-            c = (n_ids + npw - 1) // npw
-            chunks.append((n_ids + ((n_ids + c - 1) // c) - 1) // ((n_ids + c - 1) // c))
+        chunks = [_dtable_chunks(n_ids, H) for _, _, n_ids in t["launches"]]
         parts = torch.empty((sum(chunks), table.shape[0] * H), device=dev, dtype=torch.float32)
     first = 0
     for i, (S, ids, n_ids) in enumerate(t["launches"]):
@@ -1460,29 +1462,45 @@ class SDPAFunction(torch.autograd.Function):
         return dq, dk_, dv_, None, None, None, None
 
 
-def _fused_qkv_weight(wq, wk, wv):
-    """[rows_q + rows_k + rows_v, d] view over the three projection weights when they are consecutive slices of one
-    buffer (MultiHeadAttention.fuse_qkv_), else None.  The view object is kept on ``wq`` and reused while the buffer stays
-    where it is: its packed copies are cached on it like a leaf weight's (``_packed_operand``) and rebuilt by
+def _fused_weight(ws, attr):
+    """[sum of rows, d] view over the projection weights ``ws`` when they are consecutive slices of one buffer
+    (MultiHeadAttention.fuse_qkv_), else None.  The view object is kept on ``ws[0]`` under ``attr`` and reused while the buffer
+    stays where it is: its packed copies are cached on it like a leaf weight's (``_packed_operand``) and rebuilt by
     ``repack_weights`` after an optimizer step."""
+    w0 = ws[0]
     try:
-        same = wq.untyped_storage().data_ptr() == wk.untyped_storage().data_ptr() == wv.untyped_storage().data_ptr()
+        same = all(w.untyped_storage().data_ptr() == w0.untyped_storage().data_ptr() for w in ws)
     except Exception:
         return None
-    if not (same and wq.is_contiguous() and wk.is_contiguous() and wv.is_contiguous() and wq.shape[1] == wk.shape[1] == wv.shape[1]):
+    if not (same and all(w.is_contiguous() and w.shape[1] == w0.shape[1] for w in ws)):
         return None
-    if wk.storage_offset() != wq.storage_offset() + wq.numel() or wv.storage_offset() != wk.storage_offset() + wk.numel():
+    if any(b.storage_offset() != a.storage_offset() + a.numel() for a, b in zip(ws, ws[1:])):
         return None
-    rows = wq.shape[0] + wk.shape[0] + wv.shape[0]
-    hit = wq.__dict__.get("_lstc_fused_view")
-    if hit is not None and hit.data_ptr() == wq.data_ptr() and hit.shape == (rows, wq.shape[1]) and hit.device == wq.device:
+    rows = sum(w.shape[0] for w in ws)
+    hit = w0.__dict__.get(attr)
+    if hit is not None and hit.data_ptr() == w0.data_ptr() and hit.shape == (rows, w0.shape[1]) and hit.device == w0.device:
         return hit
-    view = torch.as_strided(wq.detach(), (rows, wq.shape[1]), (wq.shape[1], 1), wq.storage_offset())
+    view = torch.as_strided(w0.detach(), (rows, w0.shape[1]), (w0.shape[1], 1), w0.storage_offset())
     view._lstc_weight_view = True
-    view.__dict__["_lstc_view_of"] = wq          # its packs go stale with wq's (one optimizer updates all three slices)
-    wq.__dict__["_lstc_fused_view"] = view
+    view.__dict__["_lstc_view_of"] = w0          # its packs go stale with w0's (one optimizer updates all the slices)
+    w0.__dict__[attr] = view
     _weight_views.add(view)
     return view
+
+
+def _fused_qkv_weight(wq, wk, wv):
+    """The fused Q | K | V projection weight [rows_q + rows_k + rows_v, d], or None."""
+    return _fused_weight((wq, wk, wv), "_lstc_fused_view")
+
+
+def _fused_kv_weight(wk, wv):
+    """The fused K | V projection weight [rows_k + rows_v, d] (cross-attention over one key / value input), or None."""
+    return _fused_weight((wk, wv), "_lstc_fused_kv_view")
+
+
+def _cols3(t, rq, rk):
+    """The Q | K | V column blocks of a fused projection (or of its gradient): widths rq, rk and the rest."""
+    return t[:, :rq], t[:, rq: rq + rk], t[:, rq + rk:]
 
 
 _REPACK_WEIGHTS = os.environ.get("LSTC_NO_REPACK", "0") != "1"      # 0: weights are packed lazily, one launch per weight and layout (A/B)
@@ -1529,6 +1547,65 @@ def repack_weights(params) -> int:
 
 
 # ------------------------------------------------------------------------------ autograd Functions
+# ---- the block shell.  Every node below is the reference block  z = [LayerNorm](dropout(f(x) W^T [+ b]) + x)  around a core f of its
+# own (attention over full, unpadded, crossed or CLS-only sequences; the FFN's hidden layer).  What the blocks share stands here once:
+# the dropout draws, the output projection with its epilogue, the way back through it, and the hand-over of weight gradients.
+def _draw_dropout(cfg, sites):
+    """The dropout sites of one node invocation.  ``sites``: [(rate key in cfg, site suffix, shape)] in the node's fixed order.
+    -> [(p, seed)] in that order, p = 0 outside training.  One ``next_seed()`` per site with p > 0, in list order, then the
+    ``_note``s in the same order: the order of the draws is what makes a step replayable (``record_dropout``, the oracle's
+    replays, the device seed word of engine.GraphedStep), so no node draws a seed of its own."""
+    rates = [cfg[key] if cfg["training"] else 0.0 for key, _, _ in sites]
+    drawn = [(p, next_seed() if p > 0 else 0) for p in rates]
+    for (p, seed), (_, suffix, shape) in zip(drawn, sites):
+        if p > 0:
+            _note(cfg["site"] + suffix, p, seed, shape)
+    return drawn
+
+
+def _block_out(f, w, x2, ln_w, ln_b, cfg, drop, bias=None, pack=False):
+    """The forward epilogue of a block on f32 rows: y = dropout(f w^T [+ bias]) + x2 in the GEMM's epilogue, then LayerNorm when
+    the block has one (``pack``: see ``layernorm_fwd``).  -> (z, y for the backward - None without LayerNorm, where y is z -,
+    mean, rstd)."""
+    y = gemm(f, w, trans_b=True, bias=bias, dropout=drop, residual=x2)
+    if not cfg["layer_norm"]:
+        return y, None, None, None
+    z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6, pack=pack)
+    return z, y, mean, rstd
+
+
+def _wgrad_delivered(w, dy, x, x_pack=None):
+    """dW = dy^T x written to the sink of ``w`` where it has one, and delivered: what backward returns for ``w``."""
+    return deliver(w, wgrad(dy, x, x_pack, out=grad_sink(w)))
+
+
+def _proj_bwd(df, w, f, f_pack=None, out_pack=False):
+    """Back through the output projection y = f w^T: the weight gradient is delivered FIRST (the bucketed reducer steps per
+    bucket in delivery order), then d f = df w.  -> (what backward returns for w, d f)."""
+    dw = _wgrad_delivered(w, df, f, f_pack)
+    return dw, gemm(df, w, out_pack=out_pack)
+
+
+def _deliver_rows(ws, dw):
+    """The row blocks of a fused weight gradient ``dw``, delivered weight by weight in the order of ``ws``."""
+    out, r0 = [], 0
+    for w in ws:
+        out.append(deliver(w, dw[r0: r0 + w.shape[0]]))
+        r0 += w.shape[0]
+    return out
+
+
+def _cls_dropout(cfg, N, H, S, dm):
+    """The two sites of a CLS-only attention node: row 0 of the full [N, H, S, S] mask, and the [N, d] CLS rows."""
+    return _draw_dropout(cfg, [("attn_dropout", "attn_dropout#cls", (N, H, S, S)), ("fc_dropout", "dropout#cls", (N, dm))])
+
+
+def _zero_table_grad(shape, device):
+    """Gradient of a relative-bias table in a CLS-only node: the CLS row never sees the bias, so it is exactly zero - but the
+    reference still hands Adagrad that zero tensor, which applies weight decay to it (grad != None): zeros, not None."""
+    return None if shape is None else torch.zeros(shape, device=device, dtype=torch.float32)
+
+
 class MHAFunction(torch.autograd.Function):
     """models/MultiHeadAttention.py:93-132 (self-attention) as one autograd node.
 
@@ -1542,9 +1619,6 @@ class MHAFunction(torch.autograd.Function):
         N, S, dm = cfg["act_shape"]
         M = N * S
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
-        training = cfg["training"]
-        p_attn = cfg["attn_dropout"] if training else 0.0
-        p_fc = cfg["fc_dropout"] if training else 0.0
         out16 = bool(cfg.get("act16_out", False))
         xp = _act_pack(x, M, dm)
         wqkv = _fused_qkv_weight(wq, wk, wv)
@@ -1552,12 +1626,8 @@ class MHAFunction(torch.autograd.Function):
                                 packed_out_shape(M, H * dv) and packed_out_shape(M, dm)) or (not cfg["layer_norm"] and not out16):
             raise RuntimeError("MHAFunction: this layer / shape cannot run on the bf16 activation stream (functional.act_chain_ok)")
         qkv_p = gemm(xp, wqkv, trans_b=True, out_pack=True)
-        seed_a = next_seed() if p_attn > 0 else 0
-        seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:
-            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, S, S))
-        if p_fc > 0:
-            _note(cfg["site"] + "dropout", p_fc, seed_f, (N, S, dm))
+        (p_attn, seed_a), (p_fc, seed_f) = _draw_dropout(cfg, [("attn_dropout", "attn_dropout", (N, H, S, S)),
+                                                               ("fc_dropout", "dropout", (N, S, dm))])
         op, probs = attn_fwd(qkv_p, None, None, N, S, H, dk, dv, table, index, p_attn, seed_a)
         yp = gemm(op, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xp, out_pack=True)
         if cfg["layer_norm"]:
@@ -1585,13 +1655,11 @@ class MHAFunction(torch.autograd.Function):
         else:                    # z = dropout(f) + x: the incoming pack is the residual stream's gradient, its dropped form fc's
             dy, dln_w, dln_b = dzin, None, None
             df = dropout_apply_pack(dzin, c["p_fc"], c["seed_f"]) if c["p_fc"] > 0 else dzin
-        dwfc = deliver(wfc, wgrad(df, None, op, out=grad_sink(wfc)))
-        do = gemm(df, wfc, out_pack=True)
+        dwfc, do = _proj_bwd(df, wfc, None, op, out_pack=True)
         wqkv = _fused_qkv_weight(wq, wk, wv)
-        rq, rk = wq.shape[0], wk.shape[0]
         dqkv, _, _, dtable = attn_bwd(do, qkv_p, None, None, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"])
         dwqkv = wgrad(dqkv, None, xp, out=fused_grad_sink(wq, wk, wv))
-        dwq, dwk, dwv = deliver(wq, dwqkv[:rq]), deliver(wk, dwqkv[rq: rq + rk]), deliver(wv, dwqkv[rq + rk:])
+        dwq, dwk, dwv = _deliver_rows((wq, wk, wv), dwqkv)
         dx = _act_tensor(gemm(dqkv, wqkv, residual=dy, out_pack=True)) if want_dx else None
         return dx, dwq, dwk, dwv, dwfc, dln_w, dln_b, dtable, None, None
 
@@ -1607,9 +1675,6 @@ class MHAFunction(torch.autograd.Function):
         if seqs is not None and ((N, S) != (1, seqs.M) or cfg.get("mask") is not None):
             raise RuntimeError(f"MHAFunction: an unpadded batch is [1, M, d] = [1, {seqs.M}, d] without a mask, got {tuple(x.shape)}")
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
-        training = cfg["training"]
-        p_attn = cfg["attn_dropout"] if training else 0.0
-        p_fc = cfg["fc_dropout"] if training else 0.0
         dedup = _take_dedup_rows(x) if seqs is None else None    # exact-f32 mode, x straight from the fused gather + CLS concat: its distinct rows
         x2 = x.contiguous().view(N * S, dm)
         xp = maybe_pack(x2)            # f32x3: one pack of X feeds Q, K, V now and the three weight gradients later
@@ -1628,7 +1693,7 @@ class MHAFunction(torch.autograd.Function):
             if wqkv is not None:
                 qkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
                 expand_rows([gemm(xu, wqkv, trans_b=True)], [qkv], dedup.row_map)
-                q, k, v = qkv[:, : H * dk], qkv[:, H * dk: 2 * H * dk], qkv[:, 2 * H * dk:]
+                q, k, v = _cols3(qkv, H * dk, H * dk)
             else:
                 q, k = (torch.empty((N * S, H * dk), device=x2.device, dtype=torch.float32) for _ in range(2))
                 v = torch.empty((N * S, H * dv), device=x2.device, dtype=torch.float32)
@@ -1642,17 +1707,14 @@ class MHAFunction(torch.autograd.Function):
             del xu
         elif wqkv is not None:       # w_qs / w_ks / w_vs live in one buffer (MultiHeadAttention.fuse_qkv_): one GEMM, X read once
             qkv = gemm(xa, wqkv, trans_b=True)
-            q, k, v = qkv[:, : H * dk], qkv[:, H * dk: 2 * H * dk], qkv[:, 2 * H * dk:]
+            q, k, v = _cols3(qkv, H * dk, H * dk)
         else:
             q = gemm(xa, wq, trans_b=True)
             k = gemm(xa, wk, trans_b=True)
             v = gemm(xa, wv, trans_b=True)
-        seed_a = next_seed() if p_attn > 0 else 0
-        seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:      # unpadded: the counters run over the ragged probabilities buffer
-            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, S, S) if seqs is None else (seqs.n_probs(H),))
-        if p_fc > 0:
-            _note(cfg["site"] + "dropout", p_fc, seed_f, (N, S, dm))
+        # (unpadded: the attention counters run over the ragged probabilities buffer)
+        (p_attn, seed_a), (p_fc, seed_f) = _draw_dropout(cfg, [("attn_dropout", "attn_dropout", (N, H, S, S) if seqs is None else (seqs.n_probs(H),)),
+                                                               ("fc_dropout", "dropout", (N, S, dm))])
         if seqs is not None:
             o, probs = attn_var_fwd(q, k, v, seqs, H, dk, dv, table, index, p_attn, seed_a)
             op = maybe_pack(o)
@@ -1666,16 +1728,11 @@ class MHAFunction(torch.autograd.Function):
         else:
             o, probs = attn_fwd(q, k, v, N, S, H, dk, dv, table, index, p_attn, seed_a, mask=mask)
             op = maybe_pack(o)
-        y = gemm(op if op is not None else o, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=x2)
-        if cfg["layer_norm"]:
-            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6, pack=True)
-        else:
-            z, mean, rstd = y, None, None
-        ctx.packs = (xp, op) if (training or o is None) else (None, None)
+        z, y, mean, rstd = _block_out(op if op is not None else o, wfc, x2, ln_w, ln_b, cfg, (p_fc, seed_f), pack=True)
+        ctx.packs = (xp, op) if (cfg["training"] or o is None) else (None, None)
         ctx.qkv_p = qkv_p
         ctx.cfg = dict(cfg, N=N, S=S, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f)
-        ctx.save_for_backward(x2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs,
-                              y if cfg["layer_norm"] else None, mean, rstd)
+        ctx.save_for_backward(x2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs, y, mean, rstd)
         ctx.mark_non_differentiable(probs)
         return z.view(N, S, dm), probs
 
@@ -1690,9 +1747,8 @@ class MHAFunction(torch.autograd.Function):
         dz2 = dz.contiguous().view(N * S, -1)
         dy, df, dln_w, dln_b, _ = layernorm_bwd_branch(dz2, y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"], False)
         xp, op = ctx.packs
-        dwfc = deliver(wfc, wgrad(df, o, op, out=grad_sink(wfc)))
         qkv_p = ctx.qkv_p
-        do = gemm(df, wfc, out_pack=qkv_p is not None)       # [M, H*dv]; packed-input attention: as a packed bf16 operand only
+        dwfc, do = _proj_bwd(df, wfc, o, op, out_pack=qkv_p is not None)       # do [M, H*dv]; packed-input attention: as a packed bf16 operand only
         wqkv = _fused_qkv_weight(wq, wk, wv)
         dx = None
         if wqkv is not None:
@@ -1701,18 +1757,17 @@ class MHAFunction(torch.autograd.Function):
                 dqkv, _, _, dtable = attn_bwd(do, qkv_p, None, None, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"])
             elif seqs is not None:
                 dqkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
-                outs = (dqkv[:, :rq], dqkv[:, rq: rq + rk], dqkv[:, rq + rk:])
-                _, _, _, dtable = attn_var_bwd(do, q, k, v, probs, seqs, H, dk, dv, table, index, c["p_attn"], c["seed_a"], out=outs)
+                _, _, _, dtable = attn_var_bwd(do, q, k, v, probs, seqs, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
+                                               out=_cols3(dqkv, rq, rk))
             elif c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv) and N * S * wqkv.shape[0] * 2 < 2 ** 31:
                 # bf16 mode: the attention backward writes dQ | dK | dV straight into ONE packed bf16 operand
                 dqkv, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], packed="fused")
             else:
                 dqkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
-                outs = (dqkv[:, :rq], dqkv[:, rq: rq + rk], dqkv[:, rq + rk:])
-                _, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"], out=outs,
-                                           mask=c.get("mask"))
+                _, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
+                                           out=_cols3(dqkv, rq, rk), mask=c.get("mask"))
             dwqkv = wgrad(dqkv, x2, xp, out=fused_grad_sink(wq, wk, wv))      # one TN GEMM for the three weight gradients
-            dwq, dwk, dwv = deliver(wq, dwqkv[:rq]), deliver(wk, dwqkv[rq: rq + rk]), deliver(wv, dwqkv[rq + rk:])
+            dwq, dwk, dwv = _deliver_rows((wq, wk, wv), dwqkv)
             if ctx.needs_input_grad[0]:
                 dx = gemm(dqkv, wqkv, residual=dy).view(N, S, -1)   # dQ Wq + dK Wk + dV Wv + residual in one GEMM (K = 3*H*dk)
         else:
@@ -1722,38 +1777,13 @@ class MHAFunction(torch.autograd.Function):
                 dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
                                                 packed=c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv),
                                                 mask=c.get("mask"))
-            dwq = deliver(wq, wgrad(dq, x2, xp, out=grad_sink(wq)))
-            dwk = deliver(wk, wgrad(dk_, x2, xp, out=grad_sink(wk)))
-            dwv = deliver(wv, wgrad(dv_, x2, xp, out=grad_sink(wv)))
+            dwq, dwk, dwv = _wgrad_delivered(wq, dq, x2, xp), _wgrad_delivered(wk, dk_, x2, xp), _wgrad_delivered(wv, dv_, x2, xp)
             if ctx.needs_input_grad[0]:
                 dx = gemm(dq, wq, residual=dy)
                 gemm(dk_, wk, out=dx, accumulate=True)
                 gemm(dv_, wv, out=dx, accumulate=True)
                 dx = dx.view(N, S, -1)
         return dx, dwq, dwk, dwv, dwfc, dln_w, dln_b, dtable, None, None
-
-
-def _fused_kv_weight(wk, wv):
-    """[rows_k + rows_v, d] view over the key and value projection weights when they are consecutive slices of one buffer
-    (MultiHeadAttention.fuse_qkv_), else None; kept on ``wk`` and refreshed like ``_fused_qkv_weight``'s view."""
-    try:
-        same = wk.untyped_storage().data_ptr() == wv.untyped_storage().data_ptr()
-    except Exception:
-        return None
-    if not (same and wk.is_contiguous() and wv.is_contiguous() and wk.shape[1] == wv.shape[1]):
-        return None
-    if wv.storage_offset() != wk.storage_offset() + wk.numel():
-        return None
-    rows = wk.shape[0] + wv.shape[0]
-    hit = wk.__dict__.get("_lstc_fused_kv_view")
-    if hit is not None and hit.data_ptr() == wk.data_ptr() and hit.shape == (rows, wk.shape[1]) and hit.device == wk.device:
-        return hit
-    view = torch.as_strided(wk.detach(), (rows, wk.shape[1]), (wk.shape[1], 1), wk.storage_offset())
-    view._lstc_weight_view = True
-    view.__dict__["_lstc_view_of"] = wk
-    wk.__dict__["_lstc_fused_kv_view"] = view
-    _weight_views.add(view)
-    return view
 
 
 class MHACrossFunction(torch.autograd.Function):
@@ -1772,9 +1802,6 @@ class MHACrossFunction(torch.autograd.Function):
         N, Sq, dm = xq.shape
         Sk = xk.shape[1]
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
-        training = cfg["training"]
-        p_attn = cfg["attn_dropout"] if training else 0.0
-        p_fc = cfg["fc_dropout"] if training else 0.0
         mask = cfg.get("mask")
         xq2 = xq.contiguous().view(N * Sq, dm)
         same_kv = xk is xv
@@ -1790,12 +1817,8 @@ class MHACrossFunction(torch.autograd.Function):
         else:
             k = gemm(xkp if xkp is not None else xk2, wk, trans_b=True)
             v = gemm(xvp if xvp is not None else xv2, wv, trans_b=True)
-        seed_a = next_seed() if p_attn > 0 else 0
-        seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:
-            _note(cfg["site"] + "attn_dropout", p_attn, seed_a, (N, H, Sq, Sk))
-        if p_fc > 0:
-            _note(cfg["site"] + "dropout", p_fc, seed_f, (N, Sq, dm))
+        (p_attn, seed_a), (p_fc, seed_f) = _draw_dropout(cfg, [("attn_dropout", "attn_dropout", (N, H, Sq, Sk)),
+                                                               ("fc_dropout", "dropout", (N, Sq, dm))])
         square = Sq == Sk
         if square:
             o, probs = attn_fwd(q, k, v, N, Sq, H, dk, dv, table, index, p_attn, seed_a, mask=mask)
@@ -1807,15 +1830,10 @@ class MHACrossFunction(torch.autograd.Function):
                                 v.view(N, Sk, H, dv).transpose(1, 2), 1.0 / (dk ** 0.5), p_attn, seed_a, mask,
                                 out=o.view(N, Sq, H, dv).transpose(1, 2))
         op = maybe_pack(o)
-        y = gemm(op if op is not None else o, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xq2)
-        if cfg["layer_norm"]:
-            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6, pack=True)
-        else:
-            z, mean, rstd = y, None, None
-        ctx.packs = (xqp, xkp, xvp, op) if training else (None, None, None, None)
+        z, y, mean, rstd = _block_out(op if op is not None else o, wfc, xq2, ln_w, ln_b, cfg, (p_fc, seed_f), pack=True)
+        ctx.packs = (xqp, xkp, xvp, op) if cfg["training"] else (None, None, None, None)
         ctx.cfg = dict(cfg, N=N, Sq=Sq, Sk=Sk, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, square=square, same_kv=same_kv)
-        ctx.save_for_backward(xq2, xk2, None if same_kv else xv2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs,
-                              y if cfg["layer_norm"] else None, mean, rstd)
+        ctx.save_for_backward(xq2, xk2, None if same_kv else xv2, wq, wk, wv, wfc, ln_w, table, index, q, k, v, o, probs, y, mean, rstd)
         ctx.mark_non_differentiable(probs)
         return z.view(N, Sq, dm), probs
 
@@ -1830,8 +1848,7 @@ class MHACrossFunction(torch.autograd.Function):
         dz2 = dz.contiguous().view(N * Sq, -1)
         dy, df, dln_w, dln_b, _ = layernorm_bwd_branch(dz2, y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"], False)
         xqp, xkp, xvp, op = ctx.packs
-        dwfc = deliver(wfc, wgrad(df, o, op, out=grad_sink(wfc)))
-        do = gemm(df, wfc)                                   # [N*Sq, H*dv]
+        dwfc, do = _proj_bwd(df, wfc, o, op)                 # do [N*Sq, H*dv]
         if c["square"]:
             # dQ, dK, dV with the row strides of Q, K, V (K and V may be the two column blocks of one product)
             outs = tuple(torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=torch.float32) for t in (q, k, v))
@@ -1844,9 +1861,7 @@ class MHACrossFunction(torch.autograd.Function):
             # back to token-major rows: views, with the row pitch of the projection they belong to
             dq, dk_, dv_ = (g.transpose(1, 2).reshape(g.shape[0] * g.shape[2], H * g.shape[3]) for g in (dq4, dk4, dv4))
             dtable = None
-        dwq = deliver(wq, wgrad(dq, xq2, xqp, out=grad_sink(wq)))
-        dwk = deliver(wk, wgrad(dk_, xk2, xkp, out=grad_sink(wk)))
-        dwv = deliver(wv, wgrad(dv_, xv2, xvp, out=grad_sink(wv)))
+        dwq, dwk, dwv = _wgrad_delivered(wq, dq, xq2, xqp), _wgrad_delivered(wk, dk_, xk2, xkp), _wgrad_delivered(wv, dv_, xv2, xvp)
         dxq = gemm(dq, wq, residual=dy).view(N, Sq, -1) if ctx.needs_input_grad[0] else None
         dxk = gemm(dk_, wk).view(N, Sk, -1) if ctx.needs_input_grad[1] else None
         dxv = gemm(dv_, wv).view(N, Sk, -1) if ctx.needs_input_grad[2] else None
@@ -2042,32 +2057,20 @@ class MHAClsAssocFunction(torch.autograd.Function):
         tok = ClsTokens.of(x, cfg)
         N, S, dm = tok.N, tok.S, tok.dm
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
-        training = cfg["training"]
-        p_attn = cfg["attn_dropout"] if training else 0.0
-        p_fc = cfg["fc_dropout"] if training else 0.0
         ctx.table_shape = None if table is None else tuple(table.shape)
         xc = tok.cls_rows(H)
         scale = 1.0 / (dk ** 0.5)
         qc = gemm(xc, wq, trans_b=True)                                                   # [N, H*dk]
         u = torch.empty((N, H, dm), device=x.device, dtype=torch.float32)
         gemm_batched(qc, wk, u, N, dm, dk, H * dk, dm, H * dm, False, False, H, dk, dk * dm, dm, alpha=scale)
-        seed_a = next_seed() if p_attn > 0 else 0
-        seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:
-            _note(cfg["site"] + "attn_dropout#cls", p_attn, seed_a, (N, H, S, S))
-        if p_fc > 0:
-            _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
+        (p_attn, seed_a), (p_fc, seed_f) = _cls_dropout(cfg, N, H, S, dm)
         pd, probs = tok.dot(u, 1, None, p_attn, seed_a)                                   # dropped probs, probs
         xb = tok.wsum(pd)                                                                 # [N, H, d]
         oc = torch.empty((N, H * dv), device=x.device, dtype=torch.float32)
         per_head_rows_wT(xb, wv, oc, N, dv, dm, H)
-        y = gemm(oc, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xc)
-        if cfg["layer_norm"]:
-            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6)
-        else:
-            z, mean, rstd = y, None, None
+        z, y, mean, rstd = _block_out(oc, wfc, xc, ln_w, ln_b, cfg, (p_fc, seed_f))
         ctx.cfg = dict(cfg, N=N, S=S, dm=dm, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f, scale=scale)
-        ctx.save_for_backward(tok.x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y if cfg["layer_norm"] else None, mean, rstd, xc)
+        ctx.save_for_backward(tok.x, wq, wk, wv, wfc, ln_w, qc, u, pd, probs, xb, oc, y, mean, rstd, xc)
         return z
 
     @staticmethod
@@ -2078,15 +2081,8 @@ class MHAClsAssocFunction(torch.autograd.Function):
         N, H, dk, dv, scale = c["N"], c["n_head"], c["d_k"], c["d_v"], c["scale"]
         dm = c["dm"]
         tok = ClsTokens.of(x, c)
-        dz = dz.contiguous()
-        dln_w = dln_b = None
-        if c["layer_norm"]:
-            dy, dln_w, dln_b = layernorm_bwd(dz, y, ln_w, mean, rstd)
-        else:
-            dy = dz
-        df = dropout_apply(dy, c["p_fc"], c["seed_f"]) if c["p_fc"] > 0 else dy
-        dwfc = deliver(wfc, wgrad(df, oc, out=grad_sink(wfc)))
-        doc = gemm(df, wfc)                                                               # [N, H*dv]
+        dy, df, dln_w, dln_b = layernorm_bwd_rows(dz.contiguous(), y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"])
+        dwfc, doc = _proj_bwd(df, wfc, oc)                                                # doc [N, H*dv]
         dxb = torch.empty((N, H, dm), device=x.device, dtype=torch.float32)
         gemm_batched(doc, wv, dxb, N, dm, dv, H * dv, dm, H * dm, False, False, H, dv, dv * dm, dm)
         dwv = grad_sink(wv)
@@ -2109,20 +2105,15 @@ class MHAClsAssocFunction(torch.autograd.Function):
             else:
                 dx = tok.outer(pd, dxb, ds, u)
                 gemm(dqc, wq, out=dx[:, 0, :], accumulate=True, residual=dy)
-        dtable = None if ctx.table_shape is None else torch.zeros(ctx.table_shape, device=x.device, dtype=torch.float32)
-        return dx, deliver(wq, dwq), deliver(wk, dwk), deliver(wv, dwv), dwfc, dln_w, dln_b, dtable, None
+        return dx, deliver(wq, dwq), deliver(wk, dwk), deliver(wv, dwv), dwfc, dln_w, dln_b, _zero_table_grad(ctx.table_shape, x.device), None
 
 
 def attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_drop, seed, mask=None):
     """``mask``: a normalised attention mask (``attn_mask_arg``); the CLS kernels read its query row 0."""
     oc = torch.empty((N, H * dv), device=qc.device, dtype=torch.float32)
     probs = torch.empty((N, H, S), device=qc.device, dtype=torch.float32)
-    d = AttnDesc()
-    d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
-    d.ldq, d.ldk, d.ldv, d.ldo = qc.stride(0), k.stride(0), v.stride(0), oc.stride(0)
-    d.dtype, d.scale = F32, 1.0 / (dk ** 0.5)
-    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
-    d.Q, d.K, d.V, d.O, d.probs = dev_ptr(qc), dev_ptr(k), dev_ptr(v), dev_ptr(oc), dev_ptr(probs)
+    d = _attn_desc(N, S, H, dk, dv, qc, k, v, F32, p_drop=p_drop, seed=seed)
+    d.O, d.ldo, d.probs = dev_ptr(oc), oc.stride(0), dev_ptr(probs)
     if mask is not None:
         check(_lib.load().lstc_attn_cls_fwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_cls_fwd_masked")
     else:
@@ -2132,13 +2123,9 @@ def attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_drop, seed, mask=None):
 
 def attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, p_drop, seed, mask=None):
     dqc, dk_, dv_ = torch.empty_like(qc), torch.empty_like(k), torch.empty_like(v)
-    d = AttnDesc()
-    d.N, d.S, d.H, d.dk, d.dv = N, S, H, dk, dv
-    d.ldq, d.ldk, d.ldv, d.ldo = qc.stride(0), k.stride(0), v.stride(0), doc.stride(0)
-    d.dtype, d.scale = F32, 1.0 / (dk ** 0.5)
-    d.dropout_p, d.dropout_seed = float(p_drop), int(seed)
-    d.Q, d.K, d.V, d.probs = dev_ptr(qc), dev_ptr(k), dev_ptr(v), dev_ptr(probs)
-    d.dO, d.dQ, d.dK, d.dV = dev_ptr(doc), dev_ptr(dqc), dev_ptr(dk_), dev_ptr(dv_)
+    d = _attn_desc(N, S, H, dk, dv, qc, k, v, F32, p_drop=p_drop, seed=seed)
+    d.probs, d.dO, d.ldo = dev_ptr(probs), dev_ptr(doc), doc.stride(0)
+    d.dQ, d.dK, d.dV = dev_ptr(dqc), dev_ptr(dk_), dev_ptr(dv_)
     if mask is not None:
         check(_lib.load().lstc_attn_cls_bwd_masked(C.byref(d), C.byref(_mask_desc(mask)), stream_ptr()), "lstc_attn_cls_bwd_masked")
     else:
@@ -2155,14 +2142,9 @@ class MHAClsFunction(torch.autograd.Function):
     @staticmethod
     @_small_m_fwd
     def forward(ctx, x, wq, wk, wv, wfc, ln_w, ln_b, table, cfg):
-        # `table`: the layer's relative-position bias table.  Row 0 never sees the bias, so its gradient is exactly
-        # zero — but the reference still hands Adagrad that zero tensor, and Adagrad applies weight decay to it
-        # (grad != None).  backward() therefore returns zeros for it instead of None to keep the update identical.
+        # `table`: the layer's relative-position bias table; its gradient is ``_zero_table_grad``
         N, S, dm = x.shape
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
-        training = cfg["training"]
-        p_attn = cfg["attn_dropout"] if training else 0.0
-        p_fc = cfg["fc_dropout"] if training else 0.0
         ctx.table_shape = None if table is None else tuple(table.shape)
         x = x.contiguous()
         x2 = x.view(N * S, dm)
@@ -2170,20 +2152,11 @@ class MHAClsFunction(torch.autograd.Function):
         k = gemm(x2, wk, trans_b=True)
         v = gemm(x2, wv, trans_b=True)
         qc = gemm(xc, wq, trans_b=True)
-        seed_a = next_seed() if p_attn > 0 else 0
-        seed_f = next_seed() if p_fc > 0 else 0
-        if p_attn > 0:
-            _note(cfg["site"] + "attn_dropout#cls", p_attn, seed_a, (N, H, S, S))     # row 0 of the full mask
-        if p_fc > 0:
-            _note(cfg["site"] + "dropout#cls", p_fc, seed_f, (N, dm))
+        (p_attn, seed_a), (p_fc, seed_f) = _cls_dropout(cfg, N, H, S, dm)
         oc, probs = attn_cls_fwd(qc, k, v, N, S, H, dk, dv, p_attn, seed_a, mask=cfg.get("mask"))
-        y = gemm(oc, wfc, trans_b=True, dropout=(p_fc, seed_f), residual=xc)
-        if cfg["layer_norm"]:
-            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6)
-        else:
-            z, mean, rstd = y, None, None
+        z, y, mean, rstd = _block_out(oc, wfc, xc, ln_w, ln_b, cfg, (p_fc, seed_f))
         ctx.cfg = dict(cfg, N=N, S=S, p_attn=p_attn, p_fc=p_fc, seed_a=seed_a, seed_f=seed_f)
-        ctx.save_for_backward(x, wq, wk, wv, wfc, ln_w, qc, k, v, oc, probs, y if cfg["layer_norm"] else None, mean, rstd)
+        ctx.save_for_backward(x, wq, wk, wv, wfc, ln_w, qc, k, v, oc, probs, y, mean, rstd)
         return z
 
     @staticmethod
@@ -2194,26 +2167,17 @@ class MHAClsFunction(torch.autograd.Function):
         N, S, H, dk, dv = c["N"], c["S"], c["n_head"], c["d_k"], c["d_v"]
         dm = x.shape[-1]
         x2, xc = x.view(N * S, dm), x[:, 0, :]
-        dz = dz.contiguous()
-        dln_w = dln_b = None
-        if c["layer_norm"]:
-            dy, dln_w, dln_b = layernorm_bwd(dz, y, ln_w, mean, rstd)
-        else:
-            dy = dz
-        df = dropout_apply(dy, c["p_fc"], c["seed_f"]) if c["p_fc"] > 0 else dy
-        dwfc = deliver(wfc, wgrad(df, oc, out=grad_sink(wfc)))
-        doc = gemm(df, wfc)
+        dy, df, dln_w, dln_b = layernorm_bwd_rows(dz.contiguous(), y, ln_w, mean, rstd, c["p_fc"], c["seed_f"], c["layer_norm"])
+        dwfc, doc = _proj_bwd(df, wfc, oc)
         dqc, dk_, dv_ = attn_cls_bwd(doc, qc, k, v, probs, N, S, H, dk, dv, c["p_attn"], c["seed_a"], mask=c.get("mask"))
-        dwq = deliver(wq, wgrad(dqc, xc, out=grad_sink(wq)))
-        dwk, dwv = deliver(wk, wgrad(dk_, x2, out=grad_sink(wk))), deliver(wv, wgrad(dv_, x2, out=grad_sink(wv)))
+        dwq, dwk, dwv = _wgrad_delivered(wq, dqc, xc), _wgrad_delivered(wk, dk_, x2), _wgrad_delivered(wv, dv_, x2)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = gemm(dk_, wk)
             gemm(dv_, wv, out=dx, accumulate=True)
             gemm(dqc, wq, out=dx.view(N, S, dm)[:, 0, :], accumulate=True, residual=dy)   # CLS rows: + dQ Wq + residual
             dx = dx.view(N, S, dm)
-        dtable = None if ctx.table_shape is None else torch.zeros(ctx.table_shape, device=x.device, dtype=torch.float32)
-        return dx, dwq, dwk, dwv, dwfc, dln_w, dln_b, dtable, None
+        return dx, dwq, dwk, dwv, dwfc, dln_w, dln_b, _zero_table_grad(ctx.table_shape, x.device), None
 
 
 _PAD_HIDDEN = os.environ.get("LSTC_NO_PAD_HIDDEN", "0") != "1"
@@ -2256,10 +2220,7 @@ class FFNFunction(torch.autograd.Function):
         """The block on the bf16 activation stream (see MHAFunction._forward_act)."""
         N, S, dm = cfg["act_shape"]
         M = N * S
-        p = cfg["dropout"] if cfg["training"] else 0.0
-        seed = next_seed() if p > 0 else 0
-        if p > 0:
-            _note(cfg["site"] + "dropout", p, seed, (N, S, dm))
+        (p, seed), = _draw_dropout(cfg, [("dropout", "dropout", (N, S, dm))])
         out16 = bool(cfg.get("act16_out", False))
         F = w1.shape[0]
         Fp = _padded_hidden(F)
@@ -2311,10 +2272,7 @@ class FFNFunction(torch.autograd.Function):
         shape = x.shape
         dm = shape[-1]
         x2 = x.contiguous().view(-1, dm)
-        p = cfg["dropout"] if cfg["training"] else 0.0
-        seed = next_seed() if p > 0 else 0
-        if p > 0:
-            _note(cfg["site"] + "dropout", p, seed, shape)
+        (p, seed), = _draw_dropout(cfg, [("dropout", "dropout", shape)])
         F = w1.shape[0]
         Fp = _padded_hidden(F)
         ctx.F = F
@@ -2332,16 +2290,12 @@ class FFNFunction(torch.autograd.Function):
         else:
             h1 = gemm(xp if xp is not None else x2, w1, trans_b=True, bias=b1, relu=True)
             hp = maybe_pack(h1)
-        y = gemm(hp if hp is not None else h1, w2, trans_b=True, bias=b2, dropout=(p, seed), residual=x2)
         ctx.packs = (xp, hp) if (cfg["training"] or h1 is None) else (None, None)
-        if cfg["layer_norm"]:
-            # the packed bf16 copy of the result is worth its 2 B / element only when a full encoder layer consumes it next
-            # (Encoder sets emit_pack: not for the layer that feeds the CLS-only last layer or the caller)
-            z, mean, rstd = layernorm_fwd(y, ln_w, ln_b, 1e-6, pack=cfg.get("emit_pack", True))
-        else:
-            z, mean, rstd = y, None, None
+        # the packed bf16 copy of the result is worth its 2 B / element only when a full encoder layer consumes it next
+        # (Encoder sets emit_pack: not for the layer that feeds the CLS-only last layer or the caller)
+        z, y, mean, rstd = _block_out(hp if hp is not None else h1, w2, x2, ln_w, ln_b, cfg, (p, seed), bias=b2, pack=cfg.get("emit_pack", True))
         ctx.cfg = dict(cfg, p=p, seed=seed, shape=tuple(shape))
-        ctx.save_for_backward(x2, w1, w2, ln_w, h1, y if cfg["layer_norm"] else None, mean, rstd)
+        ctx.save_for_backward(x2, w1, w2, ln_w, h1, y, mean, rstd)
         return z.view(shape)
 
     @staticmethod
@@ -2734,14 +2688,9 @@ class HeadFunction(torch.autograd.Function):
     @_small_m_fwd
     def forward(ctx, x, w0, b0, w3, b3, w5, b5, cfg):
         x2 = x.contiguous().view(-1, x.shape[-1])
-        p = cfg["dropout"] if cfg["training"] else 0.0
         c = w5.shape[0]
-        s1 = next_seed() if p > 0 else 0
-        s2 = next_seed() if p > 0 else 0
         rows = x2.shape[0]
-        if p > 0:
-            _note(cfg["site"] + ".2", p, s1, (rows, w0.shape[0]))
-            _note(cfg["site"] + ".4", p, s2, (rows, 32))
+        (p, s1), (_, s2) = _draw_dropout(cfg, [("dropout", ".2", (rows, w0.shape[0])), ("dropout", ".4", (rows, 32))])
         h1 = gemm(x2, w0, trans_b=True, bias=b0, relu=True, dropout=(p, s1))        # relu then dropout
         h2 = gemm(h1, w3, trans_b=True, bias=b3, dropout=(p, s2))
         out = torch.empty((rows, c), device=x.device, dtype=torch.float32)
@@ -2772,7 +2721,7 @@ class HeadFunction(torch.autograd.Function):
         if p > 0:
             da1 = dropout_apply(da1, p, cf["s1"])
         db0 = colsum(da1)
-        dw0 = deliver(w0, wgrad(da1, x2, out=grad_sink(w0)))
+        dw0 = _wgrad_delivered(w0, da1, x2)
         dx = gemm(da1, w0).view(cf["in_shape"]) if ctx.needs_input_grad[0] else None
         return dx, dw0, db0, dw3, db3, dw5, db5, None
 

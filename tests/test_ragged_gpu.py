@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import util_ragged as R
+from util import _LibSpy
 from util_mask import bar
 from util_rowops import tol
 
@@ -345,23 +346,6 @@ def test_padding_gets_exact_zero_gradient_and_changes_no_bit(name):
 
 
 # ---------------------------------------------------------------------------------------------------- 4. routing
-class _LibSpy:
-    """Records the name of every C entry point the Python layer calls (``_lib.load()`` hands out this proxy)."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("lstc_") or name in ("lstc_strerror", "lstc_pack1_bytes", "lstc_version"):
-            return fn
-
-        def wrapped(*a):
-            self.calls.append(name)
-            return fn(*a)
-        return wrapped
-
-
 def _spy(monkeypatch):
     L = _lib()
     spy = _LibSpy(L.load())

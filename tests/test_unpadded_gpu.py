@@ -11,6 +11,7 @@ import torch
 
 import util_ragged as R
 import util_unpadded as U
+from util import _LibSpy
 from util_mask import bar, model_index
 from util_rowops import tol
 
@@ -527,25 +528,6 @@ def test_dropout_draws_are_reproducible_and_ragged():
     assert shapes["layer_stack.0.slf_attn.dropout"] == shapes["layer_stack.0.pos_ffn.dropout"] == {(1, M, 32)}
     assert shapes["layer_stack.2.slf_attn.attn_dropout#cls"] == {(N, 2, S_max, S_max)} and shapes["layer_stack.2.slf_attn.dropout#cls"] == {(N, 32)}
     assert shapes["layer_stack.2.pos_ffn.dropout"] == {(N, 32), (1, M, 32)}          # the CLS-only call and the full one
-
-
-class _LibSpy:
-    """Records every C entry point the Python layer calls, with the row count of each GEMM (``_lib.load()`` hands out this proxy)."""
-
-    def __init__(self, lib):
-        self._lib, self.calls, self.gemm_rows = lib, [], []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("lstc_") or name in ("lstc_strerror", "lstc_pack1_bytes", "lstc_version"):
-            return fn
-
-        def wrapped(*a):
-            self.calls.append(name)
-            if name == "lstc_gemm":
-                self.gemm_rows.append(int(a[0]._obj.M))
-            return fn(*a)
-        return wrapped
 
 
 def _spy(monkeypatch):

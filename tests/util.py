@@ -130,6 +130,26 @@ def attn_layout(kind, ts):
     return views
 
 
+class _LibSpy:
+    """Records every C entry point the Python layer calls, with the row count of each GEMM (hand it out in place of the library:
+    ``monkeypatch.setattr(_lib, "load", lambda: spy)``)."""
+
+    def __init__(self, lib):
+        self._lib, self.calls, self.gemm_rows = lib, [], []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("lstc_") or name in ("lstc_strerror", "lstc_pack1_bytes", "lstc_version"):
+            return fn
+
+        def wrapped(*a):
+            self.calls.append(name)
+            if name == "lstc_gemm":
+                self.gemm_rows.append(int(a[0]._obj.M))
+            return fn(*a)
+        return wrapped
+
+
 _BATCH_CACHE = {}
 
 
