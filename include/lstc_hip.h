@@ -260,9 +260,10 @@ typedef struct LstcAttnDesc {
      * exists in this form: the attention core moves 2 bytes per element each way. */
     int32_t in_pack_cols, Q_col0, K_col0, V_col0;
     int32_t dO_pack_cols, dO_col0;
-    /* row pitch of `probs` in floats: 0 or S = dense [N,H,S,S].  The packed-input kernels need a multiple of 4 (>= S; `probs`
-     * 16-B aligned): they move the probabilities as 16-B groups, the forward writes zeros into the padding columns and the
-     * backward expects them there. */
+    /* row pitch of `probs` in floats: 0 or S = dense [N,H,S,S].  The packed-input kernels need a multiple of 4 with
+     * S <= probs_ld <= 32 * ceil(S / 32) (`probs` 16-B aligned; LSTC_E_SHAPE otherwise): they move the probabilities as 16-B
+     * groups of a row's 32 * ceil(S / 32) key columns, the forward writes zeros into the padding columns [S, probs_ld) and the
+     * backward expects them there.  A wider pitch would hold columns neither kernel touches, so it is refused. */
     int32_t probs_ld;
 } LstcAttnDesc;
 

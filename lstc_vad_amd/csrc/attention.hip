@@ -892,7 +892,9 @@ int fill_packed_inputs(const LstcAttnDesc* d, AttnParams& p, bool bwd) {
         d->Q_col0 + p.H * p.dk > d->in_pack_cols || d->K_col0 + p.H * p.dk > d->in_pack_cols || d->V_col0 + p.H * p.dv > d->in_pack_cols ||
         M * (int64_t)d->in_pack_cols * 2 > 0x7fffffffLL) return LSTC_E_SHAPE;
     if (!aligned16(d->Q) || !aligned16(d->K) || !aligned16(d->V) || !aligned16(d->probs)) return LSTC_E_ALIGN;
-    if (d->probs_ld < p.S || d->probs_ld % 4 || (int64_t)p.S * d->probs_ld * 4 > 0x7fffffffLL) return LSTC_E_SHAPE;
+    // the forward stores the 16-B groups of a row's 32 T key columns and no others (keys >= S come out as exact zeros), the backward
+    // reads the same groups: a pitch past 32 T would leave columns that neither kernel touches, so it is refused
+    if (d->probs_ld < p.S || d->probs_ld > 32 * ((p.S + 31) / 32) || d->probs_ld % 4) return LSTC_E_SHAPE;
     p.pld = d->probs_ld;
     p.Qi = (const __bf16*)d->Q; p.Ki = (const __bf16*)d->K; p.Vi = (const __bf16*)d->V;
     p.kiq = p.kik = p.kiv = d->in_pack_cols / 32;

@@ -127,7 +127,7 @@ def test_host_side_validation_error_codes(lib):
         p.in_pack_cols, p.K_col0, p.V_col0, p.probs_ld = 768, 256, 512, 52
         p.dO_pack_cols, p.pack_cols, p.dK_col0, p.dV_col0 = 256, 768, 256, 512
         return p
-    for field, value, fwd_rc, bwd_rc in (("dtype", 0, -4, -4), ("probs_ld", 49, -2, -2), ("probs_ld", 48, -2, -2), ("K_col0", 16, -2, -2),
+    for field, value, fwd_rc, bwd_rc in (("dtype", 0, -4, -4), ("probs_ld", 49, -2, -2), ("probs_ld", 48, -2, -2), ("probs_ld", 68, -2, -2), ("K_col0", 16, -2, -2),
                                          ("in_pack_cols", 800, -2, -2), ("V_col0", 640, -2, -2), ("O_pack", None, -1, None),
                                          ("dv", 32, -4, -4), ("S", 97, -4, -4), ("N", 255, -4, -4), ("Q", 4104, -3, -3), ("probs", 4100, -3, -3),
                                          ("dO_pack_cols", 0, None, -2), ("dO_pack_cols", 288, None, -2), ("dO", 4104, None, -3),
