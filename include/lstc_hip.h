@@ -766,6 +766,50 @@ int64_t lstc_auc_workspace_bytes(int64_t n);
 int lstc_auc_weighted(const float* scores, const uint32_t* pos, const uint32_t* neg, int64_t n, void* workspace,
                       int64_t workspace_bytes, LstcAucOut* out, void* stream);
 
+/* The detection report of the same rows (replaces utils/eval_utils.py:16-19, 26-95, 97-122, 145-148 - sklearn's
+ * precision_recall_curve + auc and average_precision_score, the thresholded confusion family, the score statistics and the
+ * per-class table - for passes whose frame scores only repeat row scores).  scores / pos / neg as above; gid[i] < n_groups is the
+ * group (class) of row i, a row with gid[i] >= n_groups belongs to no group and is counted nowhere; gid == NULL puts every row in
+ * group 0 and needs n_groups == 1.  A row with pos == neg == 0 does not exist: its score is never looked at, NaN included.
+ * For every row i that covers a positive frame a pair kernel counts, over the rows j of i's group and in 32-bit integers,
+ *     tp_ge = sum pos[j] [s_j >= s_i],  fp_ge = sum neg[j] [s_j >= s_i],  tp_eq, fp_eq: the same sums under s_j == s_i
+ * (>= and == on the floats: +0.0 and -0.0 tie, a NaN compares false); they do not depend on the launch shape (slices of rows j
+ * meet in integer atomics; no float atomic anywhere).  A finish kernel - one workgroup per group, fixed thread -> row assignment,
+ * fixed reduction tree, so every double below has one summation order - writes out[g], with P = pos, N = neg of the group:
+ *   - u2 = sum pos_i (2 (N - fp_ge) + fp_eq) and auc = (double)u2 / (2.0 * P * N): for an ungrouped call the u2 and the auc bits of
+ *     lstc_auc_weighted; auc is NaN when P == 0 or N == 0;
+ *   - ap = (sum pos_i prec_i) / P, prec_i = tp_ge / (tp_ge + fp_ge): sklearn's average_precision_score of the expanded frames;
+ *   - pr_auc = (sum pos_i (prec_i + prev_i) / 2) / P, prev_i = (tp_ge - tp_eq) / ((tp_ge - tp_eq) + (fp_ge - fp_eq)), 1.0 when that
+ *     denominator is 0 (sklearn's closing point: recall 0, precision 1): the trapezoid area under precision_recall_curve; ap and
+ *     pr_auc are NaN when P == 0; every per-row division is an IEEE double division;
+ *   - tp_at[t] = sum pos_i [s_i > thresholds[t]], fp_at[t] = sum neg_i [s_i > thresholds[t]] (strict, as cal_false_alarm), 0 for
+ *     t >= n_thresholds: with P and N the whole confusion matrix at every threshold;
+ *   - sum_s_pos = sum pos_i s_i, sum_s_neg = sum neg_i s_i, sum_sq_err = sum (pos_i (1 - s_i)^2 + neg_i s_i^2), in double (score
+ *     gap, cal_pAUC, RMSE);
+ *   - flags & LSTC_DET_NAN_SCORE: a row of the group with weight has a NaN score; flags & LSTC_DET_TOO_MANY_FRAMES: P + N > 2^26
+ *     (the bound keeps the 32-bit counts safe).  With a flag every double is NaN; pos, neg, tp_at, fp_at and u2 stay the integers
+ *     of the rows with a real score (pos and neg count the NaN rows too).
+ * All buffers are device memory owned by the caller; `workspace` holds at least lstc_det_workspace_bytes(n, n_groups) =
+ * 16 min(max(n, 1), 2^20) + 16 bytes at any alignment (content unspecified before and after), `out` holds n_groups records and is
+ * 8-byte aligned.  At most one memset node and two launches on `stream`, no allocation, no synchronisation: capturable.
+ * Checked before any launch: a NULL pointer (gid apart) LSTC_E_NULL; n <= 0, n_groups <= 0, n_thresholds outside 1..8, gid NULL
+ * with n_groups != 1, workspace too small LSTC_E_SHAPE; n > 2^20 or n_groups > 64 LSTC_E_RANGE; `out` off an 8-byte boundary
+ * LSTC_E_ALIGN.  The row limit is 2^20, not the AUC's 2^24: the work is quadratic with about twice the AUC kernel's instructions
+ * per pair, 2^20 rows are about 28 of the largest lists scored here, and a call at 2^24 rows would occupy a shared GPU for minutes. */
+typedef struct {
+    uint64_t pos, neg, u2;
+    uint64_t tp_at[8], fp_at[8];
+    double auc, ap, pr_auc, sum_s_pos, sum_s_neg, sum_sq_err;
+    uint32_t flags;
+    uint32_t reserved;
+} LstcDetOut;                           /* 208 bytes */
+#define LSTC_DET_NAN_SCORE 1u
+#define LSTC_DET_TOO_MANY_FRAMES 2u
+int64_t lstc_det_workspace_bytes(int64_t n, int64_t n_groups);
+int lstc_det_report(const float* scores, const uint32_t* pos, const uint32_t* neg, const uint32_t* gid, int64_t n, int64_t n_groups,
+                    const float* thresholds, int32_t n_thresholds, void* workspace, int64_t workspace_bytes, LstcDetOut* out,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------ misc */
 int lstc_version(void);
 const char* lstc_strerror(int code);

@@ -23,6 +23,7 @@ EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
     "lstc_attn_var_fwd", "lstc_attn_var_bwd", "lstc_cls_dot_var", "lstc_cls_wsum_var", "lstc_cls_outer_var", "lstc_cls_concat_var_fwd", "lstc_cls_concat_var_bwd",
     "lstc_cls_concat_span_fwd", "lstc_segment_mean", "lstc_auc_workspace_bytes", "lstc_auc_weighted",
+    "lstc_det_workspace_bytes", "lstc_det_report",
     "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_dot_len", "lstc_cls_wsum",
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
@@ -117,6 +118,17 @@ class AucOut(C.Structure):
 
 AUC_NAN_SCORE, AUC_TOO_MANY_FRAMES = 1, 2
 
+
+class DetOut(C.Structure):
+    """LstcDetOut (include/lstc_hip.h): the 208-byte record of lstc_det_report, one per group."""
+    _fields_ = [("pos", C.c_uint64), ("neg", C.c_uint64), ("u2", C.c_uint64), ("tp_at", C.c_uint64 * 8), ("fp_at", C.c_uint64 * 8),
+                ("auc", C.c_double), ("ap", C.c_double), ("pr_auc", C.c_double), ("sum_s_pos", C.c_double),
+                ("sum_s_neg", C.c_double), ("sum_sq_err", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DET_NAN_SCORE, DET_TOO_MANY_FRAMES = 1, 2
+DET_MAX_ROWS, DET_MAX_GROUPS, DET_MAX_THRESHOLDS = 1 << 20, 64, 8
+
 _lib = None
 
 
@@ -152,6 +164,8 @@ def load():
         "lstc_segment_mean": [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp],
         "lstc_auc_workspace_bytes": [i64],
         "lstc_auc_weighted": [vp, vp, vp, i64, vp, i64, vp, vp],
+        "lstc_det_workspace_bytes": [i64, i64],
+        "lstc_det_report": [vp, vp, vp, vp, i64, i64, vp, i32, vp, i64, vp, vp],
         "lstc_sdpa_fwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_sdpa_bwd": [C.POINTER(SdpaDesc), C.POINTER(AttnMask), vp],
         "lstc_cls_dot": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
@@ -213,6 +227,7 @@ def load():
     lib.lstc_pack3_bytes.restype = C.c_int64
     lib.lstc_pack1_bytes.restype = C.c_int64
     lib.lstc_auc_workspace_bytes.restype = C.c_int64
+    lib.lstc_det_workspace_bytes.restype = C.c_int64
     lib.lstc_sqnorm_multi_scratch.restype = C.c_int64
     lib.lstc_strerror.argtypes = [C.c_int]
     lib.lstc_strerror.restype = C.c_char_p

@@ -140,7 +140,32 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                         "list are built once (pipeline.AucWeights), every evaluation is then one exact weighted pair count over the "
                         "flat score vector (lstc_auc_weighted) and only its 40-byte record comes to the host.  With or without "
                         "--resident_eval")
+    p.add_argument("--report", action="store_true",
+                   help="the detection report of the evaluated test list beside its AUC, computed on the device (implies the "
+                        "--device_auc route; pipeline.ReportWeights, lstc_det_report): after the AUC line rank 0 prints AUC, AP, "
+                        "PR-AUC, the false-alarm rate at 0.5 and the score gap of all frames and, on the UCF-Crime scripts, the "
+                        "per-class lines of the reference's eval_each_part and its mAP.  With or without --resident_eval")
     return p
+
+
+def _report_weights(args, dataset):
+    """--report: the ReportWeights of a test list (UCF-Crime: grouped by the class in the video name), else None."""
+    if not getattr(args, "report", False):
+        return None
+    from .pipeline import ReportWeights, ucf_class
+    return ReportWeights(group_of=ucf_class if dataset == "UCF" else None)
+
+
+def report_lines(weights):
+    """What --report prints after the AUC line: the overall line, then (grouped) eval_each_part's lines and the mAP line."""
+    rep = getattr(weights, "report", None)
+    if rep is None:
+        return []
+    lines = [rep.overall_line()]
+    if rep.names:
+        lines += rep.each_part_lines()
+        lines.append("report: normal FAR {}, mAP {:.6f}".format(rep.normal_far(), rep.mean_ap(13)))
+    return lines
 
 
 def complete_args(script: str, args=None, argv=None) -> Namespace:
@@ -429,6 +454,9 @@ def train(script: str, argv=None, args=None):
             for ln in lines:
                 logger.info(ln)
             if rank == 0:
+                for ln in report_lines(getattr(eval_fn, "report_weights", None)):
+                    logger.info(ln)
+            if rank == 0:
                 logger.info('======================================================================================')
         if args.steps and it >= args.steps:
             break
@@ -587,9 +615,9 @@ def _real_data(script, args, mode, part_len, pseudo_path, dev, rank, world, enc,
             train_set = ResidentSet.from_pairs(data)
     # --device_auc: one AucWeights per pass, filled by the first evaluation and reused by every later one
     test_w = train_w = None
-    if getattr(args, "device_auc", False):
+    if getattr(args, "device_auc", False) or getattr(args, "report", False):
         from .pipeline import AucWeights
-        test_w, train_w = AucWeights(), AucWeights()
+        test_w, train_w = _report_weights(args, dataset) or AucWeights(), AucWeights()
 
     def eval_fn():
         """(test AUC, train AUC) as the script's in-loop evaluation computes them (0 where it does not)."""
@@ -603,6 +631,7 @@ def _real_data(script, args, mode, part_len, pseudo_path, dev, rank, world, enc,
                                            getattr(args, "test_mask_dir", ""), part_len, args.n_patch, args.segment_len,
                                            rank=rank, world=world, resident=train_set, device_auc=train_w)
         return auc_test, auc_train
+    eval_fn.report_weights = test_w              # --report: the loop logs report_lines(test_w) after the AUC lines
     return data, eval_fn
 
 
@@ -762,9 +791,10 @@ def evaluate_cli(script: str, argv=None, args=None):
         test_set = _resident_set(args, dev, args.dataset_path, _list_keys("UCF" if ucf else args.dataset, args.testing_txt),
                                  args.n_patch, ucf)
         torch.cuda.synchronize(); t0 = _time.perf_counter()
-        if getattr(args, "device_auc", False):
+        weights = None
+        if getattr(args, "device_auc", False) or getattr(args, "report", False):
             from .pipeline import AucWeights
-            weights = AucWeights()
+            weights = _report_weights(args, "UCF" if ucf else args.dataset) or AucWeights()
             auc = evaluate_auc(enc, head, "LTN", "UCF" if ucf else args.dataset, args.dataset_path, args.testing_txt, masks,
                                part_len, args.n_patch, seg, resident=test_set, device_auc=weights)
             n_frames = weights.frames
@@ -776,6 +806,8 @@ def evaluate_cli(script: str, argv=None, args=None):
         LAST_RUN.clear()
         LAST_RUN.update(script=script, clips=n_frames // seg, score_s=_time.perf_counter() - t0, world=1)
         print("auc = ", auc)
+        for ln in report_lines(weights):
+            print(ln)
         return auc
     data = SyntheticVideos(2, 1, 1, part_len, args.n_patch, args.d_model, dev, seed=0)
     scores, labels = [], []

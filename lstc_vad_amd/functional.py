@@ -2639,6 +2639,68 @@ def read_auc(record: torch.Tensor):
     return _lib.AucOut.from_buffer_copy(record.cpu().numpy().tobytes())
 
 
+_det_workspaces = {}        # (device index, rows, groups) -> uint8 workspace of lstc_det_report
+_DET_WORDS = C.sizeof(_lib.DetOut) // 8
+
+
+def detection_report(scores: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, gid: Optional[torch.Tensor] = None,
+                     n_groups: int = 1, thresholds=(0.5,), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """AUC, AP, PR-AUC, the confusion counts at ``thresholds`` (1 .. 8 floats, or a float32 device tensor) and the score sums of
+    the frames that repeat row scores, per group of rows (``lstc_det_report``; ``metrics.detection_report_weighted`` is the host
+    statement of the same contract): ``scores`` float32 [n], ``pos`` / ``neg`` / ``gid`` int32 or uint32 [n], contiguous on one
+    HIP device; ``gid`` None: one group of all rows.  Returns the ``n_groups`` 208-byte ``LstcDetOut`` records as an int64
+    [n_groups, 26] device tensor (``out`` when given) without synchronising; ``read_detection_report`` copies them to the host.
+    At most 2^20 rows and 64 groups (ValueError).  The workspace is cached per device, n and n_groups."""
+    if scores.dim() != 1 or scores.dtype != torch.float32 or scores.numel() == 0:
+        raise TypeError(f"detection_report: scores must be float32 [n], n >= 1, got {tuple(scores.shape)} {scores.dtype}")
+    counts = (torch.int32, torch.uint32)
+    ints = [pos, neg] + ([] if gid is None else [gid])
+    if any(t.dtype not in counts or t.shape != scores.shape for t in ints):
+        raise TypeError("detection_report: pos, neg and gid must be int32 or uint32 [n], one per score")
+    n, n_groups = scores.numel(), int(n_groups)
+    if n > _lib.DET_MAX_ROWS:
+        raise ValueError(f"detection_report: {n} rows, lstc_det_report takes at most 2^20 (the work is quadratic)")
+    if not 1 <= n_groups <= _lib.DET_MAX_GROUPS or (gid is None and n_groups != 1):
+        raise ValueError(f"detection_report: n_groups = {n_groups} (1 .. 64; 1 without gid)")
+    if not torch.is_tensor(thresholds):
+        th = [float(t) for t in thresholds]
+        if not 1 <= len(th) <= _lib.DET_MAX_THRESHOLDS:
+            raise ValueError(f"detection_report: 1 .. 8 thresholds, got {len(th)}")
+    elif thresholds.dtype != torch.float32 or thresholds.dim() != 1 or not 1 <= thresholds.numel() <= _lib.DET_MAX_THRESHOLDS:
+        raise TypeError("detection_report: a thresholds tensor must be float32 [1 .. 8]")
+    if not all(t.is_contiguous() for t in [scores] + ints):
+        raise TypeError("detection_report: scores, pos, neg and gid must be contiguous")
+    if not all(t.is_cuda for t in [scores] + ints):
+        raise RuntimeError("lstc_vad_amd: tensor is not on a HIP device; the hot path is HIP-only (no CPU fallback)")
+    if any(t.device != scores.device for t in ints):
+        raise ValueError("detection_report: scores, pos, neg and gid lie on different devices")
+    if not torch.is_tensor(thresholds):
+        thresholds = torch.tensor(th, dtype=torch.float32).to(scores.device)
+    elif thresholds.device != scores.device or not thresholds.is_contiguous():
+        raise ValueError("detection_report: thresholds must be contiguous on the scores' device")
+    lib = _lib.load()
+    key = (scores.device.index, n, n_groups)
+    ws = _det_workspaces.get(key)
+    if ws is None:
+        ws = _det_workspaces[key] = torch.empty((int(lib.lstc_det_workspace_bytes(n, n_groups)),), dtype=torch.uint8, device=scores.device)
+    if out is None:
+        out = torch.empty((n_groups, _DET_WORDS), dtype=torch.int64, device=scores.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n_groups, _DET_WORDS) or not out.is_contiguous() or out.device != scores.device:
+        raise TypeError(f"detection_report: out must be a contiguous int64 [{n_groups}, {_DET_WORDS}] tensor on the scores' device")
+    check(lib.lstc_det_report(dev_ptr(scores), dev_ptr(pos), dev_ptr(neg), None if gid is None else dev_ptr(gid), n, n_groups,
+                              dev_ptr(thresholds), thresholds.numel(), dev_ptr(ws), ws.numel(), dev_ptr(out), stream_ptr()),
+          "lstc_det_report")
+    return out
+
+
+def read_detection_report(record: torch.Tensor):
+    """The records ``detection_report`` returned, on the host (one copy of 208 bytes per group, which waits for the launches) ->
+    a list of ``_lib.DetOut``."""
+    raw = record.cpu().numpy().tobytes()
+    size = C.sizeof(_lib.DetOut)
+    return [_lib.DetOut.from_buffer_copy(raw[k:k + size]) for k in range(0, len(raw), size)]
+
+
 def lengths_arg(lengths, N, S, device):
     """Normalise the ``lengths`` of a padded batch of N sequences with S - 1 token slots: a Python sequence or a CPU tensor is
     range-checked here (ValueError; 1 <= L <= S - 1) and copied to ``device``; a device tensor is taken as it is, without a host

@@ -32,6 +32,12 @@ a pool come from one ``lstc_segment_mean`` launch.  Lists, masks, ``finish`` clo
 a weighted pair count over the rows (``metrics.roc_auc_weighted``).  ``AucWeights`` turns the ``finish`` closures of a pass into the
 per-row counts of label-1 / label-0 frames once; an evaluation is then ``lstc_auc_weighted`` on the flat device vector and 40 bytes
 come back instead of the scores.
+
+**Detection report on the device.**  ``device_auc=ReportWeights(group_of=, thresholds=)``: the same pass, the same return value, and
+``weights.report`` (``metrics.DetectionReport``) holds AUC, AP, PR-AUC, the confusion counts at the thresholds (FAR, precision,
+recall, ...) and the score sums (GAP, RMSE) of all frames and, with ``group_of`` (``ucf_class`` for UCF-Crime), of every class of
+videos - ``eval_each_part``'s table.  ``lstc_det_report`` counts, for every row, the label-1 / label-0 frames at scores >= and ==
+its own over the rows of its class; everything else follows from those integers (``metrics.detection_report_weighted``).
 """
 from __future__ import annotations
 
@@ -447,6 +453,70 @@ class AucWeights:
         if flat.numel() != self.total:
             raise ValueError(f"AucWeights: built for {self.total} score rows, got {flat.numel()}")
         return float(Fn.read_auc(Fn.weighted_auc(flat.contiguous(), self.pos, self.neg)).auc)
+
+
+def ucf_class(name):
+    """The class of a UCF-Crime video: the alphabetic prefix of its name (``Abuse028_x264`` -> ``Abuse``,
+    ``Normal_Videos_003_x264`` -> ``Normal``, ``RoadAccidents001_x264`` -> ``RoadAccidents``); a directory and an extension are
+    dropped first."""
+    base = str(name).replace("\\", "/").split("/")[-1].split(".")[0]
+    k = 0
+    while k < len(base) and base[k].isalpha():
+        k += 1
+    return base[:k]
+
+
+class ReportWeights(AucWeights):
+    """``AucWeights`` whose evaluation is the whole detection report (``lstc_det_report``): handed to ``evaluate_auc`` /
+    ``evaluate_train_auc`` as ``device_auc=``, the pass returns the overall AUC as before and leaves a ``metrics.DetectionReport``
+    in ``self.report`` - AUC, AP, PR-AUC, the confusion counts at ``thresholds`` and the score sums of all frames, and, with
+    ``group_of`` (video name -> class name, e.g. ``ucf_class``), the same per class: ``fill`` maps every flat row to the class of
+    its video, classes numbered in first-seen order (``group_names``).  Two reports per evaluation (all rows; the rows by class),
+    and 208 bytes per record come to the host.  At most 2^20 rows and 64 classes (ValueError before any launch)."""
+    MAX_ROWS, MAX_GROUPS = 1 << 20, 64               # the limits of lstc_det_report (include/lstc_hip.h)
+
+    def __init__(self, group_of=None, thresholds=(0.5,)):
+        super().__init__()
+        self.group_of, self.thresholds = group_of, tuple(float(t) for t in thresholds)
+        if not 1 <= len(self.thresholds) <= 8:
+            raise ValueError(f"ReportWeights: 1 .. 8 thresholds, got {len(self.thresholds)}")
+        self.group_names, self.gid, self.gid_host, self.report = [], None, None, None
+        self._thresholds_dev = None
+
+    def fill(self, board):
+        if int(board.total) > self.MAX_ROWS:
+            raise ValueError(f"ReportWeights: {int(board.total)} score rows, lstc_det_report takes at most 2^20")
+        names, gid = [], None
+        if self.group_of is not None:
+            gid = np.zeros(max(int(board.total), 0), np.int64)
+            for (off, n, _), name in zip(board.items, board.names):
+                cls = self.group_of(name)
+                if cls not in names:
+                    names.append(cls)
+                gid[off:off + n] = names.index(cls)
+            if len(names) > self.MAX_GROUPS:
+                raise ValueError(f"ReportWeights: {len(names)} classes, lstc_det_report takes at most 64")
+        super().fill(board)
+        self.group_names, self.gid_host = names, gid
+        self.gid = None if gid is None else torch.from_numpy(gid.astype(np.int32)).to(board.device)
+        self._thresholds_dev = torch.tensor(self.thresholds, dtype=torch.float32).to(board.device)
+        return self
+
+    def auc(self, flat):
+        """The report of the flat device score vector of the pass (``self.report``); returns its overall AUC."""
+        from . import functional as Fn
+        from .metrics import DetectionReport
+        if flat.numel() != self.total:
+            raise ValueError(f"ReportWeights: built for {self.total} score rows, got {flat.numel()}")
+        flat = flat.contiguous()
+        whole = Fn.detection_report(flat, self.pos, self.neg, thresholds=self._thresholds_dev)
+        parts = None
+        if self.gid is not None and self.group_names:
+            parts = Fn.detection_report(flat, self.pos, self.neg, self.gid, len(self.group_names), self._thresholds_dev)
+        overall = Fn.read_detection_report(whole)[0]
+        groups = Fn.read_detection_report(parts) if parts is not None else []
+        self.report = DetectionReport(overall, groups, self.group_names, self.thresholds)
+        return float(overall.auc)
 
 
 def _device_auc_arg(device_auc, return_frames, what):

@@ -16,7 +16,12 @@ Run on an MI355X:  python tools/resident_eval_time.py --work /tmp/resident_eval 
 ``--device_auc`` measures the device AUC instead (profiles/device_auc.txt): evaluate_auc over the same resident sets with and
 without ``device_auc=`` (one filled pipeline.AucWeights per pass), interleaved; the host tail the flag replaces (the ``.cpu()`` copy
 of the flat score vector, every ``finish`` closure and metrics.roc_auc - the code of ``_ScoreBoard.results`` and ``_auc_of``), timed
-on the same flat vector in the same process; and the event-timed kernel pair of lstc_auc_weighted on the passes' own weights."""
+on the same flat vector in the same process; and the event-timed kernel pair of lstc_auc_weighted on the passes' own weights.
+
+``--report`` measures the detection report (profiles/detection_report.txt): evaluate_auc over the same resident sets with a filled
+pipeline.ReportWeights (13 / 14 classes) against the route that gives the same numbers without it - ``return_frames=True``, then
+the frame-level functions of lstc_vad_amd.metrics on the frames, overall and by class - interleaved; and the event-timed launches
+of lstc_det_report, ungrouped and grouped, beside lstc_auc_weighted on the same rows."""
 import argparse
 import json
 import os
@@ -80,8 +85,8 @@ def _time_arms(arms, warmup, repeats):
     return times, last
 
 
-def _device_auc_report(a, dev, lines, res):
-    """The --device_auc report (see the module docstring)."""
+def _resident_world(a, dev, lines):
+    """The two lists, their models and their resident sets, as the --device_auc and --report arms use them."""
     from lstc_vad_amd.models import Regressor
     sht, sht_counts = _write(a.work, "sht", a.sht_videos, a.sht_clips, 16, False, 1)
     ucf, ucf_counts = _write(a.work, "ucf", a.ucf_videos, a.ucf_clips, 9, True, 2)
@@ -95,6 +100,111 @@ def _device_auc_report(a, dev, lines, res):
             "ucf": pipeline.ResidentSet.from_archive(ucf["feats"], keys(ucf["test"], True), dev, n_patch=9, view=True)}
     lines.append(f"SHT-shaped: {a.sht_videos} videos, {sum(sht_counts)} clips, P = 16, d = {D}, part_len 3; UCF-shaped: {a.ucf_videos} "
                  f"videos, {sum(ucf_counts)} clips, P = 9, 32 bins, part_len 2; both resident (pipeline.ResidentSet)")
+    return sht, ucf, models, sets
+
+
+def _event_time(fn, warm=3, runs=9):
+    """Median seconds of ``fn()`` between two events on the current stream."""
+    ts = []
+    for _ in range(warm + runs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e-3)
+    return statistics.median(ts[warm:])
+
+
+UCF_CLASSES = ["Abuse", "Arrest", "Arson", "Assault", "Burglary", "Explosion", "Fighting", "RoadAccidents", "Robbery", "Shooting",
+               "Shoplifting", "Stealing", "Vandalism"]
+
+
+def _class_of(name):
+    """The timing lists name their abnormal videos Abuse<i> / <scene>_<i>: spread them over 13 classes (plus Normal for UCF), the
+    class count of UCF-Crime and of ShanghaiTech's scenes."""
+    cls = pipeline.ucf_class(name)
+    if not cls:                                   # "<scene>_<i>": the scene
+        return name.split("_")[0]
+    if cls == "Normal":
+        return cls
+    return UCF_CLASSES[int(name[len(cls):len(cls) + 3]) % 13]
+
+
+def _report_arm(a, dev, lines, res):
+    """The --report arm (see the module docstring)."""
+    from lstc_vad_amd import metrics
+    sht, ucf, models, sets = _resident_world(a, dev, lines)
+    lines.append(f"evaluate_auc, medians of {a.repeats} interleaved runs after {a.warmup} warm-up round(s) (min .. max): report = "
+                 "evaluate_auc(resident=, device_auc=ReportWeights(group_of=)) with filled weights - AUC, AP, PR-AUC, FAR, GAP overall and "
+                 "per class on the device; host = what gives the same numbers today: evaluate_auc(resident=, return_frames=True), then "
+                 "cal_AP, cal_pr_auc, cal_false_alarm and cal_score_gap on all frames and eval_each_part on the frames by class "
+                 "(lstc_vad_amd.metrics, numpy)")
+    weights = {}
+    for mode, tag, kind in (("fp32", "sht", "LTN"), ("fp32", "ucf", "LTN"), ("bf16", "sht", "LTN"), ("bf16", "ucf", "LTN"),
+                            ("fp32", "sht", "STN")):
+        W, P, part_len, dataset = (sht, 16, 3, "SHT") if tag == "sht" else (ucf, 9, 2, "UCF")
+        enc, head = models[tag, kind]
+        w = weights.setdefault((tag, kind), pipeline.ReportWeights(group_of=_class_of))
+        Fn.set_compute_dtype(mode)
+        try:
+            ev = lambda **kw: pipeline.evaluate_auc(enc, head, kind, dataset, W["feats"], W["test"], W["masks"], part_len, P,
+                                                    resident=sets[tag], **kw)
+            ev(device_auc=w)                                        # fills the weights: built once, outside the timed runs
+            frame_gid = np.repeat(w.gid_host, w.pos_host + w.neg_host)
+
+            def host():
+                auc, fs, fl = ev(return_frames=True)
+                out = [auc, metrics.cal_AP(fs, fl), metrics.cal_pr_auc(fs, fl), metrics.cal_false_alarm(fs, fl), metrics.cal_score_gap(fs, fl)]
+                labels = {c: fl[frame_gid == k] for k, c in enumerate(w.group_names)}
+                scores = {c: fs[frame_gid == k] for k, c in enumerate(w.group_names)}
+                return out + list(metrics.eval_each_part(labels, scores, logger=_Quiet))
+
+            def report():
+                auc = ev(device_auc=w)
+                r = w.report
+                return [auc, r.overall.ap, r.overall.pr_auc, r.far(), r.gap(), r.normal_far(), r.mean_ap()]
+            times, last = _time_arms({"host": host, "report": report}, a.warmup, a.repeats)
+        finally:
+            Fn.set_compute_dtype("fp32")
+        diff = max(abs(x - y) for x, y in zip(last["host"], last["report"]) if x == x or y == y)
+        row = {"mode": mode, "set": tag, "net": kind, "rows": w.total, "frames": w.frames, "classes": len(w.group_names), "max_diff": diff}
+        for arm in ("host", "report"):
+            row[arm] = {"median_s": statistics.median(times[arm]), "min_s": min(times[arm]), "max_s": max(times[arm])}
+        row["host_over_report"] = row["host"]["median_s"] / row["report"]["median_s"]
+        res["rows"].append(row)
+        ms = lambda r: f"{r['median_s'] * 1e3:8.2f} ms ({r['min_s'] * 1e3:.2f} .. {r['max_s'] * 1e3:.2f})"
+        lines.append(f"  {mode:5s} {tag} {kind} {w.total:6d} rows {w.frames:7d} frames {len(w.group_names):2d} classes | host {ms(row['host'])} | "
+                     f"report {ms(row['report'])} | host / report {row['host_over_report']:.3f} | max |diff| of the 7 numbers {diff:.1e}")
+    # the launches alone, event-timed, on the passes' own weights and classes, next to lstc_auc_weighted on the same rows
+    gen = torch.Generator().manual_seed(5)
+    for what, w in (("UCF parts", weights["ucf", "LTN"]), ("SHT parts", weights["sht", "LTN"]), ("SHT clips", weights["sht", "STN"])):
+        n = w.total
+        sc = torch.rand(n, generator=gen).to(dev)
+        th = torch.tensor([0.5], dtype=torch.float32).to(dev)
+        one = Fn.detection_report(sc, w.pos, w.neg, thresholds=th)
+        many = Fn.detection_report(sc, w.pos, w.neg, w.gid, len(w.group_names), th)
+        auc = Fn.weighted_auc(sc, w.pos, w.neg)
+        t_one = _event_time(lambda: Fn.detection_report(sc, w.pos, w.neg, thresholds=th, out=one))
+        t_many = _event_time(lambda: Fn.detection_report(sc, w.pos, w.neg, w.gid, len(w.group_names), th, out=many))
+        t_auc = _event_time(lambda: Fn.weighted_auc(sc, w.pos, w.neg, out=auc))
+        busy = int((np.add.reduceat(w.pos_host, np.arange(0, n, 256)) > 0).sum())
+        pairs = busy * 256 * n
+        res["rows"].append({"kernel": "lstc_det_report", "shape": what, "n": n, "ungrouped_us": t_one * 1e6, "grouped_us": t_many * 1e6,
+                            "classes": len(w.group_names), "lstc_auc_weighted_us": t_auc * 1e6, "row_blocks_with_positives": busy})
+        lines.append(f"  lstc_det_report, {what:9s}: n = {n:6d}, {busy} of {(n + 255) // 256} blocks of 256 rows hold a positive frame: "
+                     f"{t_one * 1e6:.1f} us ungrouped ({pairs / t_one * 1e-12:.2f} T pairs/s), {t_many * 1e6:.1f} us in {len(w.group_names)} "
+                     f"classes; lstc_auc_weighted on the same rows {t_auc * 1e6:.1f} us (memset + two launches / two launches, event-timed, "
+                     "medians of 9)")
+
+
+class _Quiet:
+    info = staticmethod(lambda line: None)
+
+
+def _device_auc_report(a, dev, lines, res):
+    """The --device_auc report (see the module docstring)."""
+    sht, ucf, models, sets = _resident_world(a, dev, lines)
     lines.append(f"evaluate_auc, medians of {a.repeats} interleaved runs after {a.warmup} warm-up round(s) (min .. max): resident = "
                  "evaluate_auc(resident=) as it stands, + device_auc = the same call with a filled AucWeights; host tail = .cpu() of the "
                  "flat vector + every finish closure + metrics.roc_auc, on the pass's own flat vector, same process")
@@ -180,6 +290,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--device_auc", action="store_true", help="the device-AUC report instead (profiles/device_auc.txt)")
+    ap.add_argument("--report", action="store_true", help="the detection-report arm instead (profiles/detection_report.txt)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("resident_eval_time.py measures on the GPU: no device found")
@@ -190,6 +301,9 @@ def main():
     try:
         if a.device_auc:
             _device_auc_report(a, dev, lines, res)
+            return _finish(a, lines, res)
+        if a.report:
+            _report_arm(a, dev, lines, res)
             return _finish(a, lines, res)
         sht, sht_counts = _write(a.work, "sht", a.sht_videos, a.sht_clips, 16, False, 1)
         ucf, ucf_counts = _write(a.work, "ucf", a.ucf_videos, a.ucf_clips, 9, True, 2)
