@@ -335,6 +335,25 @@ typedef struct LstcSeqs {
 int lstc_attn_var_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
 int lstc_attn_var_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
 
+/* The same over sequences of up to 512 tokens: 128 < d->S <= 512, d->S again the longest sequence of the call.  Everything the
+ * comment above says about the offsets (row0, prob0, seq_ids), the ragged probabilities, the bias of a shorter sequence, the dropout
+ * counter prob0[n] + (h*S_n + i)*S_n + j (lstc_dropout_mask() over the ragged buffer regenerates the mask), the partial bias tables
+ * [dtable_chunks, table_rows, H] without float atomics and d->N holds here too.  One writer per output element; its value depends
+ * neither on the bucketing nor on the other sequences of the batch.
+ *   Structure and arithmetic are those of the key-tiled kernels (csrc/attention_long.hip, attn_long_fwd_kernel / attn_long_bwd_kernel
+ *   with VAR): exact-f32 products in every dtype, no mask, with their preconditions: d_k and d_v multiples of 16, row operands and
+ *   outputs, 32-bit offsets within a sequence (d->S * the largest row pitch < 2^31).  Forward: one wave per (sequence, head, 32-query
+ *   block) with the block count of d->S; the waves behind a shorter sequence's end return at once.  Backward: one workgroup per
+ *   (chunk of the call's sequences, head), every pass on the sequence's own S_n.  S_n is clamped to [1, 32 * ceil(d->S / 32)]; a
+ *   sequence of any length in that range is computed correctly, and callers that want a sequence's bits to be a function of S_n
+ *   alone send those of at most 128 tokens to lstc_attn_var_fwd / _bwd (functional.SeqLayout does).
+ * Checked before any launch: d, s, row0, prob0, Q, K, V, probs, O (forward), dO / dQ / dK / dV (backward) NULL: LSTC_E_NULL; any
+ * packed operand or output of the descriptor: LSTC_E_UNSUPPORTED; d->S <= 128, d->S > 512, d_k or d_v not a multiple of 16, or
+ * n_probs > 2^32 - 1: LSTC_E_RANGE; n_ids <= 0, n_probs < 0 or a chunk count that does not match dtable_chunks: LSTC_E_SHAPE; dtable
+ * non-NULL with dtable_chunks <= 0: LSTC_E_UNSUPPORTED.  lstc_attn_var_fwd / _bwd keep refusing d->S > 128. */
+int lstc_attn_var_long_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
+int lstc_attn_var_long_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream);
+
 /* Rectangular attention (reference models/MultiHeadAttention.py:17-23, class ScaledDotProductAttention): the queries and the
  * keys have lengths of their own and there is no relative bias (csrc/attention_x.hip).
  *   A = (Q scale) K^T [N, H, Sq, Sk] ; A = mask byte == 0 ? -1e9f : A (m non-NULL) ; P = softmax(A, -1) ; Pd = dropout(P) ;

@@ -21,7 +21,7 @@ EPI_OUT_PACK, EPI_RELU_MASK_PACK, EPI_RESIDUAL_PACK = 128, 256, 512
 
 EXPORTS = (
     "lstc_gemm", "lstc_attn_fwd", "lstc_attn_bwd", "lstc_attn_cls_fwd", "lstc_attn_cls_bwd",
-    "lstc_attn_var_fwd", "lstc_attn_var_bwd", "lstc_cls_dot_var", "lstc_cls_wsum_var", "lstc_cls_outer_var", "lstc_cls_concat_var_fwd", "lstc_cls_concat_var_bwd",
+    "lstc_attn_var_fwd", "lstc_attn_var_bwd", "lstc_attn_var_long_fwd", "lstc_attn_var_long_bwd", "lstc_cls_dot_var", "lstc_cls_wsum_var", "lstc_cls_outer_var", "lstc_cls_concat_var_fwd", "lstc_cls_concat_var_bwd",
     "lstc_cls_concat_span_fwd", "lstc_segment_mean", "lstc_auc_workspace_bytes", "lstc_auc_weighted",
     "lstc_det_workspace_bytes", "lstc_det_report",
     "lstc_attn_fwd_masked", "lstc_attn_bwd_masked", "lstc_attn_cls_fwd_masked", "lstc_attn_cls_bwd_masked", "lstc_sdpa_fwd", "lstc_sdpa_bwd", "lstc_sdpa_few_query_max", "lstc_cls_dot", "lstc_cls_dot_len", "lstc_cls_wsum",
@@ -155,6 +155,8 @@ def load():
         "lstc_attn_cls_bwd_masked": [C.POINTER(AttnDesc), C.POINTER(AttnMask), vp],
         "lstc_attn_var_fwd": [C.POINTER(AttnDesc), C.POINTER(Seqs), vp],
         "lstc_attn_var_bwd": [C.POINTER(AttnDesc), C.POINTER(Seqs), vp],
+        "lstc_attn_var_long_fwd": [C.POINTER(AttnDesc), C.POINTER(Seqs), vp],
+        "lstc_attn_var_long_bwd": [C.POINTER(AttnDesc), C.POINTER(Seqs), vp],
         "lstc_cls_dot_var": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp],
         "lstc_cls_wsum_var": [vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "lstc_cls_outer_var": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],

@@ -176,9 +176,6 @@ __device__ __forceinline__ void lds_times_rows(const float* __restrict__ Alds, c
     }
 }
 
-__device__ __forceinline__ int seq_count(const SeqParams& sq) { return sq.n_ids; }
-__device__ __forceinline__ int seq_count(const NoSeqs&) { return 0; }
-
 // First-generation kernels (S <= 128), forward and backward.
 // MASKED: where the mask byte of (n, h, i, j) is 0 the scaled logit is replaced by ATTN_MASK_FILL before the bias is added; in the
 // backward the saved P carries the mask already, so dV and the row sums do not change.  The unmasked instantiation compiles to
@@ -1088,10 +1085,11 @@ int attn_bwd(const LstcAttnDesc* d, const MaskParams* mk, hipStream_t st) {
 
 // Attention over sequence offsets (lstc_attn_var_fwd / _bwd): the checks shared by both, all ahead of any launch.  The descriptor
 // is filled as for one sequence of d->S tokens (its N does not enter: the probabilities are addressed through prob0).
-int fill_var(const LstcAttnDesc* d, const LstcSeqs* s, AttnParams& p, SeqParams& sq, bool bwd) {
+// key_tiled (lstc_attn_var_long_fwd / _bwd): 128 < d->S <= 512 and d_k, d_v multiples of 16 instead of d->S <= 128.
+int fill_var(const LstcAttnDesc* d, const LstcSeqs* s, AttnParams& p, SeqParams& sq, bool bwd, bool key_tiled = false) {
     if (!d || !s || !s->row0 || !s->prob0) return LSTC_E_NULL;
     if (d->O_pack || d->dQ_pack || d->dK_pack || d->dV_pack || d->in_pack_cols > 0 || d->dO_pack_cols > 0) return LSTC_E_UNSUPPORTED;
-    if (d->S > 128) return LSTC_E_RANGE;
+    if (key_tiled ? (d->S <= 128 || d->S > 512 || d->dk % 16 || d->dv % 16) : d->S > 128) return LSTC_E_RANGE;
     if (s->n_ids <= 0 || s->n_probs < 0) return LSTC_E_SHAPE;
     if ((uint64_t)s->n_probs > 0xffffffffull) return LSTC_E_RANGE;      // 32-bit dropout counters = offsets in the ragged buffer
     LstcAttnDesc one = *d;
@@ -1155,6 +1153,21 @@ extern "C" {
 
 int lstc_attn_var_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) { return attn_var_fwd(d, s, (hipStream_t)stream); }
 int lstc_attn_var_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) { return attn_var_bwd(d, s, (hipStream_t)stream); }
+
+// 128 < d->S <= 512: the key-tiled kernels over the same offset tables (csrc/attention_long.hip)
+int lstc_attn_var_long_fwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) {
+    AttnParams p;
+    SeqParams sq;
+    const int rc = fill_var(d, s, p, sq, false, true);
+    return rc ? rc : attn_long_var_fwd_launch(d, p, sq, (hipStream_t)stream);
+}
+
+int lstc_attn_var_long_bwd(const LstcAttnDesc* d, const LstcSeqs* s, void* stream) {
+    AttnParams p;
+    SeqParams sq;
+    const int rc = fill_var(d, s, p, sq, true, true);
+    return rc ? rc : attn_long_var_bwd_launch(d, p, sq, (hipStream_t)stream);
+}
 
 int lstc_attn_fwd(const LstcAttnDesc* d, void* stream) { return attn_fwd(d, nullptr, (hipStream_t)stream); }
 int lstc_attn_bwd(const LstcAttnDesc* d, void* stream) { return attn_bwd(d, nullptr, (hipStream_t)stream); }

@@ -54,8 +54,9 @@ constexpr float ATTN_MASK_FILL = -1e9f;
 
 // Sequence offsets of the *_var entry points (LstcSeqs): the tokens of all sequences lie back to back in [M, ld] matrices, sequence
 // n = rows row0[n] .. row0[n + 1] - 1, its probabilities H * S_n * S_n floats from prob0[n]; a launch covers the n_ids sequences
-// ids[0 .. n_ids) (ids null: 0 .. n_ids - 1).  The third argument of the first-generation kernel bodies is a SeqArg<VAR>, empty for
-// the fixed-S kernels, whose code then holds no trace of it (`if constexpr (VAR)`).
+// ids[0 .. n_ids) (ids null: 0 .. n_ids - 1).  The third argument of the first-generation kernel bodies (S_n <= 128) and of the
+// key-tiled ones (csrc/attention_long.hip, S_n <= 512) is a SeqArg<VAR>, empty for the fixed-S kernels, whose code then holds no
+// trace of it (`if constexpr (VAR)`, or the overloads below that fold to the fixed-S value).
 struct SeqParams {
     const int32_t* row0;
     const int64_t* prob0;
@@ -65,6 +66,16 @@ struct SeqParams {
 struct NoSeqs {};
 template <bool VAR>
 using SeqArg = std::conditional_t<VAR, SeqParams, NoSeqs>;
+// sequences of the launch, spelled so that the fixed-S instantiation compiles too (it never reads the value)
+__device__ __forceinline__ int seq_count(const SeqParams& sq) { return sq.n_ids; }
+__device__ __forceinline__ int seq_count(const NoSeqs&) { return 0; }
+// sequence of position `it` of the launch, its length clamped to [1, cap] and its first row
+__device__ __forceinline__ int seq_id(const SeqParams& sq, int it) { return sq.ids ? sq.ids[it] : it; }
+__device__ __forceinline__ int seq_id(const NoSeqs&, int it) { return it; }
+__device__ __forceinline__ int seq_len(const SeqParams& sq, int n, int cap) { return min(max(sq.row0[n + 1] - sq.row0[n], 1), cap); }
+__device__ __forceinline__ int seq_len(const NoSeqs&, int, int) { return 0; }
+__device__ __forceinline__ size_t seq_row0(const SeqParams& sq, int n) { return (size_t)sq.row0[n]; }
+__device__ __forceinline__ size_t seq_row0(const NoSeqs&, int) { return 0; }
 
 typedef __bf16 attn_h8 __attribute__((ext_vector_type(8)));
 typedef float attn_f2 __attribute__((ext_vector_type(2)));
@@ -82,6 +93,9 @@ __attribute__((visibility("hidden"))) int attn3f_fwd_launch(const AttnParams& p,
 // entry points (the masked instantiations of the same kernels), null for none
 __attribute__((visibility("hidden"))) int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams* mk, hipStream_t st);
 __attribute__((visibility("hidden"))) int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams* mk, hipStream_t st);
+// the same kernels over sequence offsets (their VAR instantiations, exact-f32 products, no mask), behind lstc_attn_var_long_fwd / _bwd
+__attribute__((visibility("hidden"))) int attn_long_var_fwd_launch(const LstcAttnDesc* d, AttnParams& p, const SeqParams& sq, hipStream_t st);
+__attribute__((visibility("hidden"))) int attn_long_var_bwd_launch(const LstcAttnDesc* d, AttnParams& p, const SeqParams& sq, hipStream_t st);
 
 // Host side: launch a kernel that asks for more than 64 KB of dynamic LDS.  The opt-in (MAX_LDS bytes; 160 KB = the whole LDS of a
 // CU) is a per-device attribute of the kernel: set once per device and kernel instantiation, ahead of its first launch there.

@@ -136,21 +136,40 @@ __device__ __forceinline__ void zero_acc(floatx16 (&acc)[DT]) {
 
 // MASKED: the mask (attention_common.h MaskParams) as the second argument; the unmasked instantiation compiles to what the kernel
 // was before masks existed (tools/isa_diff.py).
-template <bool BF, int DT, bool MASKED>
-__global__ void __launch_bounds__(LNT, DT == 8 ? 1 : 2) attn_long_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+// VAR (lstc_attn_var_long_fwd / _bwd): the sequence, its length and its operand rows come from the offset tables of `sq` (the
+// third argument, attention_common.h SeqParams; empty for the fixed-S kernels, which compile to what they were without it) -
+// sequence n = rows row0[n] .. row0[n + 1] - 1, its probabilities [H, S_n, S_n] from prob0[n], which is also the dropout counter
+// of its first element.  S_n is clamped to [1, 32 ceil(p.S / 32)]; the query and key block counts are the sequence's own.  The
+// forward's jobs are (sequence, head, query block) with the block count of p.S, the longest sequence of the launch: a wave whose
+// block lies behind its sequence's end returns at once (there is no block barrier to miss).
+template <bool BF, int DT, bool MASKED, bool VAR = false>
+__global__ void __launch_bounds__(LNT, DT == 8 ? 1 : 2) attn_long_fwd_kernel(const AttnParams p, const MaskArg<MASKED> mk, const SeqArg<VAR> sq) {
     const DropKey dkn = drop_key_now(p.dkey);
     __shared__ float trs[LNW][32 * TLD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h2 = lane >> 5;
-    const int S = p.S, QT = (S + 31) >> 5, KT = QT;
+    int S = p.S;
+    const int QTL = (S + 31) >> 5;                    // query blocks per (sequence, head) of the launch
     const uint32_t job = blockIdx.x * LNW + wave;
-    if (job >= (uint32_t)p.N * (uint32_t)p.H * (uint32_t)QT) return;      // no block barrier in this kernel
-    const int qt = (int)(job % (uint32_t)QT);
-    const uint32_t nh = job / (uint32_t)QT;
-    const int h = (int)(nh % (uint32_t)p.H), n = (int)(nh / (uint32_t)p.H);
-    const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-    const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-    const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-    float* Ob = p.O + (size_t)n * S * p.ldo + (size_t)h * p.dv;
+    if (job >= (uint32_t)(VAR ? seq_count(sq) : p.N) * (uint32_t)p.H * (uint32_t)QTL) return;      // no block barrier in this kernel
+    const int qt = (int)(job % (uint32_t)QTL);
+    const uint32_t nh = job / (uint32_t)QTL;
+    const int h = (int)(nh % (uint32_t)p.H);
+    int n = (int)(nh / (uint32_t)p.H);
+    size_t r0;                                        // the sequence's first row
+    if constexpr (VAR) {
+        if (sq.ids) n = sq.ids[n];
+        const int b = sq.row0[n];
+        S = min(max(sq.row0[n + 1] - b, 1), 32 * QTL);
+        if (32 * qt >= S) return;                     // a block behind the end of a shorter sequence
+        r0 = (size_t)b;
+    } else {
+        r0 = (size_t)n * S;
+    }
+    const int QT = (S + 31) >> 5, KT = QT;
+    const float* Qb = p.Q + r0 * p.ldq + (size_t)h * p.dk;
+    const float* Kb = p.K + r0 * p.ldk + (size_t)h * p.dk;
+    const float* Vb = p.V + r0 * p.ldv + (size_t)h * p.dv;
+    float* Ob = p.O + r0 * p.ldo + (size_t)h * p.dv;
     float* tr = trs[wave];
     const int q = 32 * qt + c;                        // this lane's query
     const bool bias = p.index_ld > 0 && q >= 1 && q < S;
@@ -214,8 +233,16 @@ __global__ void __launch_bounds__(LNT, DT == 8 ? 1 : 2) attn_long_fwd_kernel(con
         m = mn;
     }
 
-    float* pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
-    const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    float* pr_base;
+    uint32_t flat0;
+    if constexpr (VAR) {
+        const int64_t e0 = sq.prob0[n] + (int64_t)h * S * S;
+        pr_base = p.probs + e0;
+        flat0 = (uint32_t)e0;
+    } else {
+        pr_base = p.probs + ((size_t)n * p.H + h) * S * S;
+        flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    }
     // sweep 2 (once per group of up to 32 DT output columns): normalised P, its dropout, O += Pd V
 #pragma unroll 1
     for (int g0 = 0; g0 < p.dv; g0 += 32 * DT) {
@@ -250,29 +277,43 @@ __global__ void __launch_bounds__(LNT, DT == 8 ? 1 : 2) attn_long_fwd_kernel(con
     }
 }
 
-template <bool BF, int DT, bool MASKED>
-__global__ void __launch_bounds__(LNT, 1) attn_long_bwd_kernel(const AttnParams p, const MaskArg<MASKED> mk) {
+// VAR: one workgroup per (chunk of the call's n_ids sequences, head) as the fixed form; the row sums in Dr, the barriers and the four
+// passes run per sequence on its own S_n, and the bias-table gradient leaves as one partial table per chunk (as it always does here).
+template <bool BF, int DT, bool MASKED, bool VAR = false>
+__global__ void __launch_bounds__(LNT, 1) attn_long_bwd_kernel(const AttnParams p, const MaskArg<MASKED> mk, const SeqArg<VAR> sq) {
     const DropKey dkn = drop_key_now(p.dkey);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h2 = lane >> 5;
     float* Dr = sm;                                       // [LMAXS] rowsum(dP' * P) of the current sequence
     float* tr = sm + LMAXS + wave * 32 * TLD;             // this wave's transpose image
     float* tacc = sm + LMAXS + LNW * 32 * TLD;            // [LNW][table_rows] bias-table gradient, one copy per wave
-    const int h = (int)blockIdx.y, S = p.S, QT = (S + 31) >> 5, KT = QT;
+    const int h = (int)blockIdx.y, SL = p.S, QTL = (SL + 31) >> 5;          // the launch's S and block count; VAR: each sequence's own below
     const bool has_bias = p.index_ld > 0 && p.dtable != nullptr;
     if (has_bias)
         for (int i = threadIdx.x; i < LNW * p.table_rows; i += LNT) tacc[i] = 0.f;
     float* const tw = tacc + wave * p.table_rows;
     const int n_begin = (int)blockIdx.x * p.n_per_wg;
-    const int n_end = min(p.N, n_begin + p.n_per_wg);
+    const int n_end = min(VAR ? seq_count(sq) : p.N, n_begin + p.n_per_wg);
 #pragma unroll 1
-    for (int n = n_begin; n < n_end; ++n) {
-        const float* Qb = p.Q + (size_t)n * S * p.ldq + (size_t)h * p.dk;
-        const float* Kb = p.K + (size_t)n * S * p.ldk + (size_t)h * p.dk;
-        const float* Vb = p.V + (size_t)n * S * p.ldv + (size_t)h * p.dv;
-        const float* dOb = p.dO + (size_t)n * S * p.ldo + (size_t)h * p.dv;
-        const float* Pb = p.probs + ((size_t)n * p.H + h) * S * S;
-        const uint32_t flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+    for (int it = n_begin; it < n_end; ++it) {
+        const int n = seq_id(sq, it);
+        const int S = VAR ? seq_len(sq, n, 32 * QTL) : SL;
+        const int QT = VAR ? (S + 31) >> 5 : QTL, KT = QT;
+        const size_t r0 = VAR ? seq_row0(sq, n) : (size_t)n * S;          // the sequence's first row
+        const float* Qb = p.Q + r0 * p.ldq + (size_t)h * p.dk;
+        const float* Kb = p.K + r0 * p.ldk + (size_t)h * p.dk;
+        const float* Vb = p.V + r0 * p.ldv + (size_t)h * p.dv;
+        const float* dOb = p.dO + r0 * p.ldo + (size_t)h * p.dv;
+        const float* Pb;
+        uint32_t flat0;
+        if constexpr (VAR) {
+            const int64_t e0 = sq.prob0[n] + (int64_t)h * S * S;
+            Pb = p.probs + e0;
+            flat0 = (uint32_t)e0;
+        } else {
+            Pb = p.probs + ((size_t)n * p.H + h) * S * S;
+            flat0 = ((uint32_t)n * p.H + h) * (uint32_t)(S * S);
+        }
         const uint8_t* mk_nh = nullptr;
         if constexpr (MASKED) mk_nh = mk.m + (int64_t)n * mk.sn + (int64_t)h * mk.sh;
         // masked only.  bit r: the mask keeps (query of register r, this lane's key) - read with P's lane order, one 32-byte run per query row
@@ -364,7 +405,7 @@ __global__ void __launch_bounds__(LNT, 1) attn_long_bwd_kernel(const AttnParams 
                     }
                     acc_xtb<BF, DT>(acc, pd, dOb, p.ldo, 32 * qt, S, g0, p.dv);
                 }
-                store_acc<DT>(acc, p.dV + (size_t)n * S * p.ldv + (size_t)h * p.dv, p.ldv, 32 * kt, S, g0, p.dv, 1.f);
+                store_acc<DT>(acc, p.dV + r0 * p.ldv + (size_t)h * p.dv, p.ldv, 32 * kt, S, g0, p.dv, 1.f);
             }
 #pragma unroll 1
             for (int g0 = 0; g0 < p.dk; g0 += 32 * DT) {
@@ -381,7 +422,7 @@ __global__ void __launch_bounds__(LNT, 1) attn_long_bwd_kernel(const AttnParams 
                     }
                     acc_xtb<BF, DT>(acc, da, Qb, p.ldq, 32 * qt, S, g0, p.dk);
                 }
-                store_acc<DT>(acc, p.dK + (size_t)n * S * p.ldk + (size_t)h * p.dk, p.ldk, 32 * kt, S, g0, p.dk, p.scale);
+                store_acc<DT>(acc, p.dK + r0 * p.ldk + (size_t)h * p.dk, p.ldk, 32 * kt, S, g0, p.dk, p.scale);
             }
         }
 
@@ -427,7 +468,7 @@ __global__ void __launch_bounds__(LNT, 1) attn_long_bwd_kernel(const AttnParams 
                     __builtin_amdgcn_wave_barrier();
                     acc_xtb<BF, DT>(acc, dat, Kb, p.ldk, 32 * kt, S, g0, p.dk);
                 }
-                store_acc<DT>(acc, p.dQ + (size_t)n * S * p.ldq + (size_t)h * p.dk, p.ldq, 32 * qt, S, g0, p.dk, p.scale);
+                store_acc<DT>(acc, p.dQ + r0 * p.ldq + (size_t)h * p.dk, p.ldq, 32 * qt, S, g0, p.dk, p.scale);
             }
         }
     }
@@ -472,14 +513,14 @@ int attn_long_fwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams*
     auto go = [&](auto masked, const auto& mask_arg) {          // static LDS only
         constexpr bool M = decltype(masked)::value;
         switch (dt) {
-            case 1: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 1, M>), grid, LNT, 0, st, p, mask_arg);
-                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 1, M>), grid, LNT, 0, st, p, mask_arg); break;
-            case 2: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 2, M>), grid, LNT, 0, st, p, mask_arg);
-                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 2, M>), grid, LNT, 0, st, p, mask_arg); break;
-            case 4: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 4, M>), grid, LNT, 0, st, p, mask_arg);
-                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 4, M>), grid, LNT, 0, st, p, mask_arg); break;
-            default: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 8, M>), grid, LNT, 0, st, p, mask_arg);
-                     else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 8, M>), grid, LNT, 0, st, p, mask_arg); break;
+            case 1: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 1, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{});
+                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 1, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{}); break;
+            case 2: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 2, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{});
+                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 2, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{}); break;
+            case 4: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 4, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{});
+                    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 4, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{}); break;
+            default: if (bf) hipLaunchKernelGGL((attn_long_fwd_kernel<true, 8, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{});
+                     else hipLaunchKernelGGL((attn_long_fwd_kernel<false, 8, M>), grid, LNT, 0, st, p, mask_arg, NoSeqs{}); break;
         }
     };
     if (mk) go(std::true_type{}, *mk); else go(std::false_type{}, NoMask{});
@@ -506,17 +547,62 @@ int attn_long_bwd_launch(const LstcAttnDesc* d, AttnParams& p, const MaskParams*
     auto go = [&](auto masked, const auto& mask_arg) {
         constexpr bool M = decltype(masked)::value;
         switch (dt) {
-            case 1: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 1, M>>(grid, LNT, lds, st, p, mask_arg);
-                    else launch_big_lds<attn_long_bwd_kernel<false, 1, M>>(grid, LNT, lds, st, p, mask_arg); break;
-            case 2: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 2, M>>(grid, LNT, lds, st, p, mask_arg);
-                    else launch_big_lds<attn_long_bwd_kernel<false, 2, M>>(grid, LNT, lds, st, p, mask_arg); break;
-            case 4: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 4, M>>(grid, LNT, lds, st, p, mask_arg);
-                    else launch_big_lds<attn_long_bwd_kernel<false, 4, M>>(grid, LNT, lds, st, p, mask_arg); break;
-            default: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 8, M>>(grid, LNT, lds, st, p, mask_arg);
-                     else launch_big_lds<attn_long_bwd_kernel<false, 8, M>>(grid, LNT, lds, st, p, mask_arg); break;
+            case 1: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 1, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{});
+                    else launch_big_lds<attn_long_bwd_kernel<false, 1, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 2: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 2, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{});
+                    else launch_big_lds<attn_long_bwd_kernel<false, 2, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{}); break;
+            case 4: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 4, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{});
+                    else launch_big_lds<attn_long_bwd_kernel<false, 4, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{}); break;
+            default: if (bf) launch_big_lds<attn_long_bwd_kernel<true, 8, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{});
+                     else launch_big_lds<attn_long_bwd_kernel<false, 8, M>>(grid, LNT, lds, st, p, mask_arg, NoSeqs{}); break;
         }
     };
     if (mk) go(std::true_type{}, *mk); else go(std::false_type{}, NoMask{});
+    return lstc_launch_status();
+}
+
+// The key-tiled kernels over sequence offsets (lstc_attn_var_long_fwd / _bwd; fill_var has run): exact-f32 products only - the
+// unpadded route runs exact f32 in every compute mode, and the bf16 products are slower above S = 128 anyway - and no mask.
+// Forward: skipped-wave jobs, no device job table.  A launch group holds the sequences above 128 tokens only (functional.SeqLayout),
+// so a job table could spare no more than the waves between a sequence's own block count and the group's, which return after two
+// scalar loads; the table would cost a host pass and an upload per layout.
+int attn_long_var_fwd_launch(const LstcAttnDesc* d, AttnParams& p, const SeqParams& sq, hipStream_t st) {
+    int rc = long_check(d, false);
+    if (rc) return rc;
+    const int QT = (p.S + 31) / 32;
+    const uint64_t waves = (uint64_t)sq.n_ids * p.H * QT;
+    if (waves > 0xffffffffull) return LSTC_E_RANGE;          // 32-bit job numbers
+    const dim3 grid((unsigned)((waves + LNW - 1) / LNW));
+    switch (long_dt(p.dk, p.dv)) {
+        case 1: hipLaunchKernelGGL((attn_long_fwd_kernel<false, 1, false, true>), grid, LNT, 0, st, p, NoMask{}, sq); break;
+        case 2: hipLaunchKernelGGL((attn_long_fwd_kernel<false, 2, false, true>), grid, LNT, 0, st, p, NoMask{}, sq); break;
+        case 4: hipLaunchKernelGGL((attn_long_fwd_kernel<false, 4, false, true>), grid, LNT, 0, st, p, NoMask{}, sq); break;
+        default: hipLaunchKernelGGL((attn_long_fwd_kernel<false, 8, false, true>), grid, LNT, 0, st, p, NoMask{}, sq); break;
+    }
+    return lstc_launch_status();
+}
+
+int attn_long_var_bwd_launch(const LstcAttnDesc* d, AttnParams& p, const SeqParams& sq, hipStream_t st) {
+    int rc = long_check(d, true);
+    if (rc) return rc;
+    const bool has_table = d->index_ld > 0 && d->dtable;
+    if (has_table && d->table_rows <= 0) return LSTC_E_SHAPE;
+    if (has_table && d->dtable_chunks <= 0) return LSTC_E_UNSUPPORTED;       // partial tables only: no float atomics
+    p.table_rows = has_table ? d->table_rows : 0;
+    p.table_partials = 1;
+    const size_t lds = ((size_t)LMAXS + (size_t)LNW * 32 * TLD + (size_t)LNW * p.table_rows) * sizeof(float);
+    if (lds > 160 * 1024) return LSTC_E_RANGE;
+    const int npw = has_table ? (sq.n_ids + d->dtable_chunks - 1) / d->dtable_chunks : 1;
+    const int chunks = (sq.n_ids + npw - 1) / npw;
+    if (has_table && chunks != d->dtable_chunks) return LSTC_E_SHAPE;
+    p.n_per_wg = npw;
+    const dim3 grid((unsigned)chunks, (unsigned)p.H);
+    switch (long_dt(p.dk, p.dv)) {
+        case 1: launch_big_lds<attn_long_bwd_kernel<false, 1, false, true>>(grid, LNT, lds, st, p, NoMask{}, sq); break;
+        case 2: launch_big_lds<attn_long_bwd_kernel<false, 2, false, true>>(grid, LNT, lds, st, p, NoMask{}, sq); break;
+        case 4: launch_big_lds<attn_long_bwd_kernel<false, 4, false, true>>(grid, LNT, lds, st, p, NoMask{}, sq); break;
+        default: launch_big_lds<attn_long_bwd_kernel<false, 8, false, true>>(grid, LNT, lds, st, p, NoMask{}, sq); break;
+    }
     return lstc_launch_status();
 }
 

@@ -1238,6 +1238,9 @@ def attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, p_drop, seed, ou
 
 
 UNPADDED_MAX_TOKENS = 128      # S_n = L_n + 1 of the unpadded route: the LDS tile of the first-generation attention kernels
+# asked for by name (``max_tokens=``, ``ragged="unpadded_long"``): the key-tiled offset kernels (lstc_attn_var_long_fwd / _bwd) take
+# the sequences above 128 tokens of such a batch, the first-generation ones the rest
+UNPADDED_LONG_MAX_TOKENS = 512
 # 1: one attention launch per tile count T = ceil(S_n / 32) present in the batch, each over a device list of its sequences, instead of
 # ONE launch instantiated for the longest sequence.  Same bits either way.  Measured on the scoring workload of tools/unpadded_time.py
 # (forward only, T <= 2): 136.64 ms bucketed against 136.85 ms single, inside the spread - so the single launch is the default
@@ -1249,8 +1252,8 @@ class SeqLayout:
     ``lengths[n]`` patch tokens, ``S[n] = lengths[n] + 1`` tokens with the CLS token.  ``in0`` [N + 1]: first row of each sequence
     in the input [sum L, d]; ``row0`` [N + 1]: in the activations [M, d], ``M = sum S``; ``prob0(H)`` [N + 1]: first float of its
     [H, S_n, S_n] probabilities; ``buckets``: {T: ids} with T = ceil(S_n / 32), ids ascending (the launches of the bucketed form,
-    ``_ATTN_VAR_BUCKETS``).  ``on(device, H)`` uploads the tables once per (device, H) in two copies; everything else is plain
-    Python and runs without a device."""
+    ``_ATTN_VAR_BUCKETS``); ``launch_groups()``: the attention launches of the batch.  ``on(device, H)`` uploads the tables once per
+    (device, H) in two copies; everything else is plain Python and runs without a device."""
 
     def __init__(self, lengths):
         self.lengths = list(lengths)
@@ -1276,24 +1279,37 @@ class SeqLayout:
     def n_probs(self, H):
         return H * sum(sn * sn for sn in self.S)
 
+    def launch_groups(self, buckets=False):
+        """The attention launches of the batch -> [(S of the launch = its longest sequence, ids ascending or None = all N)].
+        S_max <= 128: one launch for all (``buckets``: one per tile count present).  S_max > 128: at most two, each through an id
+        list - the sequences of at most 128 tokens (first-generation kernels), then the rest (key-tiled kernels; the entry point
+        follows the launch's S).  The kernel that computes a sequence is thereby a function of S_n alone, whatever its neighbours."""
+        if self.S_max > UNPADDED_MAX_TOKENS:
+            short = [n for n, sn in enumerate(self.S) if sn <= UNPADDED_MAX_TOKENS]
+            rest = [n for n, sn in enumerate(self.S) if sn > UNPADDED_MAX_TOKENS]
+            return [(max(self.S[n] for n in ids), ids) for ids in (short, rest) if ids]
+        if not buckets or len(self.buckets) == 1:
+            return [(self.S_max, None)]
+        return [(max(self.S[n] for n in ids), ids) for _, ids in sorted(self.buckets.items())]
+
     def on(self, device, H):
         """-> dict(row0 int32 [N + 1], row0_64 int64 [N] (the CLS rows, for lstc_gather_rows), prob0 int64 [N + 1], launches
         [(S of the launch, ids int32 or None, n_ids)]) on ``device``."""
         key = (str(device), int(H), _ATTN_VAR_BUCKETS)
         if key not in self._dev:
-            single = not _ATTN_VAR_BUCKETS or len(self.buckets) == 1
-            groups = [] if single else [(T, ids) for T, ids in sorted(self.buckets.items())]
+            groups = self.launch_groups(_ATTN_VAR_BUCKETS)
             flat = list(self.row0)
             for _, ids in groups:
-                flat += ids
+                flat += ids or []
             i32 = torch.tensor(flat, dtype=torch.int32).to(device)
             i64 = torch.tensor(self.prob0(H) + self.row0[:-1], dtype=torch.int64).to(device)
             launches, off = [], self.N + 1
-            for _, ids in groups:
-                launches.append((max(self.S[n] for n in ids), i32[off: off + len(ids)], len(ids)))
-                off += len(ids)
-            if single:
-                launches = [(self.S_max, None, self.N)]
+            for S, ids in groups:
+                if ids is None:
+                    launches.append((S, None, self.N))
+                else:
+                    launches.append((S, i32[off: off + len(ids)], len(ids)))
+                    off += len(ids)
             self._dev[key] = dict(row0=i32[: self.N + 1], prob0=i64[: self.N + 1], row0_64=i64[self.N + 1:], launches=launches)
         return self._dev[key]
 
@@ -1301,8 +1317,11 @@ class SeqLayout:
 def unpadded_layout(lengths, max_tokens=UNPADDED_MAX_TOKENS):
     """Host lengths (a Python sequence or a CPU tensor of N integers: patch tokens per sequence, the CLS token not counted) ->
     ``SeqLayout``.  Range-checked with ValueError before anything touches a device: integers, at least one sequence, 1 <= L_n and
-    L_n + 1 <= ``max_tokens`` (128 tokens, the attention kernels' LDS tile).  A device tensor is refused: the size of the output
-    depends on the sum of the lengths, so there is no device-lengths form.  Pure Python."""
+    L_n + 1 <= ``max_tokens`` (128 tokens by default, the first-generation attention kernels' LDS tile; up to
+    ``UNPADDED_LONG_MAX_TOKENS`` = 512 where the caller asks for the key-tiled offset kernels).  A device tensor is refused: the size
+    of the output depends on the sum of the lengths, so there is no device-lengths form.  Pure Python."""
+    if max_tokens > UNPADDED_LONG_MAX_TOKENS:
+        raise ValueError(f"max_tokens: the unpadded route takes sequences of at most {UNPADDED_LONG_MAX_TOKENS} tokens, got max_tokens={max_tokens}")
     if torch.is_tensor(lengths):
         if lengths.is_cuda:
             raise ValueError("unpadded lengths must live on the host (the output size depends on their sum): pass a list or a CPU tensor")
@@ -1332,7 +1351,8 @@ def _attn_var_desc(q, k, v, H, dk, dv, table, index, p_drop, seed):
 
 def attn_var_fwd(q, k, v, lay: SeqLayout, H, dk, dv, table, index, p_drop, seed, out=None, probs=None):
     """The attention core over an unpadded batch (lstc_attn_var_fwd): q, k, v [M, ld] row operands, ``lay`` the batch's layout.
-    One launch instantiated for the longest sequence (``_ATTN_VAR_BUCKETS``: one per tile count present in the batch).
+    One launch instantiated for the longest sequence (``_ATTN_VAR_BUCKETS``: one per tile count present in the batch); a batch
+    with a sequence above 128 tokens: ``SeqLayout.launch_groups`` - lstc_attn_var_long_fwd for the launch above 128 tokens.
     Returns (o [M, H*dv], probs: the flat ragged buffer, sequence n's [H, S_n, S_n] block from ``lay.prob0(H)[n]``)."""
     dev = q.device
     t = lay.on(dev, H)
@@ -1344,7 +1364,8 @@ def attn_var_fwd(q, k, v, lay: SeqLayout, H, dk, dv, table, index, p_drop, seed,
     for S, ids, n_ids in t["launches"]:
         d.S = S
         sq = _lib.Seqs(dev_ptr(t["row0"]), dev_ptr(t["prob0"]), dev_ptr(ids), n_ids, npr)
-        check(_lib.load().lstc_attn_var_fwd(C.byref(d), C.byref(sq), stream_ptr()), "lstc_attn_var_fwd")
+        name = "lstc_attn_var_long_fwd" if S > UNPADDED_MAX_TOKENS else "lstc_attn_var_fwd"
+        check(getattr(_lib.load(), name)(C.byref(d), C.byref(sq), stream_ptr()), name)
     return o, probs
 
 
@@ -1370,7 +1391,8 @@ def attn_var_bwd(do, q, k, v, probs, lay: SeqLayout, H, dk, dv, table, index, p_
             d.dtable, d.dtable_chunks = dev_ptr(parts[first:]), chunks[i]
             first += chunks[i]
         sq = _lib.Seqs(dev_ptr(t["row0"]), dev_ptr(t["prob0"]), dev_ptr(ids), n_ids, lay.n_probs(H))
-        check(_lib.load().lstc_attn_var_bwd(C.byref(d), C.byref(sq), stream_ptr()), "lstc_attn_var_bwd")
+        name = "lstc_attn_var_long_bwd" if S > UNPADDED_MAX_TOKENS else "lstc_attn_var_bwd"
+        check(getattr(_lib.load(), name)(C.byref(d), C.byref(sq), stream_ptr()), name)
     dtable = colsum(parts).view(table.shape[0], H) if parts is not None else None
     return dq, dk_, dv_, dtable
 

@@ -3,7 +3,8 @@ import torch
 from torch import nn
 
 from ..functional import (ClsConcatFunction, ClsConcatLenFunction, ClsConcatSpanFunction, ClsConcatVarFunction, DropoutFunction,
-                          LayerNormFunction, PackedAct, act_chain_ok, drop_producer_packs, lengths_arg, span_starts, unpadded_layout)
+                          LayerNormFunction, PackedAct, UNPADDED_MAX_TOKENS, act_chain_ok, drop_producer_packs, lengths_arg, span_starts,
+                          unpadded_layout)
 from .EncoderLayer import EncoderLayer
 from .MultiHeadAttention import key_padding_mask
 
@@ -187,7 +188,8 @@ class Encoder(nn.Module):
         drop_producer_packs()
         return out
 
-    def _unpadded(self, x, lengths, enc_output_hi=None, src_mask=None, return_attn=False, return_attn_v=False):
+    def _unpadded(self, x, lengths, enc_output_hi=None, src_mask=None, return_attn=False, return_attn_v=False,
+                  max_tokens=UNPADDED_MAX_TOKENS):
         """An unpadded batch: refuse what the route does not take and check the lengths -> functional.SeqLayout.  Every refusal is
         raised before any launch, and before the input's device matters."""
         if src_mask is not None or return_attn or return_attn_v:
@@ -201,7 +203,7 @@ class Encoder(nn.Module):
             raise ValueError("Encoder: an unpadded batch is one matrix: concatenate enc_output and enc_output_hi first")
         if x.dim() != 2:
             raise ValueError(f"Encoder: an unpadded batch is [sum of lengths, d_model], got {tuple(x.shape)}")
-        lay = unpadded_layout(lengths)
+        lay = unpadded_layout(lengths, max_tokens)
         if lay.in0[-1] != x.shape[0]:
             raise ValueError(f"Encoder: the lengths sum to {lay.in0[-1]} tokens, the input has {x.shape[0]} rows")
         self._layout_fits(lay)
@@ -219,6 +221,9 @@ class Encoder(nn.Module):
                              f"({attn0.relative_position_index.shape[0]} tokens)")
         if self.position_encoding and lay.S_max > self.position_enc.shape[1]:
             raise ValueError(f"Encoder: {lay.S_max} tokens exceed max_position_tokens = {self.position_enc.shape[1]}")
+        if lay.S_max > UNPADDED_MAX_TOKENS and (attn0.d_k % 16 or attn0.d_v % 16):
+            raise ValueError(f"Encoder: a sequence above {UNPADDED_MAX_TOKENS} tokens needs d_k and d_v multiples of 16 (the key-tiled "
+                             f"attention kernels), got d_k = {attn0.d_k}, d_v = {attn0.d_v}")
 
     def _embed_unpadded(self, x, lay):
         """``_embed`` of an unpadded batch -> [1, M, d_model]: the input LayerNorm is row-wise, the concat knows the offsets."""
@@ -230,7 +235,8 @@ class Encoder(nn.Module):
             x = DropoutFunction.apply(x, self.position_dropout.p, "position_dropout")
         return x.view(1, lay.M, -1)
 
-    def forward_unpadded(self, enc_output, lengths, src_mask=None, return_attn=False, return_attn_v=False):
+    def forward_unpadded(self, enc_output, lengths, src_mask=None, return_attn=False, return_attn_v=False,
+                         max_tokens=UNPADDED_MAX_TOKENS):
         """``forward`` of an UNPADDED batch: ``enc_output`` [sum L_n, d_model] holds the patch tokens of N sequences back to back,
         ``lengths`` (a Python sequence or a CPU tensor of N integers; on the host, because the output size depends on their sum)
         their token counts L_n, 1 <= L_n <= 127.  Returns [M, d_model], M = sum (L_n + 1): rows ``row0[n] .. row0[n] + L_n`` (row0 =
@@ -241,8 +247,11 @@ class Encoder(nn.Module):
         Refused before any launch: ``src_mask``, ``return_attn``, ``return_attn_v`` (NotImplementedError), a gather spec, a
         PackedAct, ``relative_pe_2D`` unless every length is window_size**2, a sequence above 128 tokens, beyond the relative
         index or beyond ``max_position_tokens`` (ValueError).  The bf16 activation stream, packed attention operands and the layer-0
-        distinct-rows path are off, as with a mask."""
-        lay = self._unpadded(enc_output, lengths, None, src_mask, return_attn, return_attn_v)
+        distinct-rows path are off, as with a mask.
+        ``max_tokens`` (default 128, at most 512): the longest sequence the call takes, CLS token included.  Above 128 the
+        sequences of more than 128 tokens run on the key-tiled offset kernels (lstc_attn_var_long_*; d_k and d_v multiples of 16,
+        else ValueError) and the others where they always ran, so a sequence's result does not depend on its neighbours' lengths."""
+        lay = self._unpadded(enc_output, lengths, None, src_mask, return_attn, return_attn_v, max_tokens)
         h = self._embed_unpadded(enc_output, lay)
         for i, layer in enumerate(self.layer_stack):
             layer.pos_ffn._emit_pack = i + 1 < len(self.layer_stack)
@@ -251,12 +260,13 @@ class Encoder(nn.Module):
         drop_producer_packs()
         return h.view(lay.M, -1)
 
-    def forward_cls_unpadded(self, enc_output, lengths, enc_output_hi=None, src_mask=None):
+    def forward_cls_unpadded(self, enc_output, lengths, enc_output_hi=None, src_mask=None, max_tokens=UNPADDED_MAX_TOKENS):
         """``forward_unpadded(x, lengths)[row0[:-1]]`` -> [N, d_model], the CLS row of every sequence, without computing the other
         rows of the last layer: its re-associated form over sequence offsets where it applies (``_cls_assoc_ok``), else the full
         block and a gather of the CLS rows.  Row n is what ``forward_cls(x_n[None])`` returns for sequence n alone; in exact-f32
-        ``eval()`` bit for bit.  Arguments and refusals as in ``forward_unpadded``."""
-        lay = self._unpadded(enc_output, lengths, enc_output_hi, src_mask)
+        ``eval()`` bit for bit.  Arguments and refusals as in ``forward_unpadded``; a batch with a sequence above 128 tokens
+        (``max_tokens``) takes the full last block and the gather."""
+        lay = self._unpadded(enc_output, lengths, enc_output_hi, src_mask, max_tokens=max_tokens)
         h = self._embed_unpadded(enc_output, lay)
         n = len(self.layer_stack)
         for i, layer in enumerate(self.layer_stack[:-1]):
@@ -267,7 +277,7 @@ class Encoder(nn.Module):
         drop_producer_packs()
         return out
 
-    def forward_cls_spans(self, bank, starts, lengths):
+    def forward_cls_spans(self, bank, starts, lengths, max_tokens=UNPADDED_MAX_TOKENS):
         """``forward_cls_unpadded`` fed from SPANS of an HBM-resident bank: ``bank`` is [R, d_model] float32 on the device (or
         [clips, P, d_model], viewed as its clips * P rows), sequence n the rows ``starts[n] .. starts[n] + lengths[n] - 1``.  ``starts``
         and ``lengths`` are host integers (Python sequences or CPU tensors); the lengths obey ``forward_cls_unpadded``'s rules.  Spans
@@ -289,7 +299,7 @@ class Encoder(nn.Module):
         rows = bank.reshape(-1, bank.shape[-1]) if bank.is_contiguous() else None
         if rows is None:
             raise ValueError("Encoder: spans need a contiguous bank")
-        lay = unpadded_layout(lengths)
+        lay = unpadded_layout(lengths, max_tokens)
         src0 = span_starts(starts, lay, rows.shape[0])
         self._layout_fits(lay)
         if not bank.is_cuda:

@@ -55,34 +55,61 @@ def ragged_batches(seqs, max_batch=4096):
 UNPADDED_ROWS_PER_SEQUENCE = 49      # 3 clips of 16 patches + the CLS token: the longest part of the LTN workloads
 
 
-def unpadded_batches(seqs, max_batch=4096, max_rows=None):
+UNPADDED_MAX_PROBS = 2 ** 32 - 1     # floats of a chunk's ragged probabilities: their offsets are the 32-bit dropout counters
+_UNPADDED_TOKENS = {"unpadded": 128, "unpadded_long": 512}      # ragged value -> longest sequence, CLS token counted
+
+
+def _unpadded_limit(ragged, lengths, what="sequence"):
+    """ValueError where a sequence is beyond the route's limit, before anything is launched -> the limit in tokens."""
+    limit = _UNPADDED_TOKENS[ragged]
+    for i, v in enumerate(lengths):
+        if v + 1 > limit:
+            if ragged == "unpadded":
+                if what == "span":
+                    raise ValueError(f"ragged='unpadded': span {i} has {v} patch tokens, the unpadded route takes at most 127")
+                raise ValueError(f"ragged='unpadded': sequence {i} has {v} patch tokens, the unpadded route takes at most 127 "
+                                 "(128 tokens with the CLS token); use ragged=True for this pool")
+            raise ValueError(f"ragged={ragged!r}: {what} {i} has {v} patch tokens, the route takes at most {limit - 1} ({limit} tokens "
+                             "with the CLS token)" + ("; use ragged=True for this pool" if what == "sequence" else ""))
+    return limit
+
+
+def _n_head(enc):
+    return int(enc.layer_stack[0].slf_attn.n_head)
+
+
+def unpadded_batches(seqs, max_batch=4096, max_rows=None, max_tokens=128, heads=0, max_probs=UNPADDED_MAX_PROBS):
     """The batches of ``ltn_sequence_scores(ragged="unpadded")``: consecutive chunks of sequences of ANY lengths, concatenated
     without padding -> [(ids, x [sum of lengths, d], lengths)] with ``ids`` the positions in ``seqs`` (input order) and
     ``x`` the rows of ``seqs[ids[0]]``, ``seqs[ids[1]]``, ... back to back.  A chunk holds up to ``max_batch`` sequences and up to
     ``max_rows`` rows with the CLS tokens counted (default ``49 * max_batch``: a full chunk of 3-clip parts at 16 patches, the
     largest [N * S, d] the grouped path forms on the LTN workloads, so the activations of a chunk stay that size); a single
     sequence always fits.  A sequence above 127 patch tokens (128 with the CLS token, the unpadded attention kernels' tile) raises
-    ValueError before anything is launched: score such a pool with ``ragged=True``.  Pure torch; runs on CPU tensors."""
+    ValueError before anything is launched: score such a pool with ``ragged=True``.  ``max_tokens`` = 512 is the limit of
+    ``ragged="unpadded_long"``; ``heads`` > 0 also closes a chunk before its ragged probabilities [heads, S_n, S_n] would pass
+    ``max_probs`` floats (``unpadded_chunks``).  Pure torch; runs on CPU tensors."""
     max_rows = UNPADDED_ROWS_PER_SEQUENCE * max_batch if max_rows is None else max_rows
-    for i, s in enumerate(seqs):
-        if s.shape[0] + 1 > 128:
-            raise ValueError(f"ragged='unpadded': sequence {i} has {s.shape[0]} patch tokens, the unpadded route takes at most 127 "
-                             "(128 tokens with the CLS token); use ragged=True for this pool")
-    batches = unpadded_chunks([int(s.shape[0]) for s in seqs], max_batch, max_rows)
+    _unpadded_limit("unpadded_long" if max_tokens > 128 else "unpadded", [int(s.shape[0]) for s in seqs])
+    batches = unpadded_chunks([int(s.shape[0]) for s in seqs], max_batch, max_rows, heads, max_probs)
     return [(ids, torch.cat([seqs[i] for i in ids], 0), [int(seqs[i].shape[0]) for i in ids]) for ids in batches]
 
 
-def unpadded_chunks(lengths, max_batch, max_rows):
+def unpadded_chunks(lengths, max_batch, max_rows, heads=0, max_probs=UNPADDED_MAX_PROBS):
     """The chunking rule of ``unpadded_batches`` on the lengths alone -> lists of consecutive positions: up to ``max_batch``
-    sequences and ``max_rows`` rows (CLS tokens counted) per chunk, a single sequence always fits.  Pure Python."""
-    batches, ids, rows = [], [], 0
+    sequences and ``max_rows`` rows (CLS tokens counted) per chunk, a single sequence always fits.  ``heads`` > 0: a chunk also
+    closes before its ragged attention probabilities, ``heads * S_n * S_n`` floats per sequence, would pass ``max_probs`` (2^32 - 1:
+    an element's offset in that buffer is its 32-bit dropout counter; at 512 tokens and 16 heads that is 1 023 sequences).
+    Pure Python."""
+    batches, ids, rows, probs = [], [], 0, 0
     for i, v in enumerate(lengths):
         r = int(v) + 1
-        if ids and (len(ids) >= max_batch or rows + r > max_rows):
+        pr = heads * r * r
+        if ids and (len(ids) >= max_batch or rows + r > max_rows or probs + pr > max_probs):
             batches.append(ids)
-            ids, rows = [], 0
+            ids, rows, probs = [], 0, 0
         ids.append(i)
         rows += r
+        probs += pr
     if ids:
         batches.append(ids)
     return batches
@@ -97,14 +124,18 @@ def ltn_sequence_scores(enc, head, seqs, max_batch=4096, ragged=False):
     every score is what the sequence gets alone (up to float re-association), in input order.
     ``ragged="unpadded"``: sequences of all lengths share batches WITHOUT padding - concatenated (``unpadded_batches``) and scored
     through ``Encoder.forward_cls_unpadded``: one launch chain per chunk that costs the real tokens only.  Sequences of at most
-    127 patch tokens; a longer one raises before any launch."""
-    if isinstance(ragged, str) and ragged != "unpadded":
-        raise ValueError(f"ragged: expected False, True or 'unpadded', got {ragged!r}")
-    if ragged == "unpadded":
-        batches = unpadded_batches(seqs, max_batch)
+    127 patch tokens; a longer one raises before any launch.
+    ``ragged="unpadded_long"``: the same route with sequences of up to 511 patch tokens (``forward_cls_unpadded(...,
+    max_tokens=512)``: the key-tiled offset kernels for the sequences above 128 tokens; d_k and d_v multiples of 16)."""
+    if isinstance(ragged, str) and ragged not in _UNPADDED_TOKENS:
+        raise ValueError(f"ragged: expected False, True, 'unpadded' or 'unpadded_long', got {ragged!r}")
+    if isinstance(ragged, str):
+        limit = _unpadded_limit(ragged, [int(s.shape[0]) for s in seqs])
+        batches = unpadded_batches(seqs, max_batch, max_tokens=limit, heads=_n_head(enc))
         out = torch.empty(len(seqs), device=seqs[0].device, dtype=torch.float32)
         for ids, x, lengths in batches:
-            out[ids[0]:ids[-1] + 1] = head(enc.forward_cls_unpadded(x, lengths)).view(-1, 2)[:, 1]
+            cls = enc.forward_cls_unpadded(x, lengths) if limit == 128 else enc.forward_cls_unpadded(x, lengths, max_tokens=limit)
+            out[ids[0]:ids[-1] + 1] = head(cls).view(-1, 2)[:, 1]
         return out
     out = torch.empty(len(seqs), device=seqs[0].device, dtype=torch.float32)
     if ragged:
@@ -245,20 +276,20 @@ def resident_sequence_scores(enc, head, bank, spans, max_batch=4096, ragged=Fals
     (``enc.forward_cls((bank, clip_idx, N, Lc))``: the fixed-layout kernels; the spans must be whole clips of a 3-D bank); where
     that entry refuses (d % 4, an input LayerNorm) the group is gathered (``functional.gather_rows``) and scored by ``forward_cls``.
     ``ragged="unpadded"``: spans of all lengths share chunks (``unpadded_chunks``, the rule of ``unpadded_batches``) scored by
-    ``Encoder.forward_cls_spans``.  ``ragged=True`` (padded batches) does not exist on a bank.  ``classifier_head``: P(abnormal) is
-    column 1 of the head's two outputs (False: a Regressor's single output)."""
-    if ragged is True or (ragged and ragged != "unpadded"):
+    ``Encoder.forward_cls_spans``; ``ragged="unpadded_long"``: the same with spans of up to 511 patch tokens (``max_tokens=512``).
+    ``ragged=True`` (padded batches) does not exist on a bank.  ``classifier_head``: P(abnormal) is column 1 of the head's two
+    outputs (False: a Regressor's single output)."""
+    if ragged is True or (ragged and ragged not in _UNPADDED_TOKENS):
         raise ValueError(f"ragged={ragged!r}: a resident bank is scored with ragged=False (same-length groups through the gather "
                          "spec) or ragged='unpadded' (spans of all lengths, forward_cls_spans)")
     spans = [(int(r), int(t)) for r, t in spans]
     take = (lambda y: y.view(-1, 2)[:, 1]) if classifier_head else (lambda y: y.reshape(-1))
     out = torch.empty(len(spans), device=bank.device, dtype=torch.float32)
-    if ragged == "unpadded":
-        for i, (_, t) in enumerate(spans):
-            if t + 1 > 128:
-                raise ValueError(f"ragged='unpadded': span {i} has {t} patch tokens, the unpadded route takes at most 127")
-        for ids in unpadded_chunks([t for _, t in spans], max_batch, UNPADDED_ROWS_PER_SEQUENCE * max_batch):
-            cls = enc.forward_cls_spans(bank, [spans[i][0] for i in ids], [spans[i][1] for i in ids])
+    if ragged:
+        limit = _unpadded_limit(ragged, [t for _, t in spans], "span")
+        for ids in unpadded_chunks([t for _, t in spans], max_batch, UNPADDED_ROWS_PER_SEQUENCE * max_batch, _n_head(enc)):
+            starts, lens = [spans[i][0] for i in ids], [spans[i][1] for i in ids]
+            cls = enc.forward_cls_spans(bank, starts, lens) if limit == 128 else enc.forward_cls_spans(bank, starts, lens, max_tokens=limit)
             out[ids[0]:ids[-1] + 1] = take(head(cls))
         return out
     if bank.dim() != 3:
