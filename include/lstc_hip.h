@@ -699,6 +699,41 @@ typedef struct LstcAdagradItem {
     float lr, weight_decay, eps, grad_scale;
 } LstcAdagradItem;
 int lstc_adagrad_multi(const LstcAdagradItem* items, int32_t count, void* stream);
+
+/* torch.optim.Adam (decoupled = 0: weight decay added to the gradient) and torch.optim.AdamW (decoupled = 1: the weight is
+ * shrunk first), amsgrad = False, maximize = False, for EVERY parameter of the step in one launch - `items` is a HOST array that
+ * rides in the kernel arguments, 48 per launch, like lstc_adagrad_multi's.  Nothing that changes from step to step is passed by
+ * value, so a captured launch can be replayed: the step count t is the item's DEVICE word `step` (the call adds 1 to it with a
+ * one-thread-per-item launch in front of the update, then every workgroup reads the new value), and the learning rate is
+ * lr_t = lr * *lr_scale with `lr_scale` a DEVICE float (NULL = 1).  Each item owns its word.
+ *
+ * Per item, in float64 from the f32 fields widened, each rounded ONCE to f32:
+ *     omb1 = 1 - beta1     omb2 = 1 - beta2     step = lr_t / (1 - beta1^t)     rsb2 = 1 / sqrt(1 - beta2^t)
+ *     keep = 1 - lr_t * weight_decay            (lr_t = lr * *lr_scale and beta^t, by repeated squaring, in float64 too)
+ * Per element, f32, one rounding per operation, in this order (no contraction):
+ *     g = grad * grad_scale
+ *     decoupled ?  w = w * keep  :  g = g + weight_decay * w
+ *     m = m + omb1 * (g - m)
+ *     v = beta2 * v + omb2 * (g * g)
+ *     w = w - (step * m) / (sqrtf(v) * rsb2 + eps)
+ * The result of an element does not depend on pointer alignment (float4 accesses when w, grad, m and v are all 16-byte aligned,
+ * scalar ones otherwise) nor on how a list is split into calls.
+ *
+ * Refused before any launch: count < 0, items == NULL with count > 0, a NULL w / grad / m / v / step, n < 0, two items sharing one
+ * step word (LSTC_E_SHAPE); beta1 or beta2 outside [0, 1), eps, lr or weight_decay negative or not finite (LSTC_E_RANGE).
+ * An item with n == 0 updates nothing; its word is still incremented.  count == 0 does nothing. */
+typedef struct LstcAdamItem {
+    float* w;
+    const float* grad;
+    float* m;                 /* exp_avg */
+    float* v;                 /* exp_avg_sq */
+    int64_t n;
+    int32_t* step;            /* DEVICE word of this item: the call adds 1 to it, then uses the new value as t */
+    const float* lr_scale;    /* DEVICE float or NULL (= 1): lr_t = lr * *lr_scale, read on the device */
+    float lr, beta1, beta2, eps, weight_decay, grad_scale;
+    int32_t decoupled;        /* 0: Adam (wd added to the gradient), 1: AdamW (w *= 1 - lr_t * wd first) */
+} LstcAdamItem;
+int lstc_adam_multi(const LstcAdamItem* items, int32_t count, void* stream);
 /* out[0] += sum(x^2) (f32 atomics over workgroup partials; caller zeroes) — for clip_grad_norm_. */
 int lstc_sqnorm_accum(const float* x, int64_t n, float* out, void* stream);
 

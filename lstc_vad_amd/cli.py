@@ -130,6 +130,12 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                    help="MIL bag score = mean of the K largest part means of a video (1 = the maximum, as the reference computes; "
                         "1..part_num, part_num <= 64 above 1).  The reference's own --topk (default 7) still parses and still does "
                         "nothing, as upstream: wiring it up would change every existing run")
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "adam", "adamw"],
+                   help="adagrad = the reference's optimizer; adam / adamw = torch.optim.Adam / AdamW semantics on one multi-tensor "
+                        "HIP launch (lstc_adam_multi).  Learning rates and --weight_decay keep their flags")
+    p.add_argument("--adam_beta1", type=float, default=0.9, help="--optimizer adam / adamw: decay of the first-moment average")
+    p.add_argument("--adam_beta2", type=float, default=0.999, help="--optimizer adam / adamw: decay of the second-moment average")
+    p.add_argument("--adam_eps", type=float, default=1e-8, help="--optimizer adam / adamw: the denominator's epsilon")
     p.add_argument("--resident_eval", action="store_true",
                    help="evaluation and pseudo-label passes score from HBM: the test / label set is uploaded once "
                         "(pipeline.ResidentSet), the train-AUC pass reads the training bank already there, and every pass describes "
@@ -372,7 +378,12 @@ def train(script: str, argv=None, args=None):
                           mil_topk=getattr(args, "mil_topk", 1))
     if step_args.mil_topk != 1 and rank == 0:
         logger.info("--mil_topk %d: a bag is the mean of its %d largest part means (of %d parts)" % (step_args.mil_topk, step_args.mil_topk, args.part_num))
-    ts = TrainStep(step_args, mode, enc, head, _get(args, "lr_encoder", pre, 1e-4), lr_head, args.weight_decay)
+    opt_name = getattr(args, "optimizer", "adagrad")
+    opt_kw = None if opt_name == "adagrad" else dict(betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps)
+    if opt_kw and rank == 0:
+        logger.info("--optimizer %s: betas (%g, %g), eps %g, weight_decay %g" % (opt_name, args.adam_beta1, args.adam_beta2, args.adam_eps, args.weight_decay))
+    ts = TrainStep(step_args, mode, enc, head, _get(args, "lr_encoder", pre, 1e-4), lr_head, args.weight_decay,
+                   optimizer=opt_name, optimizer_kw=opt_kw)
 
     if script == "spatio_transformer_MIL_CE":
         # round 0 (the only round: `for round_i in range(1)`, Train/spatio_transformer_MIL_CE.py:113-116) trains the STN on

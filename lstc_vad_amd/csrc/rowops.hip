@@ -2,8 +2,11 @@
 // column sums, dropout replay, the fused last head layer, Adagrad, squared-norm.
 // All of them stream their operands once with 16-B-per-lane accesses where the layout allows
 // (cdna_hip_programming Guideline 13) and reduce with wave shuffles.
+#include <algorithm>
+#include <cmath>
 #include <initializer_list>
 #include <type_traits>
+#include <vector>
 #include "lstc_common.h"
 
 namespace {
@@ -974,58 +977,152 @@ __global__ void __launch_bounds__(NT) adagrad_kernel(float* __restrict__ w, cons
 }
 
 // All parameters of an optimizer step in ONE launch: up to ADA_MAX tensors ride in the kernel arguments (no device-side table,
-// no host-to-device copy); a workgroup finds its tensor by scanning the prefix of workgroup counts and then runs the same
-// element update as adagrad_kernel on its slice.  Element arithmetic and order are adagrad_kernel's: results are bit-identical.
+// no host-to-device copy); a workgroup finds its tensor by scanning the prefix of workgroup counts and then runs the optimizer's
+// element update on its ADA_PER_WG slice.  The scan, the slicing and the float4 / scalar loops are stated ONCE
+// (multi_tensor_update) for every optimizer; an optimizer is an Op: its per-workgroup scalars and ``elem``, the update of one
+// element.  Adagrad's elem is adagrad_kernel's arithmetic in adagrad_kernel's order: results are bit-identical.
 constexpr int ADA_MAX = 48;
 constexpr int ADA_PER_WG = NT * 4 * 8;        // elements per workgroup: 8 float4 per thread
-struct AdaBatch {
+template <int NS> struct MultiBatch {         // NS state tensors beside the weight and the gradient
     float* w[ADA_MAX];
     const float* g[ADA_MAX];
-    float* s[ADA_MAX];
+    float* s[NS][ADA_MAX];
     long long n[ADA_MAX];
-    float lr[ADA_MAX], wd[ADA_MAX], eps[ADA_MAX], gscale[ADA_MAX];
     int first_wg[ADA_MAX + 1];
     int count;
 };
-__global__ void __launch_bounds__(NT) adagrad_multi_kernel(const AdaBatch b) {
+struct AdaBatch : MultiBatch<1> {
+    float lr[ADA_MAX], wd[ADA_MAX], eps[ADA_MAX], gscale[ADA_MAX];
+};
+struct AdagradOp {
+    static constexpr int NS = 1;
+    float lr, wd, eps, gscale;
+    __device__ AdagradOp(const AdaBatch& b, int t) : lr(b.lr[t]), wd(b.wd[t]), eps(b.eps[t]), gscale(b.gscale[t]) {}
+    __device__ __forceinline__ void elem(float& w, float g, float& s, float&) const {
+        const float gg = g * gscale + wd * w;
+        s += gg * gg;
+        w -= lr * gg / (sqrtf(s) + eps);
+    }
+};
+
+// Adam / AdamW (lstc_adam_multi, include/lstc_hip.h).  What changes from step to step is read on the device: t from the item's
+// step word (adam_tick_kernel has added 1 to it, earlier in stream order), the learning-rate multiplier from *lr_scale.  The
+// per-item scalars are formed in float64 from the f32 fields widened and rounded ONCE to f32, per workgroup:
+//   omb1 = 1 - b1,  omb2 = 1 - b2,  step = lr_t / (1 - b1^t),  rsb2 = 1 / sqrt(1 - b2^t),  keep = 1 - lr_t wd,  lr_t = lr *lr_scale
+// (b^t by repeated squaring in float64).  The element arithmetic is f32, one rounding per operation, in this order:
+//   g = grad * gscale;   decoupled ? w = w * keep : g = g + wd * w;
+//   m = m + omb1 * (g - m);   v = b2 * v + omb2 * (g * g);   w = w - (step * m) / (sqrtf(v) * rsb2 + eps)
+struct AdamBatch : MultiBatch<2> {
+    int* step[ADA_MAX];
+    const float* lr_scale[ADA_MAX];
+    float lr[ADA_MAX], b1[ADA_MAX], b2[ADA_MAX], eps[ADA_MAX], wd[ADA_MAX], gscale[ADA_MAX];
+    unsigned long long decoupled;             // bit i: item i is AdamW
+};
+static_assert(sizeof(AdamBatch) <= 4096, "the items must fit the kernel-argument segment");
+__device__ __forceinline__ double pow_f64(double b, unsigned e) {
+    double r = 1.0;
+    for (; e; e >>= 1, b *= b)
+        if (e & 1u) r *= b;
+    return r;
+}
+struct AdamOp {
+    static constexpr int NS = 2;
+    float omb1, b2, omb2, step, rsb2, eps, wd, gscale, keep;
+    bool decoupled;
+    __device__ AdamOp(const AdamBatch& b, int i) {
+        const int* __restrict__ word = b.step[i];
+        const float* __restrict__ scale = b.lr_scale[i];
+        const unsigned t = (unsigned)*word;                                  // uniform address: one scalar load per workgroup
+        const double lr_t = (double)b.lr[i] * (double)(scale ? *scale : 1.0f);
+        const double d1 = (double)b.b1[i], d2 = (double)b.b2[i];
+        omb1 = (float)(1.0 - d1);
+        omb2 = (float)(1.0 - d2);
+        step = (float)(lr_t / (1.0 - pow_f64(d1, t)));
+        rsb2 = (float)(1.0 / sqrt(1.0 - pow_f64(d2, t)));
+        keep = (float)(1.0 - lr_t * (double)b.wd[i]);
+        b2 = b.b2[i]; eps = b.eps[i]; wd = b.wd[i]; gscale = b.gscale[i];
+        decoupled = (b.decoupled >> i) & 1ull;
+    }
+    __device__ __forceinline__ void elem(float& w, float g, float& m, float& v) const {
+        float gg = g * gscale;
+        if (decoupled) w = w * keep;
+        else gg = gg + wd * w;
+        m = m + omb1 * (gg - m);
+        v = b2 * v + omb2 * (gg * gg);
+        w = w - step * m / (sqrtf(v) * rsb2 + eps);
+    }
+};
+
+template <class Op, class Batch> __device__ __forceinline__ void multi_tensor_update(const Batch& b) {
+    constexpr bool two = Op::NS > 1;
     int t = 0;
     while (t + 1 < b.count && (int)blockIdx.x >= b.first_wg[t + 1]) ++t;          // wave-uniform scan (scalar loads of the arguments)
     float* __restrict__ w = b.w[t];
     const float* __restrict__ g = b.g[t];
-    float* __restrict__ s = b.s[t];
+    float* __restrict__ s = b.s[0][t];
+    float* __restrict__ s2 = b.s[Op::NS - 1][t];          // the second state tensor (Op::NS == 2), else `s` again and unused
     const int64_t n = b.n[t];
-    const float lr = b.lr[t], wd = b.wd[t], eps = b.eps[t], gscale = b.gscale[t];
+    const Op op(b, t);
     const int64_t e0 = (int64_t)((int)blockIdx.x - b.first_wg[t]) * ADA_PER_WG;
     const int64_t e1 = min(n, e0 + ADA_PER_WG);
-    const bool vec = aligned16(w) && aligned16(g) && aligned16(s);
+    const bool vec = aligned16(w) && aligned16(g) && aligned16(s) && aligned16(s2);
     if (vec) {
         const int64_t v1 = e1 == n ? (n >> 2) : (e1 >> 2);
         for (int64_t i = (e0 >> 2) + threadIdx.x; i < v1; i += NT) {
             float4 wv = reinterpret_cast<float4*>(w)[i], sv = reinterpret_cast<float4*>(s)[i];
+            float4 tv = sv;
+            if constexpr (two) tv = reinterpret_cast<float4*>(s2)[i];
             const float4 gv = reinterpret_cast<const float4*>(g)[i];
-            float gg;
-            gg = gv.x * gscale + wd * wv.x; sv.x += gg * gg; wv.x -= lr * gg / (sqrtf(sv.x) + eps);
-            gg = gv.y * gscale + wd * wv.y; sv.y += gg * gg; wv.y -= lr * gg / (sqrtf(sv.y) + eps);
-            gg = gv.z * gscale + wd * wv.z; sv.z += gg * gg; wv.z -= lr * gg / (sqrtf(sv.z) + eps);
-            gg = gv.w * gscale + wd * wv.w; sv.w += gg * gg; wv.w -= lr * gg / (sqrtf(sv.w) + eps);
+            op.elem(wv.x, gv.x, sv.x, tv.x);
+            op.elem(wv.y, gv.y, sv.y, tv.y);
+            op.elem(wv.z, gv.z, sv.z, tv.z);
+            op.elem(wv.w, gv.w, sv.w, tv.w);
             reinterpret_cast<float4*>(w)[i] = wv;
             reinterpret_cast<float4*>(s)[i] = sv;
+            if constexpr (two) reinterpret_cast<float4*>(s2)[i] = tv;
         }
         if (e1 != n) return;
-        for (int64_t i = (n >> 2) * 4 + threadIdx.x; i < n; i += NT) {          // the tensor's last 0-3 elements
-            const float gg = g[i] * gscale + wd * w[i];
-            const float sv = s[i] + gg * gg;
-            s[i] = sv;
-            w[i] -= lr * gg / (sqrtf(sv) + eps);
-        }
-        return;
     }
-    for (int64_t i = e0 + threadIdx.x; i < e1; i += NT) {
-        const float gg = g[i] * gscale + wd * w[i];
-        const float sv = s[i] + gg * gg;
+    // fully scalar when a pointer is unaligned; else the tensor's last 0-3 elements (its last workgroup only)
+    for (int64_t i = (vec ? (n >> 2) * 4 : e0) + threadIdx.x; i < e1; i += NT) {
+        float wv = w[i], sv = s[i], tv = sv;
+        if constexpr (two) tv = s2[i];
+        op.elem(wv, g[i], sv, tv);
         s[i] = sv;
-        w[i] -= lr * gg / (sqrtf(sv) + eps);
+        if constexpr (two) s2[i] = tv;
+        w[i] = wv;
     }
+}
+__global__ void __launch_bounds__(NT) adagrad_multi_kernel(const AdaBatch b) { multi_tensor_update<AdagradOp>(b); }
+__global__ void __launch_bounds__(NT) adam_multi_kernel(const AdamBatch b) { multi_tensor_update<AdamOp>(b); }
+// t = ++*step of every item of the launch, n == 0 items included; one thread per item, in front of adam_multi_kernel
+__global__ void __launch_bounds__(64) adam_tick_kernel(const AdamBatch b) {
+    if ((int)threadIdx.x < b.count) *b.step[threadIdx.x] += 1;
+}
+
+// The launcher of multi_tensor_update, for every optimizer: 48 items per launch, item i of a launch owning workgroups
+// first_wg[i] .. first_wg[i + 1] - 1 (none when n == 0).  `fill` copies one item's fields into slot i, `launch` issues the kernels.
+template <class Batch, class Item, class Fill, class Launch>
+static int multi_tensor_launch(const Item* items, int32_t count, void* stream, Fill fill, Launch launch) {
+    for (int32_t base = 0; base < count; base += ADA_MAX) {
+        Batch b;
+        b.count = count - base < ADA_MAX ? count - base : ADA_MAX;
+        int wg = 0;
+        for (int i = 0; i < b.count; ++i) {
+            const Item& it = items[base + i];
+            fill(b, i, it);
+            b.n[i] = it.n;
+            b.first_wg[i] = wg;
+            const int64_t nwg = (it.n + ADA_PER_WG - 1) / ADA_PER_WG;
+            if (nwg > 0x7fffffff - wg) return LSTC_E_RANGE;
+            wg += (int)nwg;
+        }
+        for (int i = b.count; i <= ADA_MAX; ++i) b.first_wg[i] = wg;
+        launch(b, wg, (hipStream_t)stream);
+        const int rc = lstc_launch_status();
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 __global__ void __launch_bounds__(NT) sqnorm_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
@@ -1564,26 +1661,37 @@ int lstc_adagrad_multi(const LstcAdagradItem* items, int32_t count, void* stream
         if (!items[i].w || !items[i].grad || !items[i].state) return LSTC_E_NULL;
         if (items[i].n <= 0) return LSTC_E_SHAPE;
     }
-    for (int32_t base = 0; base < count; base += ADA_MAX) {
-        AdaBatch b;
-        b.count = count - base < ADA_MAX ? count - base : ADA_MAX;
-        int wg = 0;
-        for (int i = 0; i < b.count; ++i) {
-            const LstcAdagradItem& it = items[base + i];
-            b.w[i] = it.w; b.g[i] = it.grad; b.s[i] = it.state; b.n[i] = it.n;
-            b.lr[i] = it.lr; b.wd[i] = it.weight_decay; b.eps[i] = it.eps; b.gscale[i] = it.grad_scale;
-            b.first_wg[i] = wg;
-            const int64_t nwg = (it.n + ADA_PER_WG - 1) / ADA_PER_WG;
-            if (nwg > 0x7fffffff - wg) return LSTC_E_RANGE;
-            wg += (int)nwg;
-        }
-        b.first_wg[b.count] = wg;
-        for (int i = b.count + 1; i <= ADA_MAX; ++i) b.first_wg[i] = wg;
-        hipLaunchKernelGGL(adagrad_multi_kernel, dim3((unsigned)wg), NT, 0, (hipStream_t)stream, b);
-        const int rc = lstc_launch_status();
-        if (rc) return rc;
+    return multi_tensor_launch<AdaBatch>(items, count, stream, [](AdaBatch& b, int i, const LstcAdagradItem& it) {
+        b.w[i] = it.w; b.g[i] = it.grad; b.s[0][i] = it.state;
+        b.lr[i] = it.lr; b.wd[i] = it.weight_decay; b.eps[i] = it.eps; b.gscale[i] = it.grad_scale;
+    }, [](const AdaBatch& b, int wg, hipStream_t st) {
+        hipLaunchKernelGGL(adagrad_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);
+    });
+}
+
+int lstc_adam_multi(const LstcAdamItem* items, int32_t count, void* stream) {
+    if (count < 0 || (!items && count > 0)) return LSTC_E_SHAPE;
+    std::vector<const int32_t*> words((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        const LstcAdamItem& it = items[i];
+        if (!it.w || !it.grad || !it.m || !it.v || !it.step || it.n < 0) return LSTC_E_SHAPE;
+        const auto bad = [](float x) { return !(x >= 0.f) || std::isinf(x); };          // negative, NaN or infinite
+        if (bad(it.beta1) || it.beta1 >= 1.f || bad(it.beta2) || it.beta2 >= 1.f || bad(it.eps) || bad(it.lr) || bad(it.weight_decay))
+            return LSTC_E_RANGE;
+        words[(size_t)i] = it.step;
     }
-    return 0;
+    std::sort(words.begin(), words.end());
+    if (std::adjacent_find(words.begin(), words.end()) != words.end()) return LSTC_E_SHAPE;          // every item owns its word
+    return multi_tensor_launch<AdamBatch>(items, count, stream, [](AdamBatch& b, int i, const LstcAdamItem& it) {
+        if (i == 0) b.decoupled = 0;
+        b.w[i] = it.w; b.g[i] = it.grad; b.s[0][i] = it.m; b.s[1][i] = it.v;
+        b.step[i] = it.step; b.lr_scale[i] = it.lr_scale;
+        b.lr[i] = it.lr; b.b1[i] = it.beta1; b.b2[i] = it.beta2; b.eps[i] = it.eps; b.wd[i] = it.weight_decay; b.gscale[i] = it.grad_scale;
+        if (it.decoupled) b.decoupled |= 1ull << i;
+    }, [](const AdamBatch& b, int wg, hipStream_t st) {
+        hipLaunchKernelGGL(adam_tick_kernel, dim3(1), 64, 0, st, b);
+        if (wg > 0) hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);          // wg == 0: only empty items
+    });
 }
 
 static int vec_batch(const LstcVecItem* items, int32_t base, int32_t count, VecBatch& b) {

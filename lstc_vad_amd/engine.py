@@ -15,13 +15,13 @@ import torch.distributed as dist
 
 from .dist import GradAllReducer, direct_grad_parameters, encoder_head_buckets
 from .losses import training_loss
-from .optim import Adagrad, clip_grad_norm_
+from .optim import Adagrad, Adam, AdamW, clip_grad_norm_
 
 
 class TrainStep:
     def __init__(self, args, mode: str, encoder, head, lr_encoder: float, lr_head: float, weight_decay: float,
                  group=None, cls_only: bool = True, loss_rank=None, loss_exchange=None, fuse_qkv="auto",
-                 grad_reduce_dtype: str = "fp32", n_buckets=None):
+                 grad_reduce_dtype: str = "fp32", n_buckets=None, optimizer: str = "adagrad", optimizer_kw=None):
         # cls_only=False evaluates the last encoder layer for every token like the reference does (its extra rows are
         # never read); kept for A/B measurements — results are identical (tests/test_hip_parity.py)
         self.cls_only = cls_only
@@ -40,8 +40,15 @@ class TrainStep:
             for layer in list(encoder.layer_stack)[:-1] if cls_only else list(encoder.layer_stack):
                 layer.slf_attn.fuse_qkv_()
         self.fused_qkv = bool(fuse_qkv is True or fuse_qkv == "on")
-        self.optimizer = Adagrad([{"params": encoder.parameters(), "lr": lr_encoder},
-                                  {"params": head.parameters(), "lr": lr_head}], weight_decay=weight_decay)
+        # "adagrad" is the reference's optimizer; "adam" / "adamw" take ``optimizer_kw`` (betas, eps) and the same two learning
+        # rates and weight decay.  All three are one launch per step with the same step(only=...) rules (optim.py)
+        if optimizer not in ("adagrad", "adam", "adamw"):
+            raise ValueError(f"optimizer must be 'adagrad', 'adam' or 'adamw', not {optimizer!r}")
+        if optimizer == "adagrad" and optimizer_kw:
+            raise ValueError("optimizer_kw (betas, eps) belongs to optimizer='adam' / 'adamw'")
+        groups = [{"params": encoder.parameters(), "lr": lr_encoder}, {"params": head.parameters(), "lr": lr_head}]
+        self.optimizer = (Adagrad(groups, weight_decay=weight_decay) if optimizer == "adagrad" else
+                          (Adam if optimizer == "adam" else AdamW)(groups, weight_decay=weight_decay, **(optimizer_kw or {})))
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         force = os.environ.get("LSTC_FORCE_DIST", "0") == "1" and dist.is_available() and dist.is_initialized()
         # measurement hook (bench.py at N > 1): a list to receive (before backward, after backward, after reducer.finish()) HIP events
@@ -191,8 +198,9 @@ class GraphedStep:
         # 1. warm-up on a side stream (lazy kernel attributes, autograd threads, allocator pools), then put weights, Adagrad
         #    state and the seed counter back: constructing a GraphedStep leaves the training state untouched
         keep_w = [p.detach().clone() for p in params]
-        keep_s = [ts.optimizer.state[p]["sum"].clone() for p in params]
-        keep_n = [ts.optimizer.state[p]["step"] for p in params]
+        # whatever tensors the optimizer keeps per parameter (Adagrad: sum; Adam: exp_avg, exp_avg_sq and the device step word)
+        keep_s = [{k: v.clone() for k, v in ts.optimizer.state[p].items() if torch.is_tensor(v)} for p in params]
+        keep_n = [ts.optimizer.host_step(p) for p in params]
         c0 = Fn._counter
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -205,8 +213,9 @@ class GraphedStep:
         with torch.no_grad():
             for p, w, s_, n in zip(params, keep_w, keep_s, keep_n):
                 p.copy_(w)
-                ts.optimizer.state[p]["sum"].copy_(s_)
-                ts.optimizer.state[p]["step"] = n
+                for k, v in s_.items():
+                    ts.optimizer.state[p][k].copy_(v)
+                ts.optimizer.set_host_step(p, n)
         del keep_w, keep_s
         Fn.bump_weight_epoch()
         Fn.reset_rng(c0)
@@ -232,7 +241,7 @@ class GraphedStep:
             raise RuntimeError("GraphedStep: a step must draw the same number of dropout seeds every time")
         Fn.reset_rng(c0)                      # nothing ran: the first replay IS the step with these seeds
         for p, n in zip(params, keep_n):
-            ts.optimizer.state[p]["step"] = n
+            ts.optimizer.set_host_step(p, n)
         # eager Adagrad.step skips parameters without a gradient (LayerNorms the reference builds but never calls): only the
         # ones the captured step really updates get their ``step`` count bumped per replay (state_dict parity with eager runs)
         self._params = [p for p in params if p.grad is not None]
@@ -255,8 +264,9 @@ class GraphedStep:
         self.graph.replay()
         self._word_host = want + self.seeds_per_step
         Fn.reset_rng(Fn._counter + self.seeds_per_step)
-        for p in self._params:
-            self.ts.optimizer.state[p]["step"] += 1
+        opt = self.ts.optimizer
+        for p in self._params:          # the host's step counts (Adam: the mirror of the device words the graph incremented)
+            opt.set_host_step(p, opt.host_step(p) + 1)
         Fn.bump_weight_epoch()
         return self.scalars.clone()
 

@@ -1,10 +1,14 @@
-"""Adagrad with the reference's settings, stepped by the fused HIP kernel.
+"""The optimizers of the training step, each stepped by ONE fused multi-tensor HIP launch.
 
-The reference builds ``torch.optim.Adagrad([{params: encoder, lr: lr_encoder}, {params: head, lr: lr_head}],
+``Adagrad`` is the reference's: it builds ``torch.optim.Adagrad([{params: encoder, lr: lr_encoder}, {params: head, lr: lr_head}],
 weight_decay=wd)`` (Train/temporal_transformer_shanghaitech.py:83-85) and calls ``zero_grad / backward /
 [clip_grad_norm_] / step`` (:137-142).  This class keeps that surface (param groups, ``zero_grad``, ``step``,
 ``state_dict``) and the exact update ``g += wd*w; s += g*g; w -= lr*g/(sqrt(s)+1e-10)``; parameters whose
 ``grad`` is None are skipped exactly like upstream (unused LayerNorms never get a gradient).
+
+``Adam`` and ``AdamW`` are ``torch.optim.Adam`` / ``torch.optim.AdamW`` (amsgrad off) on ``lstc_adam_multi``: the step count and
+the learning-rate multiplier live on the device, so a captured step (engine.GraphedStep) replays as step 2, 3, ... and follows
+a schedule set through ``set_lr_scale``.  All three share ``step(closure, grad_scales, only)`` and what follows the launch.
 """
 from __future__ import annotations
 
@@ -14,17 +18,10 @@ from . import _lib
 from ._lib import check, dev_ptr, stream_ptr
 
 
-class Adagrad(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10):
-        if lr_decay != 0:
-            raise NotImplementedError("lr_decay is 0 everywhere on the LSTC_VAD path")
-        defaults = dict(lr=lr, weight_decay=weight_decay, eps=eps, initial_accumulator_value=initial_accumulator_value)
-        super().__init__(params, defaults)
-        for group in self.param_groups:
-            for p in group["params"]:
-                self.state[p]["sum"] = torch.full_like(p, float(group["initial_accumulator_value"]),
-                                                       memory_format=torch.preserve_format)
-                self.state[p]["step"] = 0
+class _MultiTensorOptimizer(torch.optim.Optimizer):
+    """What every optimizer here shares: the selection of the parameters of a step, one launch over all of them, and the
+    packed-weight bookkeeping behind it.  A subclass gives ``_item`` (one parameter's entry of the launch; it advances that
+    parameter's host step count), ``_launch``, and the host step count itself (``host_step`` / ``set_host_step``)."""
 
     @torch.no_grad()
     def step(self, closure=None, grad_scales=None, only=None):
@@ -41,15 +38,11 @@ class Adagrad(torch.optim.Optimizer):
                 if p.grad is None or (sel is not None and id(p) not in sel):
                     continue
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                state = self.state[p]
-                state["step"] += 1
                 keep.append(g)
                 updated.append(p)
-                items.append((dev_ptr(p.data), dev_ptr(g), dev_ptr(state["sum"]), p.numel(), float(group["lr"]),
-                              float(group["weight_decay"]), float(group["eps"]), gs))
-        if items:           # every parameter in ONE launch (lstc_adagrad_multi; element arithmetic of lstc_adagrad_step)
-            arr = (_lib.AdagradItem * len(items))(*items)
-            check(lib.lstc_adagrad_multi(arr, len(items), stream_ptr()), "lstc_adagrad_multi")
+                items.append(self._item(group, p, g, gs))
+        if items:           # every parameter in ONE launch
+            self._launch(lib, items)
         from .functional import bump_weight_epoch, repack_weights
         bump_weight_epoch(updated)   # THESE weights changed through raw pointers: their packed copies (f32x3 / bf16 GEMM) are stale
         if items and not torch.cuda.is_current_stream_capturing():
@@ -57,6 +50,127 @@ class Adagrad(torch.optim.Optimizer):
             # lazily issued packs of its forward instead: the graph replays those)
             repack_weights(updated)
         return None
+
+    def host_step(self, p) -> int:
+        """Steps taken on ``p`` as the host counts them (what ``state_dict`` reports).  engine.GraphedStep reads it, puts it back
+        after its warm-up and capture, and adds 1 per replay."""
+        return self.state[p]["step"]
+
+    def set_host_step(self, p, n: int):
+        self.state[p]["step"] = n
+
+
+class Adagrad(_MultiTensorOptimizer):
+    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10):
+        if lr_decay != 0:
+            raise NotImplementedError("lr_decay is 0 everywhere on the LSTC_VAD path")
+        defaults = dict(lr=lr, weight_decay=weight_decay, eps=eps, initial_accumulator_value=initial_accumulator_value)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                self.state[p]["sum"] = torch.full_like(p, float(group["initial_accumulator_value"]),
+                                                       memory_format=torch.preserve_format)
+                self.state[p]["step"] = 0
+
+    def _item(self, group, p, g, gs):
+        state = self.state[p]
+        state["step"] += 1
+        return (dev_ptr(p.data), dev_ptr(g), dev_ptr(state["sum"]), p.numel(), float(group["lr"]),
+                float(group["weight_decay"]), float(group["eps"]), gs)
+
+    def _launch(self, lib, items):          # lstc_adagrad_multi; element arithmetic of lstc_adagrad_step
+        arr = (_lib.AdagradItem * len(items))(*items)
+        check(lib.lstc_adagrad_multi(arr, len(items), stream_ptr()), "lstc_adagrad_multi")
+
+
+class Adam(_MultiTensorOptimizer):
+    """``torch.optim.Adam(params, lr, betas, eps, weight_decay)`` with ``amsgrad=False, maximize=False`` (include/lstc_hip.h,
+    lstc_adam_multi, states the arithmetic).  State per parameter, under torch's keys: ``exp_avg``, ``exp_avg_sq`` and ``step`` -
+    here a 0-dim view of ONE int32 device tensor holding every parameter's count, which the launch itself increments.  The host
+    keeps its own count per parameter (``host_step``) so that ``state_dict()`` needs no device read; ``state_dict()`` emits and
+    ``load_state_dict()`` accepts ``step`` the way torch writes it (a 0-dim float tensor), parameters that were never stepped
+    have no entry, as in torch: a state saved by either optimizer loads into the other."""
+    _torch_twin = torch.optim.Adam
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not implemented (lstc_adam_multi keeps no running maximum)")
+        # torch's own argument checks and its param-group keys (foreach, capturable, ...): a state_dict passes either way
+        defaults = dict(self._torch_twin([torch.empty(0)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
+        self._words = None
+        super().__init__(params, defaults)
+        plist = [p for group in self.param_groups for p in group["params"]]
+        dev = plist[0].device
+        self._words = torch.zeros(len(plist), dtype=torch.int32, device=dev)
+        self._lr_scale = torch.ones(1, dtype=torch.float32, device=dev)
+        self._host_step = {}
+        for i, p in enumerate(plist):
+            self._host_step[p] = 0
+            self.state[p] = {"step": self._words[i], "exp_avg": torch.zeros_like(p, memory_format=torch.contiguous_format),
+                             "exp_avg_sq": torch.zeros_like(p, memory_format=torch.contiguous_format)}
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_words", None) is not None:
+            raise NotImplementedError("param groups are fixed at construction: the step words are one device tensor")
+        super().add_param_group(param_group)
+
+    def set_lr_scale(self, x: float):
+        """lr_t = lr * x from the next step on, eager or captured: every launch reads this one device word (a schedule's hook)."""
+        self._lr_scale.fill_(float(x))
+
+    def host_step(self, p) -> int:
+        return self._host_step[p]
+
+    def set_host_step(self, p, n: int):
+        self._host_step[p] = n
+
+    def _item(self, group, p, g, gs):
+        st = self.state[p]
+        b1, b2 = group["betas"]
+        decoupled = bool(group.get("decoupled_weight_decay", self._torch_twin is torch.optim.AdamW))
+        item = (dev_ptr(p.data), dev_ptr(g), dev_ptr(st["exp_avg"]), dev_ptr(st["exp_avg_sq"]), p.numel(), dev_ptr(st["step"]),
+                dev_ptr(self._lr_scale), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                float(group["weight_decay"]), gs, int(decoupled))
+        self._host_step[p] += 1
+        return item
+
+    def _launch(self, lib, items):
+        arr = (_lib.AdamItem * len(items))(*items)
+        check(lib.lstc_adam_multi(arr, len(items), stream_ptr()), "lstc_adam_multi")
+
+    def _ordered(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        dt = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32       # torch's scalar dtype for `step`
+        for k, p in enumerate(self._ordered()):
+            t = self._host_step[p]
+            if t == 0:
+                sd["state"].pop(k, None)
+            else:
+                sd["state"][k] = dict(sd["state"][k], step=torch.tensor(float(t), dtype=dt))
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)          # deep copies, cast to each parameter's device and dtype; `step` as saved
+        for i, p in enumerate(self._ordered()):
+            st = self.state[p]
+            t = int(st["step"]) if "step" in st else 0
+            self._words[i] = t
+            self._host_step[p] = t
+            st["step"] = self._words[i]
+            for key in ("exp_avg", "exp_avg_sq"):
+                st[key] = (st[key].contiguous() if key in st else torch.zeros_like(p, memory_format=torch.contiguous_format))
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW``: the weight is shrunk by ``1 - lr_t * weight_decay`` before the Adam update instead of the decay
+    joining the gradient."""
+    _torch_twin = torch.optim.AdamW
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0) -> torch.Tensor:
