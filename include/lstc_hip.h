@@ -734,6 +734,46 @@ typedef struct LstcAdamItem {
     int32_t decoupled;        /* 0: Adam (wd added to the gradient), 1: AdamW (w *= 1 - lr_t * wd first) */
 } LstcAdamItem;
 int lstc_adam_multi(const LstcAdamItem* items, int32_t count, void* stream);
+
+/* An exponential moving average of EVERY weight of the step in one launch (Polyak averaging; the update of
+ * torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn, with TensorFlow's optional num_updates warm-up) - `items` is a
+ * HOST array that rides in the kernel arguments, 48 per launch, like lstc_adam_multi's.  Nothing that changes from update to
+ * update is passed by value, so a captured launch can be replayed: the update count t is the item's DEVICE word `count` (the
+ * call adds 1 to it with a one-thread-per-item launch in front of the update, then every workgroup reads the new value).
+ * Each item owns its word.
+ *
+ * Per item:  t == 1: the update is a bit copy, avg = w (AveragedModel at n_averaged == 0).
+ *            t >  1: decay_t = warmup ? min(decay, (1 + u) / (10 + u)) : decay  with u = t - 1, and  a = 1 - decay_t,
+ *                    in float64 from the f32 field widened, rounded ONCE to f32.
+ * Per element, f32, one rounding per operation, in this order (no contraction):
+ *     avg = avg + a * (w - avg)
+ * (Adam's m update; torch.lerp(avg, w, a) for a < 0.5).  The result of an element does not depend on pointer alignment (float4
+ * accesses when avg and w are both 16-byte aligned, scalar ones otherwise) nor on how a list is split into calls.
+ *
+ * Refused before any launch: count < 0, items == NULL with count > 0, a NULL avg / w / count, n < 0, two items sharing one
+ * word, avg == w with n > 0 (LSTC_E_SHAPE); decay outside [0, 1) or not finite, warmup other than 0 or 1 (LSTC_E_RANGE).
+ * An item with n == 0 updates nothing; its word is still incremented.  count == 0 does nothing. */
+typedef struct LstcEmaItem {
+    float* avg;               /* the average, updated in place */
+    const float* w;           /* the weight, read only */
+    int64_t n;
+    int32_t* count;           /* DEVICE word of this item: the call adds 1 to it, then uses the new value as t */
+    float decay;              /* in [0, 1) */
+    int32_t warmup;           /* 0 / 1 */
+} LstcEmaItem;
+int lstc_ema_multi(const LstcEmaItem* items, int32_t count, void* stream);
+
+/* a[i] <-> b[i], bit for bit, for every item in one launch (48 per launch; `items` is a HOST array that rides in the kernel
+ * arguments); any alignment.  It puts averaged weights INTO the live parameter storage for an evaluation and takes them out
+ * again, so views of that storage and raw pointers held elsewhere stay valid.
+ * Refused before any launch (LSTC_E_SHAPE): count < 0, items == NULL with count > 0, a NULL a / b, n < 0, a == b with n > 0.
+ * An item with n == 0 and count == 0 do nothing. */
+typedef struct LstcSwapItem {
+    float* a;
+    float* b;
+    int64_t n;
+} LstcSwapItem;
+int lstc_swap_multi(const LstcSwapItem* items, int32_t count, void* stream);
 /* out[0] += sum(x^2) (f32 atomics over workgroup partials; caller zeroes) — for clip_grad_norm_. */
 int lstc_sqnorm_accum(const float* x, int64_t n, float* out, void* stream);
 

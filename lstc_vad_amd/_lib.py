@@ -28,7 +28,7 @@ EXPORTS = (
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_cls_concat_len_fwd", "lstc_cls_concat_len_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
-    "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_adam_multi", "lstc_sqnorm_accum", "lstc_scale",
+    "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_adam_multi", "lstc_ema_multi", "lstc_swap_multi", "lstc_sqnorm_accum", "lstc_scale",
     "lstc_sqnorm_multi_scratch", "lstc_sqnorm_multi", "lstc_clip_scale_multi",
     "lstc_gather_rows", "lstc_expand_rows", "lstc_cast_f32_bf16", "lstc_cast_bf16_f32", "lstc_pack3", "lstc_pack3_bytes", "lstc_pack1", "lstc_pack1_multi", "lstc_pack1_bytes", "lstc_colsum_pack1", "lstc_gemm_splits",
     "lstc_version", "lstc_strerror",
@@ -102,6 +102,17 @@ class AdamItem(C.Structure):
                 ("step", C.c_void_p), ("lr_scale", C.c_void_p),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("grad_scale", C.c_float), ("decoupled", C.c_int32)]
+
+
+class EmaItem(C.Structure):
+    """LstcEmaItem (include/lstc_hip.h)."""
+    _fields_ = [("avg", C.c_void_p), ("w", C.c_void_p), ("n", C.c_int64), ("count", C.c_void_p),
+                ("decay", C.c_float), ("warmup", C.c_int32)]
+
+
+class SwapItem(C.Structure):
+    """LstcSwapItem (include/lstc_hip.h)."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("n", C.c_int64)]
 
 
 class VecItem(C.Structure):
@@ -212,6 +223,8 @@ def load():
         "lstc_adagrad_step": [vp, vp, vp, i64, f32, f32, f32, f32, vp],
         "lstc_adagrad_multi": [C.POINTER(AdagradItem), i32, vp],
         "lstc_adam_multi": [C.POINTER(AdamItem), i32, vp],
+        "lstc_ema_multi": [C.POINTER(EmaItem), i32, vp],
+        "lstc_swap_multi": [C.POINTER(SwapItem), i32, vp],
         "lstc_sqnorm_accum": [vp, i64, vp, vp],
         "lstc_scale": [vp, i64, f32, vp],
         "lstc_sqnorm_multi_scratch": [C.POINTER(VecItem), i32],

@@ -17,6 +17,7 @@ Under ``torchrun`` ``--batch_size`` stays the global pair count; rank r owns pai
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import logging
 import os
@@ -108,6 +109,13 @@ class Selector:
             self.best_test, self.best_test_epoch, auc_test, self.best_train, self.best_train_epoch, auc_train)]
 
 
+def _ema_decay(text: str) -> float:
+    d = float(text)
+    if not 0.0 <= d < 1.0:          # NaN fails too
+        raise argparse.ArgumentTypeError("must be in [0, 1)")
+    return d
+
+
 def build_parser(script: str) -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog=script + ".py", description=f"MI355X drop-in for the reference Train/{script}.py")
     for flag, kind, default in _FLAGS[script]:
@@ -136,6 +144,12 @@ def build_parser(script: str) -> argparse.ArgumentParser:
     p.add_argument("--adam_beta1", type=float, default=0.9, help="--optimizer adam / adamw: decay of the first-moment average")
     p.add_argument("--adam_beta2", type=float, default=0.999, help="--optimizer adam / adamw: decay of the second-moment average")
     p.add_argument("--adam_eps", type=float, default=1e-8, help="--optimizer adam / adamw: the denominator's epsilon")
+    p.add_argument("--ema_decay", type=_ema_decay, default=0.0,
+                   help="0 = off.  In (0, 1): keep an exponential moving average of every weight (one lstc_ema_multi launch "
+                        "behind the optimizer's); evaluations and every checkpoint written use the AVERAGED weights, training "
+                        "itself is unchanged")
+    p.add_argument("--ema_warmup", action="store_true",
+                   help="--ema_decay: ramp the decay up, min(decay, (1 + u) / (10 + u)) at update u + 1")
     p.add_argument("--resident_eval", action="store_true",
                    help="evaluation and pseudo-label passes score from HBM: the test / label set is uploaded once "
                         "(pipeline.ResidentSet), the train-AUC pass reads the training bank already there, and every pass describes "
@@ -382,8 +396,13 @@ def train(script: str, argv=None, args=None):
     opt_kw = None if opt_name == "adagrad" else dict(betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps)
     if opt_kw and rank == 0:
         logger.info("--optimizer %s: betas (%g, %g), eps %g, weight_decay %g" % (opt_name, args.adam_beta1, args.adam_beta2, args.adam_eps, args.weight_decay))
+    ema_decay, ema_warmup = float(getattr(args, "ema_decay", 0.0) or 0.0), bool(getattr(args, "ema_warmup", False))
+    if ema_decay and rank == 0:
+        logger.info("--ema_decay %g%s: evaluations and checkpoints use the averaged weights" % (ema_decay, " with warm-up" if ema_warmup else ""))
     ts = TrainStep(step_args, mode, enc, head, _get(args, "lr_encoder", pre, 1e-4), lr_head, args.weight_decay,
-                   optimizer=opt_name, optimizer_kw=opt_kw)
+                   optimizer=opt_name, optimizer_kw=opt_kw, ema_decay=ema_decay, ema_warmup=ema_warmup)
+    # --ema_decay: the model holds its averaged weights inside this block (evaluation, checkpoints) and the trained ones behind it
+    averaged = ts.ema.averaged if ts.ema is not None else contextlib.nullcontext
 
     if script == "spatio_transformer_MIL_CE":
         # round 0 (the only round: `for round_i in range(1)`, Train/spatio_transformer_MIL_CE.py:113-116) trains the STN on
@@ -444,24 +463,25 @@ def train(script: str, argv=None, args=None):
             # EVERY rank evaluates: the videos of the test (and train) list are sharded over the ranks (pipeline._ScoreBoard) and
             # every rank ends up with the same AUCs, so no rank sits in a collective while another scores the whole list; rank 0
             # alone logs and writes the checkpoints
-            torch.cuda.synchronize(); t_e = _time.perf_counter()
-            auc_test, auc_train = eval_fn()
-            torch.cuda.synchronize(); t_eval += _time.perf_counter() - t_e
-            enc.train(); head.train()
-            save_auc, lines = sel.update(epoch, auc_test, auc_train)
-            if rank != 0:
-                save_auc, lines = None, []
-            if save_auc is not None:
-                t_s = _time.perf_counter()
-                logger.info("saving model......")
-                enc_path, head_path = checkpoint_names(script, args, save_auc)
-                if not (getattr(args, "model_save_dir", "") or ""):                   # no directory given: next to the log
-                    enc_path, head_path = os.path.join(log_dir, enc_path), os.path.join(log_dir, head_path)
-                os.makedirs(os.path.dirname(enc_path) or ".", exist_ok=True)
-                torch.save(enc.state_dict(), enc_path)
-                torch.save(head.state_dict(), head_path)
-                logger.info("save complete.")
-                t_save += _time.perf_counter() - t_s
+            with averaged():
+                torch.cuda.synchronize(); t_e = _time.perf_counter()
+                auc_test, auc_train = eval_fn()
+                torch.cuda.synchronize(); t_eval += _time.perf_counter() - t_e
+                enc.train(); head.train()
+                save_auc, lines = sel.update(epoch, auc_test, auc_train)
+                if rank != 0:
+                    save_auc, lines = None, []
+                if save_auc is not None:
+                    t_s = _time.perf_counter()
+                    logger.info("saving model......")
+                    enc_path, head_path = checkpoint_names(script, args, save_auc)
+                    if not (getattr(args, "model_save_dir", "") or ""):                   # no directory given: next to the log
+                        enc_path, head_path = os.path.join(log_dir, enc_path), os.path.join(log_dir, head_path)
+                    os.makedirs(os.path.dirname(enc_path) or ".", exist_ok=True)
+                    torch.save(enc.state_dict(), enc_path)
+                    torch.save(head.state_dict(), head_path)
+                    logger.info("save complete.")
+                    t_save += _time.perf_counter() - t_s
             for ln in lines:
                 logger.info(ln)
             if rank == 0:
@@ -478,8 +498,9 @@ def train(script: str, argv=None, args=None):
                     save_s=t_save,
                     snippets_per_step=2 * args.batch_size * args.part_num * part_len, world=world)
     if rank == 0 and getattr(args, "save_final", ""):
-        torch.save(enc.state_dict(), args.save_final + "encoder.ckpt")
-        torch.save(head.state_dict(), args.save_final + "head.ckpt")
+        with averaged():
+            torch.save(enc.state_dict(), args.save_final + "encoder.ckpt")
+            torch.save(head.state_dict(), args.save_final + "head.ckpt")
     if script == "spatio_transformer_MIL_CE" and real and getattr(args, "temporal_pseudo_path", ""):
         # end of the round (Train/spatio_transformer_MIL_CE.py:392-414): RE-LOAD --spatio_model_path / --regression_model_path
         # (the files, not the weights just trained - upstream expects the user's best checkpoint there) and write the next

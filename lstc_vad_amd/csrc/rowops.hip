@@ -991,11 +991,19 @@ template <int NS> struct MultiBatch {         // NS state tensors beside the wei
     int first_wg[ADA_MAX + 1];
     int count;
 };
+template <> struct MultiBatch<0> {            // no state: the Op updates `w` from `g` alone
+    float* w[ADA_MAX];
+    const float* g[ADA_MAX];
+    long long n[ADA_MAX];
+    int first_wg[ADA_MAX + 1];
+    int count;
+};
 struct AdaBatch : MultiBatch<1> {
     float lr[ADA_MAX], wd[ADA_MAX], eps[ADA_MAX], gscale[ADA_MAX];
 };
 struct AdagradOp {
     static constexpr int NS = 1;
+    static constexpr bool HAS_G = true;
     float lr, wd, eps, gscale;
     __device__ AdagradOp(const AdaBatch& b, int t) : lr(b.lr[t]), wd(b.wd[t]), eps(b.eps[t]), gscale(b.gscale[t]) {}
     __device__ __forceinline__ void elem(float& w, float g, float& s, float&) const {
@@ -1027,6 +1035,7 @@ __device__ __forceinline__ double pow_f64(double b, unsigned e) {
 }
 struct AdamOp {
     static constexpr int NS = 2;
+    static constexpr bool HAS_G = true;
     float omb1, b2, omb2, step, rsb2, eps, wd, gscale, keep;
     bool decoupled;
     __device__ AdamOp(const AdamBatch& b, int i) {
@@ -1053,50 +1062,108 @@ struct AdamOp {
     }
 };
 
+// The exponential moving average of a weight (lstc_ema_multi, include/lstc_hip.h): `w` of the shared loops is the average, `g` the
+// weight it follows, there is no state tensor.  t is the item's count word (ema_tick_kernel has added 1 to it, earlier in stream
+// order).  t == 1 copies the weight's bits; after that a = (float)(1 - decay_t) is formed in float64 per workgroup, with
+// decay_t = warmup ? min(decay, (1 + u) / (10 + u)) : decay and u = t - 1, and the element is  avg = avg + a * (w - avg)  in f32.
+struct EmaBatch : MultiBatch<0> {
+    int* step[ADA_MAX];
+    float decay[ADA_MAX];
+    unsigned long long warmup;                // bit i: item i ramps its decay up
+};
+static_assert(sizeof(EmaBatch) <= 4096, "the items must fit the kernel-argument segment");
+struct EmaOp {
+    static constexpr int NS = 0;
+    static constexpr bool HAS_G = true;
+    float a;
+    bool first;
+    __device__ EmaOp(const EmaBatch& b, int i) {
+        const int* __restrict__ word = b.step[i];
+        const unsigned t = (unsigned)*word;                                  // uniform address: one scalar load per workgroup
+        double d = (double)b.decay[i];
+        if ((b.warmup >> i) & 1ull) {
+            const double u = (double)(t - 1u);
+            d = fmin(d, (1.0 + u) / (10.0 + u));
+        }
+        a = (float)(1.0 - d);
+        first = t == 1u;
+    }
+    __device__ __forceinline__ void elem(float& avg, float w, float&, float&) const { avg = first ? w : avg + a * (w - avg); }
+};
+
+// lstc_swap_multi: `w` and the one state tensor trade their bits; no gradient operand.
+struct SwapBatch : MultiBatch<1> {};
+struct SwapOp {
+    static constexpr int NS = 1;
+    static constexpr bool HAS_G = false;
+    __device__ SwapOp(const SwapBatch&, int) {}
+    __device__ __forceinline__ void elem(float& a, float, float& b, float&) const {
+        const float x = a;
+        a = b;
+        b = x;
+    }
+};
+
+template <int K, int NS> __device__ __forceinline__ float* state_ptr(const MultiBatch<NS>& b, int t) {
+    if constexpr (K >= 0 && K < NS) return b.s[K][t];
+    else return nullptr;
+}
+// element i of an operand the Op has, else a stand-in that is never used
+template <bool Have, class T> __device__ __forceinline__ T operand(const T* p, int64_t i, const T& absent) {
+    if constexpr (Have) return p[i];
+    else return absent;
+}
 template <class Op, class Batch> __device__ __forceinline__ void multi_tensor_update(const Batch& b) {
-    constexpr bool two = Op::NS > 1;
+    constexpr bool one = Op::NS > 0, two = Op::NS > 1, grad = Op::HAS_G;
     int t = 0;
     while (t + 1 < b.count && (int)blockIdx.x >= b.first_wg[t + 1]) ++t;          // wave-uniform scan (scalar loads of the arguments)
     float* __restrict__ w = b.w[t];
     const float* __restrict__ g = b.g[t];
-    float* __restrict__ s = b.s[0][t];
-    float* __restrict__ s2 = b.s[Op::NS - 1][t];          // the second state tensor (Op::NS == 2), else `s` again and unused
+    float* __restrict__ s = state_ptr<0>(b, t);           // nullptr and never touched when Op::NS == 0
+    float* __restrict__ s2 = state_ptr<Op::NS - 1>(b, t); // the second state tensor (Op::NS == 2), else `s` again and unused
     const int64_t n = b.n[t];
     const Op op(b, t);
     const int64_t e0 = (int64_t)((int)blockIdx.x - b.first_wg[t]) * ADA_PER_WG;
     const int64_t e1 = min(n, e0 + ADA_PER_WG);
-    const bool vec = aligned16(w) && aligned16(g) && aligned16(s) && aligned16(s2);
+    const bool vec = aligned16(w) && aligned16(g) && aligned16(s) && aligned16(s2);          // an absent operand is nullptr: aligned
     if (vec) {
         const int64_t v1 = e1 == n ? (n >> 2) : (e1 >> 2);
         for (int64_t i = (e0 >> 2) + threadIdx.x; i < v1; i += NT) {
-            float4 wv = reinterpret_cast<float4*>(w)[i], sv = reinterpret_cast<float4*>(s)[i];
+            float4 wv = reinterpret_cast<float4*>(w)[i], sv;
+            if constexpr (one) sv = reinterpret_cast<float4*>(s)[i];
+            else sv = wv;
             float4 tv = sv;
             if constexpr (two) tv = reinterpret_cast<float4*>(s2)[i];
-            const float4 gv = reinterpret_cast<const float4*>(g)[i];
+            const float4 gv = operand<grad>(reinterpret_cast<const float4*>(g), i, wv);
             op.elem(wv.x, gv.x, sv.x, tv.x);
             op.elem(wv.y, gv.y, sv.y, tv.y);
             op.elem(wv.z, gv.z, sv.z, tv.z);
             op.elem(wv.w, gv.w, sv.w, tv.w);
             reinterpret_cast<float4*>(w)[i] = wv;
-            reinterpret_cast<float4*>(s)[i] = sv;
+            if constexpr (one) reinterpret_cast<float4*>(s)[i] = sv;
             if constexpr (two) reinterpret_cast<float4*>(s2)[i] = tv;
         }
         if (e1 != n) return;
     }
     // fully scalar when a pointer is unaligned; else the tensor's last 0-3 elements (its last workgroup only)
     for (int64_t i = (vec ? (n >> 2) * 4 : e0) + threadIdx.x; i < e1; i += NT) {
-        float wv = w[i], sv = s[i], tv = sv;
+        float wv = w[i], sv = operand<one>(s, i, wv), tv = sv;
         if constexpr (two) tv = s2[i];
-        op.elem(wv, g[i], sv, tv);
-        s[i] = sv;
+        op.elem(wv, operand<grad>(g, i, wv), sv, tv);
+        if constexpr (one) s[i] = sv;
         if constexpr (two) s2[i] = tv;
         w[i] = wv;
     }
 }
 __global__ void __launch_bounds__(NT) adagrad_multi_kernel(const AdaBatch b) { multi_tensor_update<AdagradOp>(b); }
 __global__ void __launch_bounds__(NT) adam_multi_kernel(const AdamBatch b) { multi_tensor_update<AdamOp>(b); }
+__global__ void __launch_bounds__(NT) ema_multi_kernel(const EmaBatch b) { multi_tensor_update<EmaOp>(b); }
+__global__ void __launch_bounds__(NT) swap_multi_kernel(const SwapBatch b) { multi_tensor_update<SwapOp>(b); }
 // t = ++*step of every item of the launch, n == 0 items included; one thread per item, in front of adam_multi_kernel
 __global__ void __launch_bounds__(64) adam_tick_kernel(const AdamBatch b) {
+    if ((int)threadIdx.x < b.count) *b.step[threadIdx.x] += 1;
+}
+__global__ void __launch_bounds__(64) ema_tick_kernel(const EmaBatch b) {          // the same, in front of ema_multi_kernel
     if ((int)threadIdx.x < b.count) *b.step[threadIdx.x] += 1;
 }
 
@@ -1691,6 +1758,38 @@ int lstc_adam_multi(const LstcAdamItem* items, int32_t count, void* stream) {
     }, [](const AdamBatch& b, int wg, hipStream_t st) {
         hipLaunchKernelGGL(adam_tick_kernel, dim3(1), 64, 0, st, b);
         if (wg > 0) hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);          // wg == 0: only empty items
+    });
+}
+
+int lstc_ema_multi(const LstcEmaItem* items, int32_t count, void* stream) {
+    if (count < 0 || (!items && count > 0)) return LSTC_E_SHAPE;
+    std::vector<const int32_t*> words((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        const LstcEmaItem& it = items[i];
+        if (!it.avg || !it.w || !it.count || it.n < 0 || (it.avg == it.w && it.n > 0)) return LSTC_E_SHAPE;
+        if (!(it.decay >= 0.f) || !(it.decay < 1.f) || (it.warmup != 0 && it.warmup != 1)) return LSTC_E_RANGE;          // NaN fails both
+        words[(size_t)i] = it.count;
+    }
+    std::sort(words.begin(), words.end());
+    if (std::adjacent_find(words.begin(), words.end()) != words.end()) return LSTC_E_SHAPE;          // every item owns its word
+    return multi_tensor_launch<EmaBatch>(items, count, stream, [](EmaBatch& b, int i, const LstcEmaItem& it) {
+        if (i == 0) b.warmup = 0;
+        b.w[i] = it.avg; b.g[i] = it.w; b.step[i] = it.count; b.decay[i] = it.decay;
+        if (it.warmup) b.warmup |= 1ull << i;
+    }, [](const EmaBatch& b, int wg, hipStream_t st) {
+        hipLaunchKernelGGL(ema_tick_kernel, dim3(1), 64, 0, st, b);
+        if (wg > 0) hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);          // wg == 0: only empty items
+    });
+}
+
+int lstc_swap_multi(const LstcSwapItem* items, int32_t count, void* stream) {
+    if (count < 0 || (!items && count > 0)) return LSTC_E_SHAPE;
+    for (int32_t i = 0; i < count; ++i)
+        if (!items[i].a || !items[i].b || items[i].n < 0 || (items[i].a == items[i].b && items[i].n > 0)) return LSTC_E_SHAPE;
+    return multi_tensor_launch<SwapBatch>(items, count, stream, [](SwapBatch& b, int i, const LstcSwapItem& it) {
+        b.w[i] = it.a; b.g[i] = nullptr; b.s[0][i] = it.b;
+    }, [](const SwapBatch& b, int wg, hipStream_t st) {
+        if (wg > 0) hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);
     });
 }
 

@@ -15,13 +15,14 @@ import torch.distributed as dist
 
 from .dist import GradAllReducer, direct_grad_parameters, encoder_head_buckets
 from .losses import training_loss
-from .optim import Adagrad, Adam, AdamW, clip_grad_norm_
+from .optim import EMA, Adagrad, Adam, AdamW, clip_grad_norm_
 
 
 class TrainStep:
     def __init__(self, args, mode: str, encoder, head, lr_encoder: float, lr_head: float, weight_decay: float,
                  group=None, cls_only: bool = True, loss_rank=None, loss_exchange=None, fuse_qkv="auto",
-                 grad_reduce_dtype: str = "fp32", n_buckets=None, optimizer: str = "adagrad", optimizer_kw=None):
+                 grad_reduce_dtype: str = "fp32", n_buckets=None, ema_decay=None, ema_warmup: bool = False,
+                 optimizer: str = "adagrad", optimizer_kw=None):
         # cls_only=False evaluates the last encoder layer for every token like the reference does (its extra rows are
         # never read); kept for A/B measurements — results are identical (tests/test_hip_parity.py)
         self.cls_only = cls_only
@@ -49,6 +50,9 @@ class TrainStep:
         groups = [{"params": encoder.parameters(), "lr": lr_encoder}, {"params": head.parameters(), "lr": lr_head}]
         self.optimizer = (Adagrad(groups, weight_decay=weight_decay) if optimizer == "adagrad" else
                           (Adam if optimizer == "adam" else AdamW)(groups, weight_decay=weight_decay, **(optimizer_kw or {})))
+        # an averaged model beside the trained one (optim.EMA): one more launch behind the optimizer's, over the same parameters.
+        # Off (None or 0) by default: nothing is allocated and no launch is added
+        self.ema = EMA(self.optimizer.param_groups, decay=ema_decay, warmup=ema_warmup) if ema_decay else None
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         force = os.environ.get("LSTC_FORCE_DIST", "0") == "1" and dist.is_available() and dist.is_initialized()
         # measurement hook (bench.py at N > 1): a list to receive (before backward, after backward, after reducer.finish()) HIP events
@@ -61,6 +65,7 @@ class TrainStep:
         # fp32 36.95 -> 37.15; full batch bf16 39.1 -> 39.4).  What it is FOR - stepping six of seven buckets under the exposed wait for the
         # last reduction over xGMI - needs N > 1 devices to show.
         self.bucket_steps = os.environ.get("LSTC_BUCKET_STEPS", "0") == "1"
+        self._ema_seen = set()
         # default bucketing: head, then per layer (last to first) its FFN half and its attention half - 2 x layers + 1 buckets of
         # <= 67 MB at the LTN widths.  Only the LAST bucket's reduction (layer 0's attention weights, ready when the backward ends)
         # cannot hide under the backward; halving it halves what is exposed, and 67 MB is still far above the size at which
@@ -142,7 +147,8 @@ class TrainStep:
             # per-bucket optimizer: Adagrad + the bf16 weight repack of bucket k run on a side stream as soon as
             # bucket k's reduction has landed, beside the backward of the layers below - not behind the LAST bucket's reduction.
             # (--clip_grad needs the norm of ALL gradients first: it keeps the one-step order below.)
-            self.reducer.finish(on_bucket=lambda bi, params: self.optimizer.step(only=params))
+            self.reducer.finish(on_bucket=self._bucket_step)
+            self._ema_rest()
             if ev is not None:
                 # exposed communication keeps its meaning: end of the backward -> the LAST bucket's reduction has landed
                 marks[2] = self.reducer.landed if self.reducer.landed is not None else marks[1]
@@ -157,7 +163,25 @@ class TrainStep:
             clip_grad_norm_(self.encoder.parameters(), 10)
             clip_grad_norm_(self.head.parameters(), 10)
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
         return scalars
+
+    def _bucket_step(self, bi, params):
+        """One gradient bucket, on the stream the reducer calls it on: the optimizer, then the average of the same weights."""
+        self.optimizer.step(only=params)
+        if self.ema is not None:
+            self.ema.update(only=params)
+            self._ema_seen.update(id(p) for p in params)
+
+    def _ema_rest(self):
+        """Behind the per-bucket steps: the parameters no bucket holds (they never change) still count the update."""
+        if self.ema is None:
+            return
+        rest = [p for p in self.ema.params if id(p) not in self._ema_seen]
+        self._ema_seen.clear()
+        if rest:
+            self.ema.update(only=rest)
 
 
 class GraphedStep:
@@ -201,6 +225,10 @@ class GraphedStep:
         # whatever tensors the optimizer keeps per parameter (Adagrad: sum; Adam: exp_avg, exp_avg_sq and the device step word)
         keep_s = [{k: v.clone() for k, v in ts.optimizer.state[p].items() if torch.is_tensor(v)} for p in params]
         keep_n = [ts.optimizer.host_step(p) for p in params]
+        # the averages and their count words (ts.ema): saved and put back like the optimizer's state
+        ema = getattr(ts, "ema", None)
+        keep_e = [] if ema is None else [{k: v.clone() for k, v in ema.state[p].items()} for p in ema.params]
+        keep_c = [] if ema is None else [ema.host_count(p) for p in ema.params]
         c0 = Fn._counter
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -216,7 +244,11 @@ class GraphedStep:
                 for k, v in s_.items():
                     ts.optimizer.state[p][k].copy_(v)
                 ts.optimizer.set_host_step(p, n)
-        del keep_w, keep_s
+            for p, s_, n in zip(ema.params if ema is not None else [], keep_e, keep_c):
+                for k, v in s_.items():
+                    ema.state[p][k].copy_(v)
+                ema.set_host_count(p, n)
+        del keep_w, keep_s, keep_e
         Fn.bump_weight_epoch()
         Fn.reset_rng(c0)
         # 2. capture one step; the seeds drawn here are baked in by value and offset by the device word at run time
@@ -233,6 +265,8 @@ class GraphedStep:
                     clip_grad_norm_(ts.encoder.parameters(), 10)
                     clip_grad_norm_(ts.head.parameters(), 10)
                 ts.optimizer.step()
+                if ema is not None:
+                    ema.update()                      # in front of the seed-word bump: the word add stays the last node
                 self.seed_word.add_(self.seeds_per_step)
         finally:
             _lib.check(lib.lstc_dropout_seed_device(None), "lstc_dropout_seed_device")
@@ -242,6 +276,8 @@ class GraphedStep:
         Fn.reset_rng(c0)                      # nothing ran: the first replay IS the step with these seeds
         for p, n in zip(params, keep_n):
             ts.optimizer.set_host_step(p, n)
+        for p, n in zip(ema.params if ema is not None else [], keep_c):
+            ema.set_host_count(p, n)
         # eager Adagrad.step skips parameters without a gradient (LayerNorms the reference builds but never calls): only the
         # ones the captured step really updates get their ``step`` count bumped per replay (state_dict parity with eager runs)
         self._params = [p for p in params if p.grad is not None]
@@ -267,6 +303,9 @@ class GraphedStep:
         opt = self.ts.optimizer
         for p in self._params:          # the host's step counts (Adam: the mirror of the device words the graph incremented)
             opt.set_host_step(p, opt.host_step(p) + 1)
+        ema = getattr(self.ts, "ema", None)
+        for p in (ema.params if ema is not None else ()):          # every parameter is averaged, with or without a gradient
+            ema.set_host_count(p, ema.host_count(p) + 1)
         Fn.bump_weight_epoch()
         return self.scalars.clone()
 
@@ -315,7 +354,11 @@ class MixedStep:
         for ts, end in zip(self.steps, ends):
             if ts.reducer is not None and getattr(ts, "bucket_steps", False) and not getattr(ts.args, "clip_grad", False):
                 # per-bucket Adagrad + repack on a side stream as each reduction lands (TrainStep.step has the same arm)
-                ts.reducer.finish(on_bucket=lambda bi, params, ts=ts: ts.optimizer.step(only=params), backward_end=end)
+                if getattr(ts, "ema", None) is None:
+                    ts.reducer.finish(on_bucket=lambda bi, params, ts=ts: ts.optimizer.step(only=params), backward_end=end)
+                else:                                # ... and the average of the bucket's weights behind it
+                    ts.reducer.finish(on_bucket=ts._bucket_step, backward_end=end)
+                    ts._ema_rest()
                 if ts.comm_events:
                     m = ts.comm_events[-1]
                     m[2] = ts.reducer.landed if ts.reducer.landed is not None else m[1]
@@ -328,4 +371,6 @@ class MixedStep:
                 clip_grad_norm_(ts.encoder.parameters(), 10)
                 clip_grad_norm_(ts.head.parameters(), 10)
             ts.optimizer.step()
+            if getattr(ts, "ema", None) is not None:
+                ts.ema.update()
         return scalars

@@ -9,8 +9,14 @@ weight_decay=wd)`` (Train/temporal_transformer_shanghaitech.py:83-85) and calls 
 ``Adam`` and ``AdamW`` are ``torch.optim.Adam`` / ``torch.optim.AdamW`` (amsgrad off) on ``lstc_adam_multi``: the step count and
 the learning-rate multiplier live on the device, so a captured step (engine.GraphedStep) replays as step 2, 3, ... and follows
 a schedule set through ``set_lr_scale``.  All three share ``step(closure, grad_scales, only)`` and what follows the launch.
+
+``EMA`` is their companion: an exponential moving average of every weight, one ``lstc_ema_multi`` launch behind the optimizer's,
+and ``lstc_swap_multi`` to evaluate and save the averaged model out of the live parameter storage.
 """
 from __future__ import annotations
+
+import contextlib
+import math
 
 import torch
 
@@ -171,6 +177,122 @@ class AdamW(Adam):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+
+
+class EMA:
+    """``avg = avg + (1 - decay_t) * (w - avg)`` for every parameter in ONE launch (include/lstc_hip.h, lstc_ema_multi, states the
+    arithmetic): Polyak averaging of the weights an optimizer above steps.  The first update copies the weights
+    (``torch.optim.swa_utils.AveragedModel`` at ``n_averaged == 0``); ``warmup`` ramps the decay up as TensorFlow's
+    ``num_updates`` does, ``decay_t = min(decay, (1 + u) / (10 + u))``.  The update counts are ONE int32 device tensor that the
+    launch itself increments (``state[p]["count"]`` is its 0-dim view), so a captured update (engine.GraphedStep) replays as
+    update 2, 3, ...; the host keeps its own count per parameter and ``state_dict()`` needs no device read.
+
+    ``swap()`` exchanges parameters and averages in place (``lstc_swap_multi``), so fused Q|K|V views and raw pointers held
+    elsewhere see the averaged weights; ``averaged()`` is the context manager around an evaluation or a checkpoint."""
+
+    def __init__(self, params, decay=0.999, warmup=False):
+        self.decay, self.warmup = self._checked(decay, warmup)
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            params = [p for group in params for p in group["params"]]
+        if not params:
+            raise ValueError("EMA: no parameters")
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("EMA: parameters must be contiguous float32 tensors")
+        self.params = params
+        self._words = torch.zeros(len(params), dtype=torch.int32, device=params[0].device)
+        self._host_count = {p: 0 for p in params}
+        self.state = {p: {"count": self._words[i], "avg": p.detach().clone(memory_format=torch.contiguous_format)}
+                      for i, p in enumerate(params)}
+        self._swapped = self._inside = False
+
+    @staticmethod
+    def _checked(decay, warmup):
+        """The kernel's rules, on the host: decay in [0, 1) as a float32, warmup 0 / 1."""
+        d = float(decay)
+        if not math.isfinite(d) or not 0.0 <= d or not float(torch.tensor(d, dtype=torch.float32)) < 1.0:
+            raise ValueError(f"EMA: decay must be in [0, 1), not {decay!r}")
+        if warmup not in (False, True, 0, 1):
+            raise ValueError(f"EMA: warmup must be False or True, not {warmup!r}")
+        return d, bool(warmup)
+
+    def host_count(self, p) -> int:
+        """Updates of ``p`` as the host counts them (the mirror of its device word; engine.GraphedStep adds 1 per replay)."""
+        return self._host_count[p]
+
+    def set_host_count(self, p, n: int):
+        self._host_count[p] = n
+
+    @torch.no_grad()
+    def update(self, only=None):
+        """One update of every parameter - with or without ``.grad`` - or of the ``only`` subset (one gradient bucket, behind
+        ``optimizer.step(only=...)``): the element arithmetic does not depend on how the parameters are grouped into launches,
+        so any partition into ``only`` sets gives ONE whole update bit for bit."""
+        if self._swapped:
+            raise RuntimeError("EMA.update: the parameters hold the averages (inside averaged(), or after an odd number of swap())")
+        sel = None if only is None else {id(p) for p in only}
+        items = []
+        for p in self.params:
+            if sel is not None and id(p) not in sel:
+                continue
+            st = self.state[p]
+            items.append((dev_ptr(st["avg"]), dev_ptr(p.data), p.numel(), dev_ptr(st["count"]), self.decay, int(self.warmup)))
+            self._host_count[p] += 1
+        if items:
+            arr = (_lib.EmaItem * len(items))(*items)
+            check(_lib.load().lstc_ema_multi(arr, len(items), stream_ptr()), "lstc_ema_multi")
+
+    @torch.no_grad()
+    def swap(self):
+        """Parameters <-> averages, bit for bit, in one launch; then what follows every raw-pointer write to the weights."""
+        items = [(dev_ptr(p.data), dev_ptr(self.state[p]["avg"]), p.numel()) for p in self.params]
+        arr = (_lib.SwapItem * len(items))(*items)
+        check(_lib.load().lstc_swap_multi(arr, len(items), stream_ptr()), "lstc_swap_multi")
+        self._swapped = not self._swapped
+        from .functional import bump_weight_epoch, repack_weights
+        bump_weight_epoch(self.params)
+        if not torch.cuda.is_current_stream_capturing():
+            repack_weights(self.params)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """The model holds its averaged weights inside the block and its training weights again behind it."""
+        if self._inside or self._swapped:
+            raise RuntimeError("EMA.averaged: the parameters already hold the averages")
+        self._inside = True
+        try:
+            self.swap()
+            try:
+                yield self
+            finally:
+                self.swap()
+        finally:
+            self._inside = False
+
+    def state_dict(self):
+        if self._swapped:
+            raise RuntimeError("EMA.state_dict: the parameters hold the averages; leave averaged() first")
+        return {"decay": self.decay, "warmup": self.warmup, "counts": [self._host_count[p] for p in self.params],
+                "avg": [self.state[p]["avg"] for p in self.params]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if self._swapped:
+            raise RuntimeError("EMA.load_state_dict: the parameters hold the averages; leave averaged() first")
+        avg, counts = list(sd["avg"]), [int(n) for n in sd["counts"]]
+        if len(avg) != len(self.params) or len(counts) != len(self.params):
+            raise ValueError(f"EMA.load_state_dict: {len(avg)} averages and {len(counts)} counts for {len(self.params)} parameters")
+        for k, (p, a) in enumerate(zip(self.params, avg)):
+            if tuple(a.shape) != tuple(p.shape):
+                raise ValueError(f"EMA.load_state_dict: average {k} has shape {tuple(a.shape)}, its parameter {tuple(p.shape)}")
+        if any(n < 0 for n in counts):
+            raise ValueError("EMA.load_state_dict: negative count")
+        self.decay, self.warmup = self._checked(sd["decay"], sd["warmup"])
+        for p, a, n in zip(self.params, avg, counts):
+            self.state[p]["avg"].copy_(a)
+            self._host_count[p] = n
+        self._words.copy_(torch.tensor(counts, dtype=torch.int32))
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0) -> torch.Tensor:
