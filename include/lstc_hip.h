@@ -831,6 +831,20 @@ int lstc_segment_mean(const float* bank, int64_t bank_clips, const int64_t* firs
 int lstc_expand_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
                      const int32_t* map, int64_t rows, int32_t cols, void* stream);
 
+/* The mirror image of lstc_expand_rows: dst[j][u, :] = sum of src[j][order[k], :] over ptr[u] <= k < ptr[u + 1], for u < groups
+ * and j < n (1 <= n <= 3) matrices of `cols` floats per row, in ONE launch - the sums of the rows of dQ, dK, dV that share an input
+ * row, which layer 0's weight gradients contract with the distinct input rows.  A sum starts from its first row's
+ * value and adds the others left to right in f32: a group of one is a bit-for-bit copy, and the result depends on the inputs alone
+ * (no atomics).  Rows groups .. dst_rows - 1 of every destination, and the rows of empty groups, are written as zeros.  `src`,
+ * `dst`, `ld_src`, `ld_dst` are HOST arrays of n entries (device pointers; row strides in floats >= cols); the sources hold
+ * `src_rows` rows.  `order` (int32, src_rows entries: source rows sorted by group, ascending inside a group) and `ptr` (int32,
+ * groups + 1 entries) are device arrays; the kernel clamps ptr into [0, src_rows] and order into the source, so a bad table cannot
+ * fault.  Bases 16-byte aligned, cols and every row stride multiples of 4 (LSTC_E_ALIGN / LSTC_E_SHAPE); src_rows, groups >= 1,
+ * groups <= dst_rows <= 2^31 - 1; n outside 1..3 LSTC_E_SHAPE; all refusals before the launch. */
+int lstc_segment_sum_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
+                          const int32_t* order, const int32_t* ptr, int64_t src_rows, int64_t groups, int64_t dst_rows, int32_t cols,
+                          void* stream);
+
 /* --------------------------------------------------------------------------- metrics
  * Frame-level ROC-AUC of a pass without its host tail (replaces utils/eval_utils.py:21-24,139-143 - sklearn roc_curve + auc over
  * the frame scores - for passes whose frame scores only repeat row scores).  Row i has score scores[i] and covers pos[i] frames

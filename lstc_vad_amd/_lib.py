@@ -30,7 +30,7 @@ EXPORTS = (
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_cls_concat_len_fwd", "lstc_cls_concat_len_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
     "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_adam_multi", "lstc_ema_multi", "lstc_swap_multi", "lstc_sqnorm_accum", "lstc_scale",
     "lstc_sqnorm_multi_scratch", "lstc_sqnorm_multi", "lstc_clip_scale_multi",
-    "lstc_gather_rows", "lstc_expand_rows", "lstc_cast_f32_bf16", "lstc_cast_bf16_f32", "lstc_pack3", "lstc_pack3_bytes", "lstc_pack1", "lstc_pack1_multi", "lstc_pack1_bytes", "lstc_colsum_pack1", "lstc_gemm_splits",
+    "lstc_gather_rows", "lstc_expand_rows", "lstc_segment_sum_rows", "lstc_cast_f32_bf16", "lstc_cast_bf16_f32", "lstc_pack3", "lstc_pack3_bytes", "lstc_pack1", "lstc_pack1_multi", "lstc_pack1_bytes", "lstc_colsum_pack1", "lstc_gemm_splits",
     "lstc_version", "lstc_strerror",
 )
 
@@ -232,6 +232,7 @@ def load():
         "lstc_clip_scale_multi": [C.POINTER(VecItem), i32, vp, f32, vp],
         "lstc_gather_rows": [vp, i64, vp, vp, i64, i64, vp],
         "lstc_expand_rows": [vp, vp, vp, vp, i32, vp, i64, i32, vp],
+        "lstc_segment_sum_rows": [vp, vp, vp, vp, i32, vp, vp, i64, i64, i64, i32, vp],
         "lstc_cast_f32_bf16": [vp, vp, i64, vp],
         "lstc_cast_bf16_f32": [vp, vp, i64, vp],
         "lstc_pack3": [vp, i64, i64, i64, C.c_int32, vp, vp],

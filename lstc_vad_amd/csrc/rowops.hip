@@ -1318,6 +1318,49 @@ __global__ void __launch_bounds__(NT) expand_rows_kernel(ExpandArgs a, int n, co
     }
 }
 
+// The mirror image of expand_rows: dst_j[u, :] = sum of src_j[m, :] over the tokens m of group u = order[ptr[u] .. ptr[u + 1]), added
+// left to right in f32 from the first one's value (a group of one is a bit-for-bit copy, nothing depends on what shares the launch:
+// no atomics); rows groups .. dst_rows - 1 and empty groups are written as zeros.  The row sums of dQ, dK, dV that the layer-0 weight
+// gradients contract with the distinct input rows.  grid = (destination row, matrix): the group bounds and the token rows are
+// wave-uniform (scalar loads), clamped into the source - a bad table cannot fault.  A thread owns the float4 columns c and c + NT of
+// its slice and walks the group in order, four tokens x two columns = 8 loads in flight; groups are mostly 1-3 tokens long, so it is
+// the resident workgroups (8 per CU) that cover an HBM miss.  HBM-bound: (tokens + destination rows) x cols x 4 bytes.
+__device__ inline int64_t clamp_row(int64_t m, int64_t rows) { return m < 0 ? 0 : (m >= rows ? rows - 1 : m); }
+__global__ void __launch_bounds__(NT) segment_sum_rows_kernel(ExpandArgs a, const int32_t* __restrict__ order,
+                                                              const int32_t* __restrict__ ptr, int64_t src_rows, int64_t groups,
+                                                              int cols4) {
+    const int64_t u = blockIdx.x;
+    const int j = blockIdx.y;
+    const float4* __restrict__ src = a.src[j];
+    const int64_t ld = a.ld_src[j];
+    float4* __restrict__ out = a.dst[j] + u * a.ld_dst[j];
+    int64_t beg = 0, end = 0;
+    if (u < groups) {
+        beg = ptr[u];
+        end = ptr[u + 1];
+        beg = beg < 0 ? 0 : (beg > src_rows ? src_rows : beg);
+        end = end < beg ? beg : (end > src_rows ? src_rows : end);
+    }
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int c = threadIdx.x; c < cols4; c += 2 * NT) {
+        const bool two = c + NT < cols4;
+        float4 s0 = zero, s1 = zero;
+        if (beg < end) {
+            const int64_t m = clamp_row(order[beg], src_rows);
+            s0 = src[m * ld + c];
+            if (two) s1 = src[m * ld + c + NT];
+        }
+#pragma unroll 4
+        for (int64_t k = beg + 1; k < end; ++k) {
+            const int64_t m = clamp_row(order[k], src_rows);
+            s0 = vadd(s0, src[m * ld + c]);
+            if (two) s1 = vadd(s1, src[m * ld + c + NT]);
+        }
+        out[c] = s0;
+        if (two) out[c + NT] = s1;
+    }
+}
+
 // ---------------------------------------------------------------------------------- segment mean
 // out[s, p, :] = mean over the count[s] clips from first[s] of bank[., p, :] (the UCF bins), optionally divided by
 // max(||row||_2, 1e-12) (F.normalize on token rows).  One workgroup per (segment, patch); a thread owns the V's c, c + NT, .. of the
@@ -1924,6 +1967,28 @@ int lstc_expand_rows(const float* const* src, const int64_t* ld_src, float* cons
     }
     const int64_t wg = (rows + NT / 64 - 1) / (NT / 64);
     hipLaunchKernelGGL(expand_rows_kernel, dim3((unsigned)wg), NT, 0, (hipStream_t)stream, a, (int)n, map, rows, (int)(cols / 4));
+    return lstc_launch_status();
+}
+
+int lstc_segment_sum_rows(const float* const* src, const int64_t* ld_src, float* const* dst, const int64_t* ld_dst, int32_t n,
+                          const int32_t* order, const int32_t* ptr, int64_t src_rows, int64_t groups, int64_t dst_rows, int32_t cols,
+                          void* stream) {
+    if (!src || !ld_src || !dst || !ld_dst || !order || !ptr) return LSTC_E_NULL;
+    if (n < 1 || n > 3 || src_rows <= 0 || src_rows > 0x7fffffffLL || groups <= 0 || dst_rows < groups || dst_rows > 0x7fffffffLL ||
+        cols <= 0 || (cols & 3))
+        return LSTC_E_SHAPE;
+    ExpandArgs a = {};
+    for (int j = 0; j < n; ++j) {
+        if (!src[j] || !dst[j]) return LSTC_E_NULL;
+        if (ld_src[j] < cols || ld_dst[j] < cols) return LSTC_E_SHAPE;
+        if (!aligned16(src[j]) || !aligned16(dst[j]) || (ld_src[j] & 3) || (ld_dst[j] & 3)) return LSTC_E_ALIGN;
+        a.src[j] = (const float4*)src[j];
+        a.dst[j] = (float4*)dst[j];
+        a.ld_src[j] = ld_src[j] / 4;
+        a.ld_dst[j] = ld_dst[j] / 4;
+    }
+    hipLaunchKernelGGL(segment_sum_rows_kernel, dim3((unsigned)dst_rows, (unsigned)n), NT, 0, (hipStream_t)stream, a, order, ptr,
+                       src_rows, groups, (int)(cols / 4));
     return lstc_launch_status();
 }
 

@@ -71,7 +71,7 @@ class LazyRows:
     the fused gather + CLS-concat kernel (lstc_cls_concat_gather_fwd: the gathered batch is never written); everything else calls
     ``materialize()`` (lstc_gather_rows) and sees the ordinary ``[bs, rows, P, d]`` tensor."""
 
-    def __init__(self, bank, idx_flat, kind, bs, rows, uniq=None, inverse=None, n_unique=0):
+    def __init__(self, bank, idx_flat, kind, bs, rows, uniq=None, inverse=None, n_unique=0, slot_order=None):
         self.bank, self.idx_flat, self.kind, self.bs, self.rows = bank, idx_flat, kind, bs, rows
         self.shape = (bs, rows) + tuple(bank.shape[1:])
         self.device = bank.device
@@ -79,7 +79,10 @@ class LazyRows:
         # clip indices, ``inverse[i]`` the place of clip ``idx_flat[i]`` among them (both int64, beside the indices); the host knows
         # ``n_unique`` before anything is launched.  Layer 0 projects the distinct rows only (functional.DedupRows).
         self.uniq, self.inverse, self.n_unique = uniq, inverse, int(n_unique)
+        # ``slot_order``: the stable argsort of ``inverse`` (int64, from the host beside it; sorted here when it is not given)
+        self.slot_order = slot_order
         self._row_maps = {}
+        self._row_csrs = {}
 
     def row_map(self, Lc, n_cls):
         """int32 [N * (1 + Lc * P)]: for every token of the N = 2 * bs * rows / Lc sequences ``[CLS, Lc clips x P patches]`` its row in
@@ -95,6 +98,37 @@ class LazyRows:
             tok = self.inverse.view(N, Lc, 1) * P + torch.arange(P, device=self.inverse.device) + n_cls
             cls = torch.arange(N, device=self.inverse.device).view(N, 1) if n_cls == N else tok.new_zeros((N, 1))
             hit = self._row_maps[(Lc, n_cls)] = torch.cat([cls, tok.view(N, Lc * P)], 1).reshape(-1).to(torch.int32)
+        return hit
+
+    def row_csr(self, Lc, n_cls):
+        """``row_map(Lc, n_cls)`` turned round, as a CSR over the tokens: ``order`` int32 [N * S], the tokens sorted by their row of Xu
+        with the tokens of one row in ascending order, and ``ptr`` int32 [n_cls + n_unique * P + 1], row r's tokens being
+        ``order[ptr[r]:ptr[r + 1]]``.  The CLS rows come first (N groups of one token, or one group of N for a shared CLS row), then
+        for distinct clip u and patch p the clip slots that hold u, in slot order - which is token order.  Index arithmetic on the
+        device from the clip slots' stable argsort: no sort of the tokens, nothing read back."""
+        hit = self._row_csrs.get((Lc, n_cls))
+        if hit is None:
+            P, nu, dev = int(self.bank.shape[1]), self.n_unique, self.inverse.device
+            n = self.inverse.numel()
+            N, S = n // Lc, 1 + Lc * P
+            if n_cls not in (1, N):
+                raise ValueError(f"row_csr: {n_cls} CLS rows for {N} sequences (1 or {N})")
+            so = self.slot_order if self.slot_order is not None else torch.argsort(self.inverse, stable=True)
+            inv_s = self.inverse[so]                                      # ascending: the slots of distinct clip 0, then of 1, ..
+            cptr = torch.searchsorted(inv_s, torch.arange(nu + 1, device=dev))         # [nu + 1]: where clip u's slots start
+            cnt = cptr[1:] - cptr[:-1]
+            first, many = cptr[inv_s], cnt[inv_s]                         # per sorted slot: its clip's start and slot count
+            p = torch.arange(P, device=dev)
+            # sorted slot j, the t-th of clip u, patch p -> place N + first * P + p * many + t among the tokens, t = j - first
+            pos = (N + first * (P - 1) + torch.arange(n, device=dev)).view(n, 1) + p * many.view(n, 1)
+            tok = (torch.div(so, Lc, rounding_mode="floor") * S + 1 + (so % Lc) * P).view(n, 1) + p
+            order = torch.empty(N * S, device=dev, dtype=torch.int64)
+            order[:N] = torch.arange(N, device=dev) * S
+            order.scatter_(0, pos.reshape(-1), tok.reshape(-1))
+            cls = torch.arange(N, device=dev) if n_cls == N else torch.zeros(1, device=dev, dtype=torch.int64)
+            clip = (N + cptr[:-1] * P).view(nu, 1) + p * cnt.view(nu, 1)
+            ptr = torch.cat([cls, clip.reshape(-1), torch.full((1,), N * S, device=dev, dtype=torch.int64)])
+            hit = self._row_csrs[(Lc, n_cls)] = (order.to(torch.int32), ptr.to(torch.int32))
         return hit
 
     def idx(self):
@@ -161,15 +195,17 @@ class ResidentBank:
         if lazy:
             if idx.ndim != 3 or idx.shape[0] != 2:
                 raise ValueError("gather(lazy=True) takes the [2, bs, rows] index array of a normal / abnormal pair batch")
-            # indices | distinct clips (padded to the same length: the slab keeps its shape from step to step) | inverse: ONE copy
+            # indices | distinct clips (padded to the same length: the slab keeps its shape from step to step) | inverse | the stable
+            # argsort of inverse (the clip slots grouped by distinct clip, LazyRows.row_csr): ONE copy
             n = idx.size
             uniq, inverse = unique_clips(idx)
-            staged = np.zeros(3 * n, np.int64)
-            staged[:n], staged[n:n + uniq.size], staged[2 * n:] = idx.reshape(-1), uniq, inverse
+            staged = np.zeros(4 * n, np.int64)
+            staged[:n], staged[n:n + uniq.size], staged[2 * n:3 * n] = idx.reshape(-1), uniq, inverse
+            staged[3 * n:] = np.argsort(inverse, kind="stable")
             dev = self._stage([staged] + list(extras))
-            flat, more = dev[0][:n], (dev[0][n:2 * n], dev[0][2 * n:], uniq.size)
+            flat, more = dev[0][:n], (dev[0][n:2 * n], dev[0][2 * n:3 * n], uniq.size, dev[0][3 * n:])
             pair = (LazyRows(self.bank, flat, 0, idx.shape[1], idx.shape[2], *more), LazyRows(self.bank, flat, 1, idx.shape[1], idx.shape[2], *more))
-            pair[1]._row_maps = pair[0]._row_maps
+            pair[1]._row_maps, pair[1]._row_csrs = pair[0]._row_maps, pair[0]._row_csrs
             return (pair, *dev[1:])
         dev = self._stage([idx.reshape(-1)] + list(extras))
         out = self.F.gather_rows(self.bank, dev[0]).reshape(tuple(idx.shape) + tuple(self.bank.shape[1:]))

@@ -705,6 +705,9 @@ def deliver(w, g):
     return None
 
 
+WGRAD_SPLIT_MIN_ROWS = 4096     # contracted rows from which a weight gradient is throughput-bound and its K range is split
+
+
 def wgrad(dy: torch.Tensor, x: torch.Tensor, x_pack: Optional[Packed] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dW[out, in] = dy[T, out]^T @ x[T, in]  (autograd of nn.Linear's weight).  f32x3 mode: the contraction runs over the
     tokens, i.e. along the ROWS of the packs that the forward (X) and input-gradient (dY) products already made, so those
@@ -716,7 +719,7 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, x_pack: Optional[Packed] = None, ou
         raise RuntimeError(f"wgrad: out must be a contiguous float32 [{O}, {I}] tensor")
     pkind = _packed_kind()
     # split-K factor: 256x256 output tiles on the packed bf16 kernel, 128x128 everywhere else
-    s = _wgrad_split(O, I, 256 if pkind == _lib.BF16P else 128) if T >= 4096 else 1
+    s = _wgrad_split(O, I, 256 if pkind == _lib.BF16P else 128) if T >= WGRAD_SPLIT_MIN_ROWS else 1
     tr_ok = T % 128 == 0 and (pkind == _lib.BF16P or (O % 128 == 0 and I % 128 == 0))
     # a gradient that already IS a packed operand (layernorm_bwd_branch emits df packed whenever [rows, d_model] fills the tile
     # grid, whatever the width of its partner) always takes the packed TR form; the partner is packed on demand (the TR kernel
@@ -746,7 +749,7 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, x_pack: Optional[Packed] = None, ou
         raise RuntimeError(f"wgrad: packed gradient [{T}, {O}] x [{T}, {I}] does not qualify for the packed kernel")
     x3_big = pkind is not None and min(O, I) >= _x3_min[0] and T >= _x3_min[1] and T * O * I >= _x3_min[2]
     if pkind == _lib.BF16P and not x3_big:
-        s = _wgrad_split(O, I, 128) if T >= 4096 else 1       # not a packed product after all: 128x128-tile kernel
+        s = _wgrad_split(O, I, 128) if T >= WGRAD_SPLIT_MIN_ROWS else 1       # not a packed product after all: 128x128-tile kernel
     if s > 1 and (_compute_dtype == F32 or (_compute_dtype == _lib.F32X3 and not x3_big)) and \
             T % s == 0 and dy.stride(1) == 1 and x.stride(1) == 1:
         # exact-f32 kernel (also the small products of f32x3 mode): the s K-chunks are ONE batched launch into [s, O, I] partials, summed in a fixed order by
@@ -854,6 +857,28 @@ def expand_rows(srcs, dsts, row_map: torch.Tensor):
     return dsts
 
 
+def segment_sum_rows(srcs, dsts, order: torch.Tensor, ptr: torch.Tensor):
+    """dsts[j][u, :] = the sum of srcs[j][order[ptr[u]:ptr[u + 1]], :] in that order (f32, from the first row's value) for up to three
+    float32 matrices of equal width in ONE launch (``lstc_segment_sum_rows``), the mirror image of ``expand_rows``.  ``order`` int32
+    [source rows] and ``ptr`` int32 [groups + 1] on the device; destination rows behind the last group are written as zeros."""
+    n = len(srcs)
+    if n != len(dsts) or any(t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1 for t in (order, ptr)):
+        raise TypeError("segment_sum_rows: as many sources as destinations, contiguous int32 order and ptr")
+    rows, cols = srcs[0].shape
+    dst_rows, groups = dsts[0].shape[0], ptr.numel() - 1
+    for a, b in zip(srcs, dsts):
+        if a.dtype != torch.float32 or b.dtype != torch.float32 or b.dim() != 2 or tuple(a.shape) != (rows, cols) or \
+                tuple(b.shape) != (dst_rows, cols) or a.stride(1) != 1 or b.stride(1) != 1:
+            raise TypeError("segment_sum_rows: float32 matrices of one width with contiguous columns")
+    if order.numel() != rows or groups < 1 or dst_rows < groups:
+        raise RuntimeError(f"segment_sum_rows: {order.numel()} order entries for {rows} rows, {groups} groups into {dst_rows} rows")
+    ptrs = lambda ts: (C.c_void_p * n)(*[dev_ptr(t) for t in ts])
+    lds = lambda ts: (C.c_int64 * n)(*[t.stride(0) for t in ts])
+    check(_lib.load().lstc_segment_sum_rows(ptrs(srcs), lds(srcs), ptrs(dsts), lds(dsts), n, dev_ptr(order), dev_ptr(ptr), rows, groups,
+                                            dst_rows, cols, stream_ptr()), "lstc_segment_sum_rows")
+    return dsts
+
+
 # ---- layer-0 projections on the distinct rows of a batch (exact-f32 mode).  The window sampler's parts overlap whenever a video has
 # fewer clips than part_num * part_len, so the same (clip, patch) bank row sits in several sequences; layer 0 has no LayerNorm in front
 # of Q / K / V, which are therefore per-row functions of raw bank rows - equal rows in, equal rows out, bit for bit (every tile form of
@@ -867,24 +892,60 @@ def expand_rows(srcs, dsts, row_map: torch.Tensor):
 # multiple of 128, 0.24 ms = 1.26 ms, over 3 x 5.65 ms = 16.95 ms -> 0.074.
 DEDUP_MIN_SHARE = 0.075
 
+# The backward half (training, same mode and switch): the three layer-0 weight gradients dW = dQ^T X contract over all M token rows,
+# but X = Xu[row_map], so  dW = sum_u (sum of dQ[m] over the tokens m with row_map[m] = u)^T Xu[u]:  lstc_segment_sum_rows adds up the
+# rows of dQ, dK, dV (or of the fused dQ|dK|dV) that share an input row - one launch, fixed order, no atomics - and the same ``wgrad``
+# calls contract those sums with Xu, which the forward keeps for it (+ U' * d floats until the backward).  The contracted row count is
+# U' = U rounded up to DEDUP_WGRAD_PAD rows, so that every split factor of ``_wgrad_split`` (<= 16) cuts it into whole 32-row K tiles
+# and ``wgrad`` keeps its deterministic batched split (``T % s == 0``); the pad rows are exact zeros on both sides, fmaf(0, 0, acc).
+# Layer 0 needs no dX; where it does (learned CLS) the token-row gradients still feed that product.  These three gradients are the
+# same sums in another fixed order - repeats first - so they differ from LSTC_DEDUP_ROWS=0 in the last bits (the GEMM tests' bound);
+# everything else stays bitwise.  Taken when U' >= WGRAD_SPLIT_MIN_ROWS (a product ``wgrad`` treats as throughput-bound: below it the
+# weight gradient is launch latency and nothing is saved) and the saved share 1 - U / M is at least DEDUP_WGRAD_MIN_SHARE = cost of
+# what the path adds / GEMM time of the three full products, read from the kernel trace at the headline shape (M = 100352, d = 2048;
+# profiles/dedup_wgrad_kernel_stats_{parent,pr}.md): segment sum 0.78 ms (4.39 GB at 5.7 TB/s) + the CSR's index arithmetic, 33
+# launches of 4 - 7 us back to back, 0.16 ms + the zero fill of Xu's pad rows 0.005 ms + up to 511 pad rows in three products, 0.09 ms
+# = 1.04 ms, over 5.78 + 5.62 + 5.61 = 17.0 ms -> 0.061.  (The forward half's gate, 0.075, is the higher one and holds first.)
+DEDUP_WGRAD_PAD = 512
+DEDUP_WGRAD_MIN_SHARE = 0.065
+
 
 class DedupRows:
-    __slots__ = ("bank", "uniq", "n_unique", "row_map", "n_cls", "S")
+    __slots__ = ("bank", "uniq", "n_unique", "row_map", "n_cls", "S", "M", "csr")
 
-    def __init__(self, bank, uniq, n_unique, row_map, n_cls, S):
+    def __init__(self, bank, uniq, n_unique, row_map, n_cls, S, M, csr):
         self.bank, self.uniq, self.n_unique, self.row_map, self.n_cls, self.S = bank, uniq, n_unique, row_map, n_cls, S
+        self.M, self.csr = M, csr         # token rows; csr() -> (order, ptr) of feed.LazyRows.row_csr, formed when first asked for
 
     def rows(self):
         return self.n_cls + self.n_unique * int(self.bank.shape[1])
 
-    def unique_input(self, x2):
-        """Xu [n_cls + U * P, d]: the CLS rows as the concat wrote them into ``x2`` [N * S, d], then the distinct clips' rows."""
+    def wgrad_rows(self):
+        """U', the padded row count over which the backward contracts the weight gradients, or 0: they keep their token rows."""
+        padded = -(-self.rows() // DEDUP_WGRAD_PAD) * DEDUP_WGRAD_PAD
+        if padded < WGRAD_SPLIT_MIN_ROWS or 1.0 - self.rows() / float(self.M) < DEDUP_WGRAD_MIN_SHARE:
+            return 0
+        return padded
+
+    def unique_input(self, x2, padded=0):
+        """Xu [n_cls + U * P, d]: the CLS rows as the concat wrote them into ``x2`` [N * S, d], then the distinct clips' rows.
+        ``padded`` > rows(): the first rows of a [padded, d] buffer whose other rows are zeros; -> (Xu, the buffer)."""
         P, dm = int(self.bank.shape[1]), int(self.bank.shape[2])
-        xu = torch.empty((self.rows(), dm), device=x2.device, dtype=torch.float32)
+        rows = self.rows()
+        buf = torch.empty((max(rows, padded), dm), device=x2.device, dtype=torch.float32)
+        if padded > rows:
+            buf[rows:].zero_()                # torch.empty garbage times a zero gradient row could be NaN
+        xu = buf[:rows]
         cls_at = torch.arange(0, self.n_cls * self.S, self.S, device=x2.device, dtype=torch.int64)
         gather_rows(x2, cls_at, out=xu[:self.n_cls])
         gather_rows(self.bank, self.uniq[:self.n_unique], out=xu[self.n_cls:].view(self.n_unique, P, dm))
-        return xu
+        return xu, buf
+
+    def sum_rows(self, grads, padded):
+        """The [padded, .] sums of the token-row gradients ``grads`` (one width) over the tokens that share a row of Xu."""
+        order, ptr = self.csr()
+        sums = [torch.empty((padded, g.shape[1]), device=g.device, dtype=torch.float32) for g in grads]
+        return segment_sum_rows(grads, sums, order, ptr)
 
 
 _dedup_rows = {}            # _pack_key(layer-0 input) -> (tensor, version, DedupRows): one entry, consumed by the block that reads it
@@ -899,7 +960,7 @@ def _dedup_spec(lazy, idx, N, Lc, S, learned_cls, has_pos, pack_only):
     n_cls = 1 if learned_cls else N
     if 1.0 - (n_cls + lazy.n_unique * int(lazy.bank.shape[1])) / float(N * S) < DEDUP_MIN_SHARE:
         return None
-    return DedupRows(lazy.bank, lazy.uniq, lazy.n_unique, lazy.row_map(Lc, n_cls), n_cls, S)
+    return DedupRows(lazy.bank, lazy.uniq, lazy.n_unique, lazy.row_map(Lc, n_cls), n_cls, S, N * S, lambda: lazy.row_csr(Lc, n_cls))
 
 
 def _take_dedup_rows(x):
@@ -1697,6 +1758,7 @@ class MHAFunction(torch.autograd.Function):
         if seqs is not None and ((N, S) != (1, seqs.M) or cfg.get("mask") is not None):
             raise RuntimeError(f"MHAFunction: an unpadded batch is [1, M, d] = [1, {seqs.M}, d] without a mask, got {tuple(x.shape)}")
         H, dk, dv = cfg["n_head"], cfg["d_k"], cfg["d_v"]
+        ctx.dedup = None
         dedup = _take_dedup_rows(x) if seqs is None else None    # exact-f32 mode, x straight from the fused gather + CLS concat: its distinct rows
         x2 = x.contiguous().view(N * S, dm)
         xp = maybe_pack(x2)            # f32x3: one pack of X feeds Q, K, V now and the three weight gradients later
@@ -1711,7 +1773,11 @@ class MHAFunction(torch.autograd.Function):
             qkv_p = gemm(xa, wqkv, trans_b=True, out_pack=True)
             q = k = v = None
         elif dedup is not None:      # layer 0 of a batch with repeated clips: project the distinct rows, then spread them over the tokens
-            xu = dedup.unique_input(x2)
+            # training: the backward contracts the three weight gradients over Xu too (``DedupRows.wgrad_rows``) and keeps it
+            wg_rows = dedup.wgrad_rows() if cfg["training"] else 0
+            xu, xu_buf = dedup.unique_input(x2, wg_rows)
+            if wg_rows:
+                ctx.dedup = (dedup, xu_buf)
             if wqkv is not None:
                 qkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
                 expand_rows([gemm(xu, wqkv, trans_b=True)], [qkv], dedup.row_map)
@@ -1726,7 +1792,7 @@ class MHAFunction(torch.autograd.Function):
                     expand_rows(us[:2], [q, k], dedup.row_map)
                     expand_rows(us[2:], [v], dedup.row_map)
                 del us
-            del xu
+            del xu, xu_buf
         elif wqkv is not None:       # w_qs / w_ks / w_vs live in one buffer (MultiHeadAttention.fuse_qkv_): one GEMM, X read once
             qkv = gemm(xa, wqkv, trans_b=True)
             q, k, v = _cols3(qkv, H * dk, H * dk)
@@ -1788,7 +1854,13 @@ class MHAFunction(torch.autograd.Function):
                 dqkv = torch.empty((N * S, wqkv.shape[0]), device=x2.device, dtype=torch.float32)
                 _, _, _, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
                                            out=_cols3(dqkv, rq, rk), mask=c.get("mask"))
-            dwqkv = wgrad(dqkv, x2, xp, out=fused_grad_sink(wq, wk, wv))      # one TN GEMM for the three weight gradients
+            if ctx.dedup is not None:       # layer 0 on distinct rows: the rows of dQ | dK | dV that share an input row, added up
+                dedup, xu = ctx.dedup
+                gsum, = dedup.sum_rows([dqkv], xu.shape[0])
+                dwqkv = wgrad(gsum, xu, None, out=fused_grad_sink(wq, wk, wv))
+                del gsum, xu
+            else:
+                dwqkv = wgrad(dqkv, x2, xp, out=fused_grad_sink(wq, wk, wv))      # one TN GEMM for the three weight gradients
             dwq, dwk, dwv = _deliver_rows((wq, wk, wv), dwqkv)
             if ctx.needs_input_grad[0]:
                 dx = gemm(dqkv, wqkv, residual=dy).view(N, S, -1)   # dQ Wq + dK Wk + dV Wv + residual in one GEMM (K = 3*H*dk)
@@ -1799,7 +1871,14 @@ class MHAFunction(torch.autograd.Function):
                 dq, dk_, dv_, dtable = attn_bwd(do, q, k, v, probs, N, S, H, dk, dv, table, index, c["p_attn"], c["seed_a"],
                                                 packed=c.get("mask") is None and xp is not None and attn_bwd_packs(N, S, H, dk, dv),
                                                 mask=c.get("mask"))
-            dwq, dwk, dwv = _wgrad_delivered(wq, dq, x2, xp), _wgrad_delivered(wk, dk_, x2, xp), _wgrad_delivered(wv, dv_, x2, xp)
+            if ctx.dedup is not None:       # layer 0 on distinct rows: the rows of dQ, dK, dV that share an input row, added up
+                dedup, xu = ctx.dedup
+                gq, gk, gv = dedup.sum_rows([dq, dk_, dv_], xu.shape[0]) if dk == dv else \
+                    dedup.sum_rows([dq, dk_], xu.shape[0]) + dedup.sum_rows([dv_], xu.shape[0])
+                dwq, dwk, dwv = _wgrad_delivered(wq, gq, xu), _wgrad_delivered(wk, gk, xu), _wgrad_delivered(wv, gv, xu)
+                del gq, gk, gv, xu
+            else:
+                dwq, dwk, dwv = _wgrad_delivered(wq, dq, x2, xp), _wgrad_delivered(wk, dk_, x2, xp), _wgrad_delivered(wv, dv_, x2, xp)
             if ctx.needs_input_grad[0]:
                 dx = gemm(dq, wq, residual=dy)
                 gemm(dk_, wk, out=dx, accumulate=True)
