@@ -700,6 +700,44 @@ typedef struct LstcAdagradItem {
 } LstcAdagradItem;
 int lstc_adagrad_multi(const LstcAdagradItem* items, int32_t count, void* stream);
 
+/* lstc_adagrad_multi under a learning-rate schedule: the items, their checks, the 48-per-launch split and the element order are
+ * lstc_adagrad_multi's; per workgroup  lr_t = (float)((double)lr * (double)*lr_scale)  (the widening lstc_adam_multi uses) and the
+ * element runs with lr_t in place of lr.  `lr_scale` is ONE DEVICE float, read on the device by every launch of a split list, so a
+ * captured launch follows whatever lstc_lr_schedule writes there.  *lr_scale == 1.0f gives lstc_adagrad_multi's results bit for
+ * bit.  lr_scale == NULL: LSTC_E_NULL, like a NULL pointer of an item. */
+int lstc_adagrad_multi_scaled(const LstcAdagradItem* items, int32_t count, const float* lr_scale, void* stream);
+
+/* A learning-rate schedule evaluated on the device: ONE launch, one thread, does  t = *step;  *scale = f(t);  *step = t + 1
+ * (a word at INT32_MAX is not incremented).  `step` and `scale` are DEVICE words; `scale` is the multiplier lstc_adam_multi and
+ * lstc_adagrad_multi_scaled read.  t is the ZERO-based index of the optimizer step about to be taken (torch.optim.lr_scheduler's
+ * last_epoch).  The schedule itself is passed by value and nothing that changes from step to step is, so a captured launch
+ * replays as step t + 1, t + 2, ...
+ *
+ * f is evaluated in float64 from the f32 fields widened and rounded ONCE to f32.  With W = warmup_steps, T = total_steps,
+ * ws = warmup_start, m = min_scale and D = T - W:
+ *     t <  W, every kind:   f = ws + (1 - ws) * t / W
+ *     t >= W, u = min(t - W, D):
+ *         CONSTANT   f = 1
+ *         LINEAR     f = 1 - (1 - m) * u / D
+ *         COSINE     f = m + (1 - m) * 0.5 * (1 + cos(pi * u / D))
+ *         STEP       f = max(m, gamma^floor((t - W) / step_size))          (the power by repeated squaring in float64)
+ *         INV_SQRT   f = max(m, sqrt(W' / max(t, W')))  with  W' = max(W, 1)
+ * Products and quotients associate left to right as written; there is no contraction.
+ *
+ * Refused before any launch: s, step or scale NULL (LSTC_E_NULL); an unknown kind, W < 0, LINEAR or COSINE with T <= W, STEP with
+ * step_size < 1 (LSTC_E_SHAPE); ws or m outside [0, 1] or NaN, STEP with gamma outside (0, 1] or NaN (LSTC_E_RANGE). */
+enum { LSTC_LR_CONSTANT = 0, LSTC_LR_LINEAR = 1, LSTC_LR_COSINE = 2, LSTC_LR_STEP = 3, LSTC_LR_INV_SQRT = 4 };
+typedef struct LstcLrSchedule {
+    int32_t kind;             /* LSTC_LR_* */
+    int32_t warmup_steps;     /* W >= 0 */
+    int32_t total_steps;      /* T; LINEAR / COSINE need T > W; ignored otherwise */
+    int32_t step_size;        /* STEP: >= 1; ignored otherwise */
+    float warmup_start;       /* ws in [0, 1]: the scale of step 0 when W > 0 */
+    float min_scale;          /* m in [0, 1] */
+    float gamma;              /* STEP: in (0, 1] */
+} LstcLrSchedule;
+int lstc_lr_schedule(const LstcLrSchedule* s, int32_t* step, float* scale, void* stream);
+
 /* torch.optim.Adam (decoupled = 0: weight decay added to the gradient) and torch.optim.AdamW (decoupled = 1: the weight is
  * shrunk first), amsgrad = False, maximize = False, for EVERY parameter of the step in one launch - `items` is a HOST array that
  * rides in the kernel arguments, 48 per launch, like lstc_adagrad_multi's.  Nothing that changes from step to step is passed by

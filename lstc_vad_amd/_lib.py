@@ -28,7 +28,7 @@ EXPORTS = (
     "lstc_cls_outer", "lstc_cls_dot_pack", "lstc_cls_wsum_pack", "lstc_cls_outer_pack", "lstc_unpack1_rows", "lstc_splitk_finish", "lstc_layernorm_fwd", "lstc_layernorm_bwd", "lstc_layernorm_fwd_pack",
     "lstc_layernorm_bwd_drop_pack", "lstc_layernorm_bwd_drop", "lstc_layernorm_fwd_act", "lstc_layernorm_bwd_act",
     "lstc_cls_concat_fwd", "lstc_cls_concat_fwd_pack", "lstc_cls_concat_gather_fwd", "lstc_cls_concat_bwd", "lstc_cls_concat_len_fwd", "lstc_cls_concat_len_bwd", "lstc_colsum", "lstc_colsum_batched", "lstc_dropout_apply", "lstc_dropout_apply_pack", "lstc_dropout_mask", "lstc_dropout_seed_device",
-    "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_adam_multi", "lstc_ema_multi", "lstc_swap_multi", "lstc_sqnorm_accum", "lstc_scale",
+    "lstc_head_out_fwd", "lstc_head_out_bwd", "lstc_vad_loss", "lstc_adagrad_step", "lstc_adagrad_multi", "lstc_adagrad_multi_scaled", "lstc_lr_schedule", "lstc_adam_multi", "lstc_ema_multi", "lstc_swap_multi", "lstc_sqnorm_accum", "lstc_scale",
     "lstc_sqnorm_multi_scratch", "lstc_sqnorm_multi", "lstc_clip_scale_multi",
     "lstc_gather_rows", "lstc_expand_rows", "lstc_segment_sum_rows", "lstc_cast_f32_bf16", "lstc_cast_bf16_f32", "lstc_pack3", "lstc_pack3_bytes", "lstc_pack1", "lstc_pack1_multi", "lstc_pack1_bytes", "lstc_colsum_pack1", "lstc_gemm_splits",
     "lstc_version", "lstc_strerror",
@@ -108,6 +108,15 @@ class EmaItem(C.Structure):
     """LstcEmaItem (include/lstc_hip.h)."""
     _fields_ = [("avg", C.c_void_p), ("w", C.c_void_p), ("n", C.c_int64), ("count", C.c_void_p),
                 ("decay", C.c_float), ("warmup", C.c_int32)]
+
+
+class LrSchedule(C.Structure):
+    """LstcLrSchedule (include/lstc_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("warmup_steps", C.c_int32), ("total_steps", C.c_int32), ("step_size", C.c_int32),
+                ("warmup_start", C.c_float), ("min_scale", C.c_float), ("gamma", C.c_float)]
+
+
+LR_CONSTANT, LR_LINEAR, LR_COSINE, LR_STEP, LR_INV_SQRT = range(5)
 
 
 class SwapItem(C.Structure):
@@ -222,6 +231,8 @@ def load():
         "lstc_vad_loss": [C.POINTER(LossDesc), vp],
         "lstc_adagrad_step": [vp, vp, vp, i64, f32, f32, f32, f32, vp],
         "lstc_adagrad_multi": [C.POINTER(AdagradItem), i32, vp],
+        "lstc_adagrad_multi_scaled": [C.POINTER(AdagradItem), i32, vp, vp],
+        "lstc_lr_schedule": [C.POINTER(LrSchedule), vp, vp, vp],
         "lstc_adam_multi": [C.POINTER(AdamItem), i32, vp],
         "lstc_ema_multi": [C.POINTER(EmaItem), i32, vp],
         "lstc_swap_multi": [C.POINTER(SwapItem), i32, vp],

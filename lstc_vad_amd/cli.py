@@ -150,6 +150,19 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                         "itself is unchanged")
     p.add_argument("--ema_warmup", action="store_true",
                    help="--ema_decay: ramp the decay up, min(decay, (1 + u) / (10 + u)) at update u + 1")
+    p.add_argument("--lr_schedule", type=str, default="none", choices=["none", "constant", "linear", "cosine", "step", "inv_sqrt"],
+                   help="none = constant rates, nothing added.  Otherwise both learning rates are multiplied by a curve evaluated on "
+                        "the device, one lstc_lr_schedule launch in front of every step (optim.LRSchedule), with any --optimizer: "
+                        "linear warm-up over --lr_warmup_steps, then constant / linear or cosine decay to --lr_min_scale at "
+                        "--lr_total_steps / --lr_gamma every --lr_step_size steps / sqrt(warm-up / step)")
+    p.add_argument("--lr_warmup_steps", type=int, default=0, help="--lr_schedule: steps of linear warm-up")
+    p.add_argument("--lr_warmup_start", type=float, default=0.0, help="--lr_schedule: multiplier of step 0 of the warm-up, in [0, 1]")
+    p.add_argument("--lr_total_steps", type=int, default=0,
+                   help="--lr_schedule linear / cosine: the step at which --lr_min_scale is reached; 0 = the run's own length "
+                        "(--steps, else epochs x batches per epoch)")
+    p.add_argument("--lr_min_scale", type=float, default=0.0, help="--lr_schedule: the multiplier's floor, in [0, 1]")
+    p.add_argument("--lr_step_size", type=int, default=None, help="--lr_schedule step: steps between two decays")
+    p.add_argument("--lr_gamma", type=float, default=None, help="--lr_schedule step: factor of one decay, in (0, 1]")
     p.add_argument("--resident_eval", action="store_true",
                    help="evaluation and pseudo-label passes score from HBM: the test / label set is uploaded once "
                         "(pipeline.ResidentSet), the train-AUC pass reads the training bank already there, and every pass describes "
@@ -166,6 +179,31 @@ def build_parser(script: str) -> argparse.ArgumentParser:
                         "PR-AUC, the false-alarm rate at 0.5 and the score gap of all frames and, on the UCF-Crime scripts, the "
                         "per-class lines of the reference's eval_each_part and its mAP.  With or without --resident_eval")
     return p
+
+
+def lr_schedule_kw(args, epochs, data):
+    """--lr_schedule: the keywords of optim.LRSchedule (engine.TrainStep's ``lr_schedule``), or None for "none".  A linear or cosine
+    decay ends at --lr_total_steps, else at the run's own length: --steps when given, otherwise epochs x batches per epoch - and
+    where the feed cannot tell the latter the run stops here with a message: a guessed length would be a wrong curve."""
+    kind = getattr(args, "lr_schedule", "none") or "none"
+    if kind == "none":
+        return None
+    total = int(getattr(args, "lr_total_steps", 0) or 0)
+    if kind in ("linear", "cosine") and total == 0:
+        total = int(getattr(args, "steps", 0) or 0)
+        if total == 0:
+            try:
+                total = int(epochs) * len(data)
+            except TypeError:
+                raise SystemExit(f"--lr_schedule {kind} needs the length of the run and this feed cannot tell how many batches "
+                                 "an epoch has: give --lr_total_steps or --steps") from None
+    kw = dict(kind=kind, warmup_steps=int(getattr(args, "lr_warmup_steps", 0) or 0), total_steps=total or None,
+              min_scale=float(getattr(args, "lr_min_scale", 0.0) or 0.0), warmup_start=float(getattr(args, "lr_warmup_start", 0.0) or 0.0))
+    if kind == "step":
+        kw.update(step_size=getattr(args, "lr_step_size", None), gamma=getattr(args, "lr_gamma", None))
+        if kw["step_size"] is None or kw["gamma"] is None:
+            raise SystemExit("--lr_schedule step needs --lr_step_size and --lr_gamma")
+    return kw
 
 
 def _report_weights(args, dataset):
@@ -424,6 +462,14 @@ def train(script: str, argv=None, args=None):
         eval_fn = lambda: (evaluate(enc, head, mode, data, part_len, roc_auc),
                            evaluate(enc, head, mode, data, part_len, roc_auc, train=True) if SELECTION[script]["train"] else 0)
     epochs = int(_get(args, "epochs", pre, 1))
+    # --lr_schedule: attached here, behind the feed, because a decay without --lr_total_steps ends with the run
+    sched_kw = lr_schedule_kw(args, epochs, data)
+    try:
+        ts.set_lr_schedule(sched_kw)
+    except ValueError as e:
+        raise SystemExit(f"--lr_schedule: {e}") from None
+    if ts.schedule is not None and rank == 0:
+        logger.info("--lr_schedule %s" % ", ".join("%s %s" % (k, v) for k, v in ts.schedule.state_dict().items() if k != "step"))
     inter = int(getattr(args, "inter_epoch", 10))
     sel = Selector(script, args)
     it = 0
@@ -487,6 +533,10 @@ def train(script: str, argv=None, args=None):
             if rank == 0:
                 for ln in report_lines(getattr(eval_fn, "report_weights", None)):
                     logger.info(ln)
+            if rank == 0 and ts.schedule is not None:          # from the host's count and the host twin: no device read
+                n = ts.schedule.host_step()
+                logger.info("lr schedule: %d step(s) taken, scale of the last %.8g, rates %s" % (
+                    n, float(ts.schedule.scale(max(n - 1, 0))), ", ".join("%.6g" % r for r in ts.schedule.get_last_lr())))
             if rank == 0:
                 logger.info('======================================================================================')
         if args.steps and it >= args.steps:

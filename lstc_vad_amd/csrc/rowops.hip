@@ -1012,6 +1012,19 @@ struct AdagradOp {
         w -= lr * gg / (sqrtf(s) + eps);
     }
 };
+// lstc_adagrad_multi_scaled: Adagrad under a learning-rate schedule.  Per workgroup lr_t = (float)((double)lr * (double)*lr_scale),
+// Adam's widening, from ONE device float that every launch of a split list reads; the element is AdagradOp's with lr_t for lr,
+// so *lr_scale == 1.0f gives lstc_adagrad_multi's bits.
+struct AdaScaledBatch : AdaBatch {
+    const float* lr_scale;
+};
+static_assert(sizeof(AdaScaledBatch) <= 4096, "the items must fit the kernel-argument segment");
+struct AdagradScaledOp : AdagradOp {
+    __device__ AdagradScaledOp(const AdaScaledBatch& b, int t) : AdagradOp(b, t) {
+        const float* __restrict__ scale = b.lr_scale;                        // uniform address: one scalar load per workgroup
+        lr = (float)((double)lr * (double)*scale);
+    }
+};
 
 // Adam / AdamW (lstc_adam_multi, include/lstc_hip.h).  What changes from step to step is read on the device: t from the item's
 // step word (adam_tick_kernel has added 1 to it, earlier in stream order), the learning-rate multiplier from *lr_scale.  The
@@ -1165,6 +1178,33 @@ __global__ void __launch_bounds__(64) adam_tick_kernel(const AdamBatch b) {
 }
 __global__ void __launch_bounds__(64) ema_tick_kernel(const EmaBatch b) {          // the same, in front of ema_multi_kernel
     if ((int)threadIdx.x < b.count) *b.step[threadIdx.x] += 1;
+}
+__global__ void __launch_bounds__(NT) adagrad_multi_scaled_kernel(const AdaScaledBatch b) { multi_tensor_update<AdagradScaledOp>(b); }
+
+// lstc_lr_schedule (include/lstc_hip.h states the arithmetic): the learning-rate multiplier of optimizer step t, zero-based, in
+// float64 from the f32 fields widened, rounded ONCE to f32.  One thread: t = *step, *scale = f(t), *step = t + 1 (INT32_MAX stays).
+// The schedule rides by value; what changes from step to step is the device word, so a captured launch replays as t + 1, t + 2, ...
+__device__ __forceinline__ double lr_schedule_f64(const LstcLrSchedule& s, int t) {
+    const double W = (double)s.warmup_steps, ws = (double)s.warmup_start, m = (double)s.min_scale;
+    if (t < s.warmup_steps) return ws + (1.0 - ws) * (double)t / W;
+    const double D = (double)s.total_steps - W;                              // in float64: exact, and no int overflow for a T the kind ignores
+    const double u = fmin((double)(t - s.warmup_steps), D);                  // LINEAR / COSINE only: D > 0 there
+    switch (s.kind) {
+    case LSTC_LR_LINEAR: return 1.0 - (1.0 - m) * u / D;
+    case LSTC_LR_COSINE: return m + (1.0 - m) * 0.5 * (1.0 + cos(3.141592653589793 * u / D));
+    case LSTC_LR_STEP: return fmax(m, pow_f64((double)s.gamma, (unsigned)((t - s.warmup_steps) / s.step_size)));
+    case LSTC_LR_INV_SQRT: {
+        const double Wp = fmax(W, 1.0);
+        return fmax(m, sqrt(Wp / fmax((double)t, Wp)));
+    }
+    default: return 1.0;          // LSTC_LR_CONSTANT
+    }
+}
+__global__ void __launch_bounds__(64) lr_schedule_kernel(const LstcLrSchedule s, int* __restrict__ step, float* __restrict__ scale) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int t = *step;
+    *scale = (float)lr_schedule_f64(s, t);
+    if (t != 0x7fffffff) *step = t + 1;
 }
 
 // The launcher of multi_tensor_update, for every optimizer: 48 items per launch, item i of a launch owning workgroups
@@ -1777,6 +1817,35 @@ int lstc_adagrad_multi(const LstcAdagradItem* items, int32_t count, void* stream
     }, [](const AdaBatch& b, int wg, hipStream_t st) {
         hipLaunchKernelGGL(adagrad_multi_kernel, dim3((unsigned)wg), NT, 0, st, b);
     });
+}
+
+int lstc_adagrad_multi_scaled(const LstcAdagradItem* items, int32_t count, const float* lr_scale, void* stream) {
+    if (!items || !lr_scale) return LSTC_E_NULL;
+    if (count <= 0) return LSTC_E_SHAPE;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!items[i].w || !items[i].grad || !items[i].state) return LSTC_E_NULL;
+        if (items[i].n <= 0) return LSTC_E_SHAPE;
+    }
+    return multi_tensor_launch<AdaScaledBatch>(items, count, stream, [lr_scale](AdaScaledBatch& b, int i, const LstcAdagradItem& it) {
+        b.w[i] = it.w; b.g[i] = it.grad; b.s[0][i] = it.state;
+        b.lr[i] = it.lr; b.wd[i] = it.weight_decay; b.eps[i] = it.eps; b.gscale[i] = it.grad_scale;
+        b.lr_scale = lr_scale;
+    }, [](const AdaScaledBatch& b, int wg, hipStream_t st) {
+        hipLaunchKernelGGL(adagrad_multi_scaled_kernel, dim3((unsigned)wg), NT, 0, st, b);
+    });
+}
+
+int lstc_lr_schedule(const LstcLrSchedule* s, int32_t* step, float* scale, void* stream) {
+    if (!s || !step || !scale) return LSTC_E_NULL;
+    const bool decays = s->kind == LSTC_LR_LINEAR || s->kind == LSTC_LR_COSINE;
+    if (s->kind < LSTC_LR_CONSTANT || s->kind > LSTC_LR_INV_SQRT || s->warmup_steps < 0 || (decays && s->total_steps <= s->warmup_steps) ||
+        (s->kind == LSTC_LR_STEP && s->step_size < 1))
+        return LSTC_E_SHAPE;
+    const auto unit = [](float x) { return x >= 0.f && x <= 1.f; };          // NaN fails
+    if (!unit(s->warmup_start) || !unit(s->min_scale) || (s->kind == LSTC_LR_STEP && !(s->gamma > 0.f && s->gamma <= 1.f)))
+        return LSTC_E_RANGE;
+    hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), 64, 0, (hipStream_t)stream, *s, step, scale);
+    return lstc_launch_status();
 }
 
 int lstc_adam_multi(const LstcAdamItem* items, int32_t count, void* stream) {

@@ -15,14 +15,14 @@ import torch.distributed as dist
 
 from .dist import GradAllReducer, direct_grad_parameters, encoder_head_buckets
 from .losses import training_loss
-from .optim import EMA, Adagrad, Adam, AdamW, clip_grad_norm_
+from .optim import EMA, Adagrad, Adam, AdamW, LRSchedule, clip_grad_norm_
 
 
 class TrainStep:
     def __init__(self, args, mode: str, encoder, head, lr_encoder: float, lr_head: float, weight_decay: float,
                  group=None, cls_only: bool = True, loss_rank=None, loss_exchange=None, fuse_qkv="auto",
                  grad_reduce_dtype: str = "fp32", n_buckets=None, ema_decay=None, ema_warmup: bool = False,
-                 optimizer: str = "adagrad", optimizer_kw=None):
+                 lr_schedule=None, optimizer: str = "adagrad", optimizer_kw=None):
         # cls_only=False evaluates the last encoder layer for every token like the reference does (its extra rows are
         # never read); kept for A/B measurements — results are identical (tests/test_hip_parity.py)
         self.cls_only = cls_only
@@ -53,6 +53,11 @@ class TrainStep:
         # an averaged model beside the trained one (optim.EMA): one more launch behind the optimizer's, over the same parameters.
         # Off (None or 0) by default: nothing is allocated and no launch is added
         self.ema = EMA(self.optimizer.param_groups, decay=ema_decay, warmup=ema_warmup) if ema_decay else None
+        # warm-up and decay of both learning rates (optim.LRSchedule; ``lr_schedule`` is a dict of its keywords): one launch in
+        # front of everything else of a step.  Off (None) by default: nothing is allocated, no launch is added, and Adagrad
+        # keeps lstc_adagrad_multi
+        self.schedule = None
+        self.set_lr_schedule(lr_schedule)
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         force = os.environ.get("LSTC_FORCE_DIST", "0") == "1" and dist.is_available() and dist.is_initialized()
         # measurement hook (bench.py at N > 1): a list to receive (before backward, after backward, after reducer.finish()) HIP events
@@ -74,6 +79,15 @@ class TrainStep:
                                        force=force, reduce_dtype=grad_reduce_dtype,
                                        direct=direct_grad_parameters(encoder, head))
                         if (self.world > 1 or force) else None)
+
+    def set_lr_schedule(self, lr_schedule):
+        """Attach the schedule ``lr_schedule`` describes (a dict of optim.LRSchedule's keywords; None leaves things as they are)
+        before the first step - for a caller that learns the run's length only after it has built the step (cli.train)."""
+        if lr_schedule:
+            if self.schedule is not None:
+                raise RuntimeError("TrainStep: a learning-rate schedule is already attached")
+            self.schedule = LRSchedule(self.optimizer, **lr_schedule)
+        return self.schedule
 
     @staticmethod
     def _qkv_fusion_pays(args, mode, encoder) -> bool:
@@ -131,6 +145,10 @@ class TrainStep:
     def step(self, norm_feats, abnorm_feats, abnorm_labs):
         """forward, loss, backward, [gradient all-reduce], [clip], Adagrad.  Returns the 5 scalars
         (loss, MIL, err, l1, aux) as a device tensor — no host sync happens here."""
+        if self.schedule is not None:
+            # the first launch of the step, on the launch stream: in front of every side-stream bucket step, which waits for the
+            # backward behind it; ONE tick per training step however many step(only=...) launches follow
+            self.schedule.step()
         loss, scalars, _ = self.forward_loss(norm_feats, abnorm_feats, abnorm_labs)
         if self.reducer is not None:
             self.reducer.zero_grad()
@@ -229,6 +247,9 @@ class GraphedStep:
         ema = getattr(ts, "ema", None)
         keep_e = [] if ema is None else [{k: v.clone() for k, v in ema.state[p].items()} for p in ema.params]
         keep_c = [] if ema is None else [ema.host_count(p) for p in ema.params]
+        # the schedule's step word, the scale word it writes and its host count (ts.schedule): the same
+        sched = getattr(ts, "schedule", None)
+        keep_l = None if sched is None else (sched._step.clone(), sched._scale.clone(), sched.host_step())
         c0 = Fn._counter
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -248,6 +269,10 @@ class GraphedStep:
                 for k, v in s_.items():
                     ema.state[p][k].copy_(v)
                 ema.set_host_count(p, n)
+            if sched is not None:
+                sched._step.copy_(keep_l[0])
+                sched._scale.copy_(keep_l[1])
+                sched.set_host_step(keep_l[2])
         del keep_w, keep_s, keep_e
         Fn.bump_weight_epoch()
         Fn.reset_rng(c0)
@@ -259,6 +284,8 @@ class GraphedStep:
         _lib.check(lib.lstc_dropout_seed_device(self.seed_word.data_ptr()), "lstc_dropout_seed_device")
         try:
             with torch.cuda.graph(self.graph):
+                if sched is not None:
+                    sched.step()                      # the tick in front of the forward, as in TrainStep.step
                 loss, scalars, _ = ts.forward_loss(self.nf, self.af, self.al)
                 loss.backward()
                 if getattr(ts.args, "clip_grad", False):
@@ -278,6 +305,8 @@ class GraphedStep:
             ts.optimizer.set_host_step(p, n)
         for p, n in zip(ema.params if ema is not None else [], keep_c):
             ema.set_host_count(p, n)
+        if sched is not None:
+            sched.set_host_step(keep_l[2])
         # eager Adagrad.step skips parameters without a gradient (LayerNorms the reference builds but never calls): only the
         # ones the captured step really updates get their ``step`` count bumped per replay (state_dict parity with eager runs)
         self._params = [p for p in params if p.grad is not None]
@@ -306,6 +335,9 @@ class GraphedStep:
         ema = getattr(self.ts, "ema", None)
         for p in (ema.params if ema is not None else ()):          # every parameter is averaged, with or without a gradient
             ema.set_host_count(p, ema.host_count(p) + 1)
+        sched = getattr(self.ts, "schedule", None)
+        if sched is not None:                                      # the captured tick added 1 to the device word
+            sched.set_host_step(min(sched.host_step() + 1, sched.INT32_MAX))
         Fn.bump_weight_epoch()
         return self.scalars.clone()
 
@@ -327,6 +359,8 @@ class MixedStep:
         """``batches``: one ``(norm_feats, abnorm_feats, abnorm_labs)`` per TrainStep.  Returns the per-model scalar tensors."""
         scalars, ends = [], []
         for ts, (nf, af, al) in zip(self.steps, batches):
+            if getattr(ts, "schedule", None) is not None:
+                ts.schedule.step()                   # each model's tick in front of its own forward (TrainStep.step's order)
             loss, sc, _ = ts.forward_loss(nf, af, al)
             if ts.reducer is not None:
                 ts.reducer.zero_grad()

@@ -12,10 +12,14 @@ a schedule set through ``set_lr_scale``.  All three share ``step(closure, grad_s
 
 ``EMA`` is their companion: an exponential moving average of every weight, one ``lstc_ema_multi`` launch behind the optimizer's,
 and ``lstc_swap_multi`` to evaluate and save the averaged model out of the live parameter storage.
+
+``LRSchedule`` moves the one device float all three read through ``set_lr_scale``: warm-up and decay as one ``lstc_lr_schedule``
+launch in front of the step.  Adagrad allocates that float, and switches to ``lstc_adagrad_multi_scaled``, only when asked to.
 """
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 
 import torch
@@ -72,11 +76,20 @@ class Adagrad(_MultiTensorOptimizer):
             raise NotImplementedError("lr_decay is 0 everywhere on the LSTC_VAD path")
         defaults = dict(lr=lr, weight_decay=weight_decay, eps=eps, initial_accumulator_value=initial_accumulator_value)
         super().__init__(params, defaults)
+        self._lr_scale = None          # the device float of a schedule: allocated by the first set_lr_scale, never without one
         for group in self.param_groups:
             for p in group["params"]:
                 self.state[p]["sum"] = torch.full_like(p, float(group["initial_accumulator_value"]),
                                                        memory_format=torch.preserve_format)
                 self.state[p]["step"] = 0
+
+    def set_lr_scale(self, x: float):
+        """lr_t = lr * x from the next step on, eager or captured (a schedule's hook, as Adam's).  The first call allocates the
+        device float; from then on every launch is ``lstc_adagrad_multi_scaled`` and reads it (x = 1 gives the same bits)."""
+        if self._lr_scale is None:
+            dev = self.param_groups[0]["params"][0].device
+            self._lr_scale = torch.ones(1, dtype=torch.float32, device=dev)
+        self._lr_scale.fill_(float(x))
 
     def _item(self, group, p, g, gs):
         state = self.state[p]
@@ -86,7 +99,10 @@ class Adagrad(_MultiTensorOptimizer):
 
     def _launch(self, lib, items):          # lstc_adagrad_multi; element arithmetic of lstc_adagrad_step
         arr = (_lib.AdagradItem * len(items))(*items)
-        check(lib.lstc_adagrad_multi(arr, len(items), stream_ptr()), "lstc_adagrad_multi")
+        if self._lr_scale is None:
+            check(lib.lstc_adagrad_multi(arr, len(items), stream_ptr()), "lstc_adagrad_multi")
+        else:
+            check(lib.lstc_adagrad_multi_scaled(arr, len(items), dev_ptr(self._lr_scale), stream_ptr()), "lstc_adagrad_multi_scaled")
 
 
 class Adam(_MultiTensorOptimizer):
@@ -293,6 +309,137 @@ class EMA:
             self.state[p]["avg"].copy_(a)
             self._host_count[p] = n
         self._words.copy_(torch.tensor(counts, dtype=torch.int32))
+
+
+class LRSchedule:
+    """Warm-up and decay of the learning rates of an optimizer above, evaluated on the device: ONE ``lstc_lr_schedule`` launch per
+    training step reads this schedule's step word, writes ``f(t)`` into the optimizer's ``_lr_scale`` float - the multiplier every
+    ``lstc_adam_multi`` / ``lstc_adagrad_multi_scaled`` launch reads - and adds 1 to the word (include/lstc_hip.h states ``f``).
+    ``t`` is the zero-based index of the optimizer step about to be taken (torch's ``last_epoch``): call ``step()`` IN FRONT of
+    ``optimizer.step()``, once per training step however many ``step(only=...)`` bucket launches that step is made of.  Nothing
+    that changes from step to step is passed by value, so a captured step (engine.GraphedStep) replays as step t + 1, t + 2, ...
+
+    ``kind``: "constant", "linear", "cosine", "step" or "inv_sqrt".  The first ``warmup_steps`` steps ramp linearly from
+    ``warmup_start`` to 1 for every kind; "linear" and "cosine" then reach ``min_scale`` at ``total_steps`` and stay there, "step"
+    multiplies by ``gamma`` every ``step_size`` steps and "inv_sqrt" decays as sqrt(W / t), both floored at ``min_scale``.  The
+    host keeps its own count (``host_step``) and its own float64 twin of ``f`` (``scale_at``): nothing here reads the device."""
+    KINDS = ("constant", "linear", "cosine", "step", "inv_sqrt")
+    INT32_MAX = 2 ** 31 - 1
+
+    def __init__(self, optimizer, kind, warmup_steps=0, total_steps=None, min_scale=0.0, warmup_start=0.0, step_size=None,
+                 gamma=0.1):
+        self.config = self._checked(kind, warmup_steps, total_steps, min_scale, warmup_start, step_size, gamma)
+        if not hasattr(optimizer, "set_lr_scale"):
+            raise TypeError("LRSchedule: the optimizer has no set_lr_scale (optim.Adagrad, optim.Adam and optim.AdamW do)")
+        self.optimizer = optimizer
+        if getattr(optimizer, "_lr_scale", None) is None:
+            optimizer.set_lr_scale(1.0)          # Adagrad: the device float exists from here on, and its launches read it
+        self._scale = optimizer._lr_scale
+        self._step = torch.zeros(1, dtype=torch.int32, device=self._scale.device)
+        self._host = 0
+        c = self.config
+        self._desc = _lib.LrSchedule(self.KINDS.index(c["kind"]), c["warmup_steps"], c["total_steps"], c["step_size"],
+                                     c["warmup_start"], c["min_scale"], c["gamma"])
+
+    @classmethod
+    def _checked(cls, kind, warmup_steps=0, total_steps=None, min_scale=0.0, warmup_start=0.0, step_size=None, gamma=0.1):
+        """The kernel's rules, on the host; returns the configuration as the kernel's fields hold it (f32 numbers, 0 for the
+        integers a kind ignores and the caller left out)."""
+        if kind not in cls.KINDS:
+            raise ValueError(f"LRSchedule: kind must be one of {cls.KINDS}, not {kind!r}")
+        ints = {}
+        for name, v in (("warmup_steps", warmup_steps), ("total_steps", total_steps), ("step_size", step_size)):
+            v = 0 if v is None else v
+            if isinstance(v, bool) or int(v) != v or abs(int(v)) > cls.INT32_MAX:
+                raise ValueError(f"LRSchedule: {name} must be a 32-bit integer, not {v!r}")
+            ints[name] = int(v)
+        if ints["warmup_steps"] < 0:
+            raise ValueError("LRSchedule: warmup_steps must be >= 0")
+        if kind in ("linear", "cosine") and ints["total_steps"] <= ints["warmup_steps"]:
+            raise ValueError(f"LRSchedule: kind {kind!r} needs total_steps > warmup_steps, not {total_steps!r} and {warmup_steps!r}")
+        if kind == "step" and ints["step_size"] < 1:
+            raise ValueError(f"LRSchedule: kind 'step' needs step_size >= 1, not {step_size!r}")
+        f32 = lambda x: ctypes.c_float(float(x)).value          # the number the kernel's f32 field holds
+        ws, m, g = f32(warmup_start), f32(min_scale), f32(gamma)
+        if not 0.0 <= ws <= 1.0 or not 0.0 <= m <= 1.0:          # NaN fails both
+            raise ValueError(f"LRSchedule: warmup_start and min_scale must be in [0, 1], not {warmup_start!r} and {min_scale!r}")
+        if kind == "step" and not 0.0 < g <= 1.0:
+            raise ValueError(f"LRSchedule: kind 'step' needs gamma in (0, 1], not {gamma!r}")
+        return dict(kind=kind, **ints, min_scale=m, warmup_start=ws, gamma=g)
+
+    @classmethod
+    def scale_at(cls, t, kind, warmup_steps=0, total_steps=None, min_scale=0.0, warmup_start=0.0, step_size=None, gamma=0.1):
+        """The host twin of the kernel: ``f(t)`` by the same float64 expressions in the same order, rounded once, as ``np.float32``."""
+        return cls._f(cls._checked(kind, warmup_steps, total_steps, min_scale, warmup_start, step_size, gamma), t)
+
+    @staticmethod
+    def _f(c, t):
+        """``f(t)`` of a configuration ``_checked`` returned."""
+        import numpy as np
+        kind, W, T, m, ws, t = c["kind"], c["warmup_steps"], c["total_steps"], c["min_scale"], c["warmup_start"], int(t)
+        if t < W:
+            return np.float32(ws + (1.0 - ws) * float(t) / float(W))
+        D = float(T - W)
+        u = min(float(t - W), D)
+        if kind == "linear":
+            f = 1.0 - (1.0 - m) * u / D
+        elif kind == "cosine":
+            f = m + (1.0 - m) * 0.5 * (1.0 + math.cos(3.141592653589793 * u / D))
+        elif kind == "step":
+            b, e, r = c["gamma"], (t - W) // c["step_size"], 1.0
+            while e:                        # the kernel's pow_f64: repeated squaring in float64
+                if e & 1:
+                    r *= b
+                e >>= 1
+                b *= b
+            f = max(m, r)
+        elif kind == "inv_sqrt":
+            Wp = max(float(W), 1.0)
+            f = max(m, math.sqrt(Wp / max(float(t), Wp)))
+        else:
+            f = 1.0
+        return np.float32(f)
+
+    def scale(self, t):
+        """``scale_at(t)`` of this schedule (its configuration was checked at construction)."""
+        return self._f(self.config, t)
+
+    def step(self):
+        """The one launch, on the current stream: *scale = f(*step), *step += 1.  The host count follows without a device read."""
+        check(_lib.load().lstc_lr_schedule(ctypes.byref(self._desc), dev_ptr(self._step), dev_ptr(self._scale), stream_ptr()),
+              "lstc_lr_schedule")
+        self._host = min(self._host + 1, self.INT32_MAX)
+
+    def host_step(self) -> int:
+        """Ticks so far as the host counts them: the index of the NEXT optimizer step (the mirror of the device word;
+        engine.GraphedStep reads it, puts it back after its warm-up and capture, and adds 1 per replay)."""
+        return self._host
+
+    def set_host_step(self, n: int):
+        self._host = int(n)
+
+    def get_last_lr(self):
+        """The rate of every param group at the last step taken (before the first: at step 0), as torch's schedulers report it."""
+        s = float(self.scale(max(self._host - 1, 0)))
+        return [float(group["lr"]) * s for group in self.optimizer.param_groups]
+
+    def state_dict(self):
+        return dict(self.config, step=self._host)
+
+    def load_state_dict(self, sd):
+        """Continue at ``sd["step"]``: sets the device word and the host count.  The configuration must be this schedule's."""
+        theirs = {k: v for k, v in sd.items() if k != "step"}
+        try:
+            theirs = self._checked(**theirs)
+        except TypeError as e:
+            raise ValueError(f"LRSchedule.load_state_dict: {e}") from None
+        if theirs != self.config:
+            raise ValueError(f"LRSchedule.load_state_dict: the saved schedule {theirs} is not this one {self.config}")
+        n = int(sd["step"])
+        if not 0 <= n <= self.INT32_MAX:
+            raise ValueError(f"LRSchedule.load_state_dict: step {n} is no step count")
+        self._step.fill_(n)
+        self._host = n
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0) -> torch.Tensor:
